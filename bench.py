@@ -10,17 +10,23 @@ Workload = BASELINE.json configs[1]: 9x9 Go AlphaZero, n=400, 6 blocks x 64 chan
 fixed-weight network (deterministic generator, seed 0), games from the empty board.  Games shard across GPUs with no data-path
 collective: weak scaling, rank r seeds program_seed + r.
 
-After the timed region (not part of `value`) the same worker keeps playing for --game-moves more moves (default 164 = one full
-game length: 9x9 games of the synthetic net run to the 163-move cap) and the line reports MEASURED games/s = finished
-`SelfPlay true` records / wall-clock of that leg.
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` and what the timed region itself
+counted).  `--full` adds everything else, after the timed region (not part of `value`): the same worker keeps playing for
+--game-moves more moves (default 164 = one full game length: 9x9 games of the synthetic net run to the 163-move cap) and the line
+reports MEASURED games/s = finished `SelfPlay true` records / wall-clock of that leg; the one-RNG-stream leg; the roofline with
+the stand-alone tower timings; the C3 / C4 / C5 legs; the CPU baseline.
 
-    python bench.py --gpus 1 --steps K --warmup W
+`--dump-outputs DIR` writes what the last timed step computed (every game's move, the root visit counts and root value of its
+search, the games that ended in it: dump_outputs below) as DIR/<name>.npy, for comparing two builds output for output.
+
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 Rank 0 prints ONE JSON line.
 """
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -73,6 +79,59 @@ def cpu_baseline(conf, seconds):
     return out
 
 
+_MOVE = re.compile(r";[BW]\[(\d+)\]((?:[A-Z]+\[[^\]]*\])*)")
+
+
+def _record_moves(record):
+    """(action, {tag: value}) of every move of an SGF-style record `(;HEADER;B[a]P[..]V[..]R[..];W[..]..)`"""
+    return [(int(a), dict(re.findall(r"([A-Z]+)\[([^\]]*)\]", info))) for a, info in _MOVE.findall(record[2:])]
+
+
+def dump_outputs(worker, games, policy_size, out_dir, prefix=""):
+    """What the last timed step computed, as a caller of the worker receives it (the records), as float arrays:
+      last_move_action [G]        f64  action each game played in the step (-1: the game ended in the step, see game_ended)
+      last_move_visits [G, A]     f32  root visit counts of that move's search (the record's P tag)
+      last_move_root_value [G]    f64  root mean value of that search (V tag)
+      moves_in_record [G]         f64  moves of the game's record after the step
+      game_ended [G]              f64  1 where the game ended in the step (its record left the worker; the game restarted)
+      ended_length, ended_score [G] f64  length and score of that finished record (0 elsewhere)
+    Finished records leave in game order (Worker::serialSection), so the last k queued lines are the k games whose record is empty."""
+    import numpy as np
+    records = worker.peek_records(games)
+    lines = worker.pop_lines()
+    action = np.full(games, -1.0)
+    visits = np.zeros((games, policy_size), np.float32)
+    value = np.zeros(games)
+    count = np.zeros(games)
+    ended = np.zeros(games)
+    ended_length, ended_score = np.zeros(games), np.zeros(games)
+    empty = []
+    for g, rec in enumerate(records):
+        moves = _record_moves(rec)
+        count[g] = len(moves)
+        if not moves:
+            empty.append(g)
+            continue
+        a, info = moves[-1]
+        action[g] = a
+        value[g] = float(info["V"])
+        for item in filter(None, info["P"].split(",")):
+            k, c = item.split(":")
+            visits[g, int(k)] = float(c)
+    if empty:
+        if len(lines) < len(empty):
+            raise SystemExit(f"bench.py: {len(empty)} games restarted but only {len(lines)} finished records")
+        for g, line in zip(empty, lines[-len(empty):]):
+            f = line.split(" ")
+            if f[0] != "SelfPlay":
+                raise SystemExit(f"bench.py: unexpected worker line {line[:80]!r}")
+            ended[g], ended_length[g], ended_score[g] = 1.0, float(f[3]), float(f[4])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("last_move_action", action), ("last_move_visits", visits), ("last_move_root_value", value), ("moves_in_record", count),
+                      ("game_ended", ended), ("ended_length", ended_length), ("ended_score", ended_score)):
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), arr)
+
+
 def kernel_fingerprint():
     """sha256 over the device sources of libmzgpu (every .hip / .inc and every header under minizero_amd/csrc except the host-only ones, names and contents, sorted):
     what a committed counter summary was taken on.  (`.git` does not travel to the GPU box, so a commit id cannot be read there.)"""
@@ -94,6 +153,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20, help="timed moves of every game (401 cycles each)")
     ap.add_argument("--warmup", type=int, default=3, help="untimed warm-up moves")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline (games/s, one RNG stream, roofline + stand-alone tower timings, C3 / C4 / C5, CPU baseline); "
+                         "--game-moves, --one-stream-moves, --other-moves, --cpu-seconds and --no-cpu-baseline shape those legs")
     ap.add_argument("--games", type=int, default=256)
     ap.add_argument("--game-moves", type=int, default=164, help="moves of the games/s leg after the timed region (0 = skip)")
     ap.add_argument("--threads", type=int, default=0, help="host threads for the per-move work (0 = cores / ranks); does NOT change the records (see --rng-streams)")
@@ -176,10 +239,12 @@ def main():
     s1 = worker.stats()
     dt = float(grp.reduce([dt], "max")[0])
     moves, games_done = grp.reduce([s1["moves"] - s0["moves"], s1["games"] - s0["games"]], "sum")
+    if args.dump_outputs:
+        dump_outputs(worker, args.games, desc.action_size, args.dump_outputs, f"rank{rank}_" if world > 1 else "")
 
-    # ---- games/s leg: the same worker keeps playing (steady state: games at every stage of their 163 moves) ----
+    # ---- games/s leg (--full): the same worker keeps playing (steady state: games at every stage of their 163 moves) ----
     g_dt, g_games, g_moves, g_evals = 0.0, 0.0, 0.0, 0.0
-    if args.game_moves > 0:
+    if args.full and args.game_moves > 0:
         worker.pop_lines()
         grp.barrier()
         tg = time.perf_counter()
@@ -203,11 +268,11 @@ def main():
                                   float(zlib.crc32(worker.peek_records(1)[0].encode()))]
     per_rank = grp.reduce(row, "sum")
 
-    # ---- one-stream leg (not `value`): the same workload with mz_rng_streams=1, the deterministic contract of the reference's zero_num_threads=1 that every
+    # ---- one-stream leg (--full, not `value`): the same workload with mz_rng_streams=1, the deterministic contract of the reference's zero_num_threads=1 that every
     # parity test runs on — a round-to-round comparable number next to the S-stream headline.  A second worker on the same device; the first one idles (its pool sleeps)
     one_stream = None
     osm = args.steps if args.one_stream_moves < 0 else args.one_stream_moves
-    if osm > 0 and args.precision == "f32" and streams != 1:
+    if args.full and osm > 0 and args.precision == "f32" and streams != 1:
         w1 = mz.Worker(make_conf(1), desc, weights, device=device)
         w1.command("start")
         assert w1.run_cycles(max(1, args.warmup) * cpm) == max(1, args.warmup) * cpm
@@ -230,40 +295,12 @@ def main():
         # the host's noise and rotation draws for the later parts overlap the earlier ones, worker.cpp runCyclesSim).  Its GPU time
         # inside the timed region comes from HIP events recorded on the worker's own stream around every launch (worker stats:
         # ms_forward); the algorithmic work per leaf evaluation is 73.3 MFLOP of 3x3 convolutions.
-        net = worker.net()
-        ms_fwd, ms_tower, fl_tower = net.time_forward(args.games, 100)          # the stand-alone tower + heads kernels, for reference
-        ms_layer, fl_layer, bytes_layer = net.time_tower_conv(args.games, 200)  # the stand-alone per-layer kernel, for reference
         gpu_ms = s1["ms_forward"] - s0["ms_forward"]
         launches = s1["sim_launches"] - s0["sim_launches"]
-        flops_per_eval = fl_tower / args.games
-        flops_total = flops_per_eval * args.games * cpm * args.steps  # this rank's timed region
         resident = launches > 0
         if not resident:
             raise SystemExit("bench.py: the simulation kernel did not run (sim_launches == 0)")
-        achieved = flops_total / (gpu_ms * 1e-3) / 1e12
         bf = args.precision == "bf16x3"
-        # bf16x3: every product is three MFMAs (hi*hi, hi*lo, lo*hi) at the 16-bit rate: the roofline is the dense bf16 peak against the
-        # MFMA work actually issued (3 x the f32-equivalent FLOPs)
-        peak = 2500.0 if bf else F32_MFMA_PEAK_TFLOPS
-        issued = achieved * (3.0 if bf else 1.0)
-        # HBM traffic from the rocprofv3 PMC passes committed under profiles/ (FETCH_SIZE x 2 + WRITE_SIZE, KB -> bytes; the x2 on
-        # gfx950 per MI355X_MICROARCH.md, re-calibrated on a known-size copy kernel with the same 4-B/lane access, see profiles/README.md)
-        # The counters are not collected in this run (a --pmc pass is a rocprofv3 run of its own: tools/refresh_c2_pmc.sh); the summary file records which kernel
-        # SOURCES it was taken on (kernel_fingerprint below), and a file whose fingerprint is not the running build's is reported as stale, not as this build's.
-        traffic, traffic_src, traffic_stale = None, None, None
-        fp_now = kernel_fingerprint()
-        for name in ("r06_pmc_sim.json", "r05_pmc_sim.json", "r04_pmc_sim.json", "r03_pmc_sim.json", "r02_pmc_sim.json", "r01_pmc_sim.json"):
-            try:
-                j = json.load(open(os.path.join(ROOT, "profiles", name)))
-                per_cycle = j.get("bytes_per_cycle", j.get("bytes_per_step"))
-                traffic = per_cycle * cpm * args.steps / launches
-                traffic_stale = j.get("kernel_fingerprint") != fp_now
-                traffic_src = (f"profiles/{name} (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of this bench; bytes per lock-step cycle x cycles per average launch)" +
-                               (f" — STALE: taken on kernel sources {j.get('kernel_fingerprint', 'unrecorded')}, this build is {fp_now}" if traffic_stale else
-                                f"; taken on this build's kernel sources ({fp_now})"))
-                break
-            except Exception:
-                pass
         phase = {k: round((s1[k] - s0[k]) / args.steps, 4) for k in ("ms_select", "ms_env", "ms_forward", "ms_expand", "ms_move", "ms_total")}
         out = {
             "metric": "self-play leaf-evals/s (9x9 Go AlphaZero n=400)" + (" — OPT-IN bf16x3 tower, not the headline" if bf else ""), "value": value, "unit": "leaf-evals/s",
@@ -278,31 +315,62 @@ def main():
                        "ranks": [{"rank": r, "device": int(per_rank[5 * r]), "program_seed": int(per_rank[5 * r + 1]), "cpu_base": int(per_rank[5 * r + 2]),
                                   "host_threads": int(per_rank[5 * r + 3]), "first_record_crc32": int(per_rank[5 * r + 4])} for r in range(world)]},
             "moves_per_sec": moves / dt, "games_finished_in_timed_region": games_done,
-            "one_rng_stream": one_stream,
-            "games_per_sec": (g_games / g_dt) if g_dt > 0 else None,
-            "games_leg": {"moves_per_game_slot": args.game_moves, "seconds": g_dt, "games_finished": g_games, "moves": g_moves,
-                          "leaf_evals_per_sec": (g_evals / g_dt) if g_dt > 0 else None,
-                          "note": "measured after the timed region on the same workers: finished `SelfPlay true` records / wall-clock "
-                                  "(9x9 games of the synthetic net mostly run to the 163-move cap, ref go.cpp:253-254)"},
             "per_step_ms": phase,
-            "forward": {"ms_per_forward": ms_fwd, "ms_tower_per_forward": ms_tower,
-                        "per_layer_kernel": {"us_per_launch": ms_layer * 1e3, "tflops": fl_layer / (ms_layer * 1e-3) / 1e12}},
-            "roofline": {"kernel": ("sim_kernel<9,9,20,64,2,BF=true> (per game: PUCT select, Go leaf position/planes/legal mask, stem + 12 x conv3x3 64->64 as three "
-                                    "split-bf16 products on v_mfma_f32_16x16x32_bf16 with activations in LDS, heads, candidate sort, expand + backup)") if bf else
-                                   ("sim_kernel<9,9,20,64,2> (per game: PUCT select, Go leaf position/planes/legal mask, stem + 12 x conv3x3 64->64 on "
-                                    "v_mfma_f32_16x16x4_f32 with activations in LDS, heads, candidate sort, expand + backup)"),
-                         "bound": "mfma", "achieved": issued, "peak": peak, "unit": "TFLOP/s",
-                         "frac": issued / peak, "f32_equivalent_tflops": achieved, "traffic": None if bf else traffic, "traffic_source": None if bf else traffic_src, "traffic_stale": None if bf else traffic_stale,
-                         "launches": launches, "avg_launch_ms": gpu_ms / launches, "flops_per_avg_launch": flops_total / launches,
-                         "flops_per_leaf_eval": flops_per_eval, "gpu_ms_per_step": gpu_ms / args.steps,
-                         "timing": "HIP events on the worker's stream around every sim_kernel launch of the timed region (a move = three launches of 1 + 16 + 384 cycles queued back to back, so that the host's noise / rotation draws overlap them)",
-                         # per cycle, without the weights (1.9 MB: they stay in the XCDs' L2s): a children block written + one read per game
-                         "compulsory_bytes_per_avg_launch": args.games * 2.0 * 2600 * cpm * args.steps / launches,
-                         "tower_alone": {"kernel": "tower_fused<9,9,20,64> (the same tower as a stand-alone launch of 256 samples)",
-                                         "us_per_launch": ms_tower * 1e3, "achieved": fl_tower / (ms_tower * 1e-3) / 1e12,
-                                         "frac": fl_tower / (ms_tower * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS}},
         }
-        if world == 1 and args.other_moves > 0 and not bf:
+        if args.full:
+            net = worker.net()
+            ms_fwd, ms_tower, fl_tower = net.time_forward(args.games, 100)          # the stand-alone tower + heads kernels, for reference
+            ms_layer, fl_layer, bytes_layer = net.time_tower_conv(args.games, 200)  # the stand-alone per-layer kernel, for reference
+            flops_per_eval = fl_tower / args.games
+            flops_total = flops_per_eval * args.games * cpm * args.steps  # this rank's timed region
+            achieved = flops_total / (gpu_ms * 1e-3) / 1e12
+            # bf16x3: every product is three MFMAs (hi*hi, hi*lo, lo*hi) at the 16-bit rate: the roofline is the dense bf16 peak against the
+            # MFMA work actually issued (3 x the f32-equivalent FLOPs)
+            peak = 2500.0 if bf else F32_MFMA_PEAK_TFLOPS
+            issued = achieved * (3.0 if bf else 1.0)
+            # HBM traffic from the rocprofv3 PMC passes committed under profiles/ (FETCH_SIZE x 2 + WRITE_SIZE, KB -> bytes; the x2 on
+            # gfx950 per MI355X_MICROARCH.md, re-calibrated on a known-size copy kernel with the same 4-B/lane access, see profiles/README.md)
+            # The counters are not collected in this run (a --pmc pass is a rocprofv3 run of its own: tools/refresh_c2_pmc.sh); the summary file records which kernel
+            # SOURCES it was taken on (kernel_fingerprint below), and a file whose fingerprint is not the running build's is reported as stale, not as this build's.
+            traffic, traffic_src, traffic_stale = None, None, None
+            fp_now = kernel_fingerprint()
+            for name in ("r06_pmc_sim.json", "r05_pmc_sim.json", "r04_pmc_sim.json", "r03_pmc_sim.json", "r02_pmc_sim.json", "r01_pmc_sim.json"):
+                try:
+                    j = json.load(open(os.path.join(ROOT, "profiles", name)))
+                    per_cycle = j.get("bytes_per_cycle", j.get("bytes_per_step"))
+                    traffic = per_cycle * cpm * args.steps / launches
+                    traffic_stale = j.get("kernel_fingerprint") != fp_now
+                    traffic_src = (f"profiles/{name} (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes of this bench; bytes per lock-step cycle x cycles per average launch)" +
+                                   (f" — STALE: taken on kernel sources {j.get('kernel_fingerprint', 'unrecorded')}, this build is {fp_now}" if traffic_stale else
+                                    f"; taken on this build's kernel sources ({fp_now})"))
+                    break
+                except Exception:
+                    pass
+            out.update({
+                "one_rng_stream": one_stream,
+                "games_per_sec": (g_games / g_dt) if g_dt > 0 else None,
+                "games_leg": {"moves_per_game_slot": args.game_moves, "seconds": g_dt, "games_finished": g_games, "moves": g_moves,
+                              "leaf_evals_per_sec": (g_evals / g_dt) if g_dt > 0 else None,
+                              "note": "measured after the timed region on the same workers: finished `SelfPlay true` records / wall-clock "
+                                      "(9x9 games of the synthetic net mostly run to the 163-move cap, ref go.cpp:253-254)"},
+                "forward": {"ms_per_forward": ms_fwd, "ms_tower_per_forward": ms_tower,
+                            "per_layer_kernel": {"us_per_launch": ms_layer * 1e3, "tflops": fl_layer / (ms_layer * 1e-3) / 1e12}},
+                "roofline": {"kernel": ("sim_kernel<9,9,20,64,2,BF=true> (per game: PUCT select, Go leaf position/planes/legal mask, stem + 12 x conv3x3 64->64 as three "
+                                        "split-bf16 products on v_mfma_f32_16x16x32_bf16 with activations in LDS, heads, candidate sort, expand + backup)") if bf else
+                                       ("sim_kernel<9,9,20,64,2> (per game: PUCT select, Go leaf position/planes/legal mask, stem + 12 x conv3x3 64->64 on "
+                                        "v_mfma_f32_16x16x4_f32 with activations in LDS, heads, candidate sort, expand + backup)"),
+                             "bound": "mfma", "achieved": issued, "peak": peak, "unit": "TFLOP/s",
+                             "frac": issued / peak, "f32_equivalent_tflops": achieved, "traffic": None if bf else traffic, "traffic_source": None if bf else traffic_src, "traffic_stale": None if bf else traffic_stale,
+                             "launches": launches, "avg_launch_ms": gpu_ms / launches, "flops_per_avg_launch": flops_total / launches,
+                             "flops_per_leaf_eval": flops_per_eval, "gpu_ms_per_step": gpu_ms / args.steps,
+                             "timing": "HIP events on the worker's stream around every sim_kernel launch of the timed region (a move = three launches of 1 + 16 + 384 cycles queued back to back, so that the host's noise / rotation draws overlap them)",
+                             # per cycle, without the weights (1.9 MB: they stay in the XCDs' L2s): a children block written + one read per game
+                             "compulsory_bytes_per_avg_launch": args.games * 2.0 * 2600 * cpm * args.steps / launches,
+                             "tower_alone": {"kernel": "tower_fused<9,9,20,64> (the same tower as a stand-alone launch of 256 samples)",
+                                             "us_per_launch": ms_tower * 1e3, "achieved": fl_tower / (ms_tower * 1e-3) / 1e12,
+                                             "frac": fl_tower / (ms_tower * 1e-3) / 1e12 / F32_MFMA_PEAK_TFLOPS}},
+            })
+        if args.full and world == 1 and args.other_moves > 0 and not bf:
             # BASELINE configs[2..4] on the same box, same worker code as tools/run_configs.py: a fresh worker per config, a few warm-up moves,
             # then `--other-moves` timed moves (one run_cycles call per move); leaf-evals/s by wall clock, roofline by HIP events around the launches
             worker.close()
@@ -318,7 +386,7 @@ def main():
                                              **({"note": "600 timed moves (2.1 s) cross three sequence boundaries of every game: the OBS tags of 64 x 200 moves (6 MB each) are gzip-compressed on the host "
                                                          "beside the search; a leg without a boundary (150 moves, what rounds 3-5 timed) is 2-3 % faster on the same box: profiles/r06_gpu_sanitize.txt"} if key == "c5" else {}),
                                              "roofline": {k: r["roofline"][k] for k in ("kernel", "bound", "achieved", "peak", "unit", "frac", "avg_launch_ms", "launches", "launches_by_kernel", "flops_per_leaf_eval", "wall_frac")}}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del worker
             out["cpu_baseline"] = cpu_baseline(base_conf + ":program_seed=1:nn_file_name=synthetic_go_6bx64_seed0.pt", args.cpu_seconds)
         print(json.dumps(out), flush=True)

@@ -8,8 +8,8 @@ This module rebuilds exactly that from the `_tree_*` tables — the layer tree a
 and fills it with a flat parameter blob in the worker's order (`mz_net_create`).  Its forward is the identity: the tests use the file as a
 weight container for `load_model`, never as a network (the network math is pinned by tests/golden/nn_*.npz).
 
-tests/test_pt_reader.py::test_own_writer_has_the_reference_layout checks, where /root/reference exists, that the state_dict keys, shapes and
-getter values equal those of the reference's own `create_network(...)` module for every network type.
+tests/test_pt_writer.py::test_own_writer_has_the_reference_layout checks that the state_dict keys, shapes and getter values equal those of
+the reference's own `create_network(...)` module for every network type (tests/golden/ref_module_layout.json).
 """
 import numpy as np
 import torch

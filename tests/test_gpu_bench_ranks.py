@@ -25,7 +25,7 @@ def _free_port():
 def test_bench_world_size_two_on_one_gpu(mz):
     games, steps = 32, 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--game-moves", "0", "--no-cpu-baseline", "--other-moves", "0",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--full", "--game-moves", "0", "--no-cpu-baseline", "--other-moves", "0",
            "--games", str(games), "--backend", "gloo", "--device-map", "0,0", "--threads", "2"]
     env = dict(os.environ)
     env.pop("MZ_DEVICE_MAP", None)
@@ -56,7 +56,7 @@ def test_bench_world_size_eight_on_one_gpu(mz):
     whole-job value = 8 ranks' leaf evaluations over the max-over-ranks time."""
     games, steps = 8, 1
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", str(steps), "--warmup", "1", "--game-moves", "0", "--no-cpu-baseline", "--other-moves", "0",
+           os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", str(steps), "--warmup", "1", "--full", "--game-moves", "0", "--no-cpu-baseline", "--other-moves", "0",
            "--games", str(games), "--backend", "gloo", "--device-map", ",".join(["0"] * 8), "--threads", "1", "--one-stream-moves", "0"]
     env = dict(os.environ)
     env.pop("MZ_DEVICE_MAP", None)

@@ -1,7 +1,8 @@
 """The native TorchScript reader (ptfile.cpp: zip directory + the pickle subset torch.jit emits) against torch itself — CPU only.
 
-The files are scripted at test time from the REFERENCE's own Python network modules (exactly what learner/train.py:127 saves), so the
-test needs /root/reference and torch; a .pt embeds the reference's module source, so none is committed as a fixture."""
+The files are scripted at test time (exactly what learner/train.py:127 saves) from the REFERENCE's own Python network modules where
+they are present, otherwise from the repo's own module with the same layout (tests/pt_writer.py, pinned to the reference's by
+tests/test_pt_writer.py); a .pt embeds the module source, so none is committed as a fixture."""
 import os
 import sys
 
@@ -9,7 +10,17 @@ import numpy as np
 import pytest
 
 REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "minizero", "network", "py")), reason="needs the reference's Python network modules")
+
+
+def create_network(*args):
+    """The reference's create_network where its modules are present, else the same layout from tests/pt_writer.py."""
+    if os.path.isdir(os.path.join(REF, "minizero", "network", "py")):
+        sys.path.insert(0, REF)
+        from minizero.network.py.create_network import create_network as ref_create_network
+        return ref_create_network(*args)
+    import minizero_amd as mz
+    import pt_writer
+    return pt_writer.build_module(mz.make_desc(*args[:10], vh=args[10], dv=args[11], type_name="muzero_atari" if args[0].startswith("atari") else args[12]))
 
 CASES = {
     "small_go_az": ("go_9x9", 18, 9, 9, 8, 9, 9, 1, 1, 82, 16, 1, "alphazero"),
@@ -23,8 +34,6 @@ CASES = {
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_native_reader_matches_torch(mz, name, tmp_path):
     import torch
-    sys.path.insert(0, REF)
-    from minizero.network.py.create_network import create_network
     from minizero_amd.export_weights import blob_of_state_dict, desc_of_module
     torch.manual_seed(hash(name) % 1000)
     net = create_network(*CASES[name])
@@ -56,8 +65,6 @@ def test_reader_survives_corrupted_archives(mz, tmp_path):
     """Crafted / damaged files must come back as MzError, never as an out-of-bounds read: truncations, flipped bytes in the zip directory and
     in the pickle (sizes / strides / offsets), 0xFF-filled ZIP64-style fields."""
     import torch
-    sys.path.insert(0, REF)
-    from minizero.network.py.create_network import create_network
     net = create_network(*CASES["small_go_az"])
     net.eval()
     path = str(tmp_path / "good.pt")

@@ -1,15 +1,19 @@
 """tests/pt_writer.py (the repo's own TorchScript writer, used by the -m gpu iteration tests for `load_model <file>.pt`) — CPU only.
 
-With /root/reference present: the module it builds has the state_dict keys, shapes and getter values of the reference's own
-`create_network(...)` module for every network type, i.e. the file it saves is laid out like a trainer-written one.  Everywhere: the
-native reader (ptfile.cpp) gives back exactly the hyper-parameters and the blob the file was written from."""
+The module it builds has the state_dict keys, shapes and getter values of the reference's own `create_network(...)` module for every
+network type (tests/golden/ref_module_layout.json, recorded from the reference by tests/golden/gen_layout_golden.py), i.e. the file it
+saves is laid out like a trainer-written one; the native reader (ptfile.cpp) gives back exactly the hyper-parameters and the blob the
+file was written from."""
+import json
 import os
-import sys
 
 import numpy as np
 import pytest
 
-REF = "/root/reference"
+HERE = os.path.dirname(os.path.abspath(__file__))
+GETTERS = ["get_type_name", "get_game_name", "get_num_input_channels", "get_input_channel_height", "get_input_channel_width", "get_num_hidden_channels",
+           "get_hidden_channel_height", "get_hidden_channel_width", "get_num_blocks", "get_action_size", "get_num_value_hidden_channels",
+           "get_discrete_value_size"]
 CASES = {
     "ttt_az": ("tictactoe", 4, 3, 3, 16, 3, 3, 1, 2, 9, 256, 1, "alphazero"),
     "go_az": ("go_9x9", 18, 9, 9, 8, 9, 9, 1, 1, 82, 16, 1, "alphazero"),
@@ -37,21 +41,17 @@ def test_written_file_reads_back(mz, name, tmp_path):
     assert bytes(d3) == bytes(d) and np.array_equal(w3.view(np.uint32), w.view(np.uint32))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "minizero", "network", "py")), reason="needs the reference's Python network modules")
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_own_writer_has_the_reference_layout(mz, name, tmp_path):
     import torch
     import pt_writer
-    sys.path.insert(0, REF)
-    from minizero.network.py.create_network import create_network
     a = CASES[name]
-    ref = create_network(*a)
+    ref = json.load(open(os.path.join(HERE, "golden", "ref_module_layout.json")))[name]
     own = pt_writer.build_module(_desc(mz, a))
-    assert [(k, tuple(t.shape), t.dtype) for k, t in own.state_dict().items()] == [(k, tuple(t.shape), t.dtype) for k, t in ref.state_dict().items()]
-    own_s, ref_s = torch.jit.script(own), torch.jit.script(ref)
-    getters = ["get_type_name", "get_game_name", "get_num_input_channels", "get_input_channel_height", "get_input_channel_width", "get_num_hidden_channels",
-               "get_hidden_channel_height", "get_hidden_channel_width", "get_num_blocks", "get_action_size", "get_num_value_hidden_channels",
-               "get_discrete_value_size"] + ([] if a[12] == "alphazero" else ["get_num_action_feature_channels"])
+    assert [[k, list(t.shape), str(t.dtype)] for k, t in own.state_dict().items()] == ref["state_dict"]
+    own_s = torch.jit.script(own)
+    getters = GETTERS + ([] if a[12] == "alphazero" else ["get_num_action_feature_channels"])
+    assert sorted(ref["getters"]) == sorted(getters)
     for g in getters:
-        assert getattr(own_s, g)() == getattr(ref_s, g)(), g
-    assert type(own).__name__ == type(ref).__name__
+        assert getattr(own_s, g)() == ref["getters"][g], g
+    assert type(own).__name__ == ref["class"]

@@ -13,9 +13,9 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
 O=gpurun_out/refresh
 rm -rf $O; mkdir -p $O
-SHORT="--steps 4 --warmup 1 --game-moves 0 --no-cpu-baseline --other-moves 0 --one-stream-moves 0"
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
-timeout 600 python bench.py --steps 20 --warmup 5 --precision bf16x3 --no-cpu-baseline --other-moves 0 > $O/bench_bf16x3.json 2> $O/bench_bf16x3.err
+SHORT="--steps 4 --warmup 1 --full --game-moves 0 --no-cpu-baseline --other-moves 0 --one-stream-moves 0"
+timeout 600 python bench.py --steps 20 --warmup 5 --full > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --steps 20 --warmup 5 --full --precision bf16x3 --no-cpu-baseline --other-moves 0 > $O/bench_bf16x3.json 2> $O/bench_bf16x3.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python bench.py $SHORT > $O/bench_profiled.json 2> $O/stats.err
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv 2>/dev/null
 # FETCH_SIZE takes 3 of the 4 TCC slots and WRITE_SIZE 2: one pass each (MI355X_MICROARCH.md, PMC section)
