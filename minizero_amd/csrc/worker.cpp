@@ -118,19 +118,8 @@ public:
         return MZ_OK;
     }
     int runCycles(int n);
-    // mz_pipeline_lanes = 0 (automatic): a pool that plays in the lock-step mode with the device rules — a shape without a simulation-kernel instance — and whose
-    // cycle is dominated by long convolution kernels runs faster as TWO lanes on two streams: one lane's single-wave tree kernels (select, leaf, candidates, expand:
-    // ~0.3 ms per cycle with 255 CUs idle) run under the other lane's convolutions.  Measured (profiles/r06_lockstep_lanes.json): 19x19 6b x 128, 256 games, 331 GFLOP
-    // per cycle: 64.1 -> 67.1 k leaf-evals/s; 13x13 6b x 96, 73 GFLOP per cycle: 182 -> 167 k (its convolutions at 128 samples no longer fill the chip) — hence the bound.
-    bool wantsTwoLanes() const
-    {
-        if (cfg_.mz_pipeline_lanes != 0 || lanes_.size() != 1 || shared_net_ || !resident_ || sim_kernel_ || G_ < 64) { return false; }
-        const double P = double(desc_.hidden_channel_height) * desc_.hidden_channel_width, C = desc_.num_hidden_channels;
-        const double conv_flops = 2.0 * 9.0 * P * (double(desc_.num_input_channels) * C + 2.0 * desc_.num_blocks * C * C);
-        return double(G_) * conv_flops >= 2.0e11;
-    }
     int cyclesPerMove() const { return n_ + 1; }
-    int numLanes() const { return static_cast<int>(lanes_.size()); }
+    int numLanes() const { return plan_.lanes; }
     int popLine(char* buf, int cap);
     int waitLines();
     int peekRecord(int game, char* buf, int cap, const char* const* keys = nullptr, const char* const* values = nullptr, int ntags = 0);
@@ -226,7 +215,7 @@ private:
             if (up_stream) { (void)hipStreamDestroy(up_stream); }
         }
     };
-    Lane& laneOf(int g) { return *lanes_[g / lane_size_ < int(lanes_.size()) ? g / lane_size_ : int(lanes_.size()) - 1]; }
+    Lane& laneOf(int g) { return *lanes_[std::min(g / plan_.lane_size, plan_.lanes - 1)]; }
     int phase1(Lane& L, bool root_expansion, bool done, bool launch_select = true);
     int phase2(Lane& L);
     int phase2Resident(Lane& L);
@@ -234,7 +223,6 @@ private:
     void drawCycles(int b0, int b1, int noise_row);
     void drawStream(int t, int b0, int b1, int noise_row);
     int uploadRoots(Lane& L);
-    int setupDeviceGumbel();
     int cycle();
     int createActors();
     int resetAllSearches();
@@ -264,7 +252,6 @@ private:
     mz_net_desc desc_{};
     int device_ = 0, G_ = 0, A_ = 0, n_ = 0;
     std::vector<std::unique_ptr<Lane>> lanes_;
-    int lane_size_ = 1;
     std::unique_ptr<ThreadPool> threads_;
     std::vector<Game> games_;
     Rng main_rng_;
@@ -293,9 +280,6 @@ private:
     std::vector<float> noise_policy_, noise_logit_, noise_noise_;
     PhaseTrace trace_;
     int flipping_player_ = 2;
-    bool use_signal_ = true;  // wait on a pinned completion word written by a 1-thread kernel instead of hipStreamSynchronize
-    bool feat_bits_ = false; // AlphaZero leaves travel host->device as bit-packed planes (all board-game planes are 0/1)
-    bool resident_ = false;  // the whole cycle runs on the device (go_dev.hip): the host only does the RNG-ordered per-move logic
     struct DeferredInfo { int g, mover; size_t index; };
     // what the per-move host logic of one RNG stream's games leaves for the pool: with several streams (mz_rng_streams) the streams' blocks of games run side by
     // side on the pool's threads and their results are merged in stream order = game order (serialSection)
@@ -312,24 +296,19 @@ private:
     void serialGame(int g, bool want_noise, bool done, bool az, std::vector<float>& noise);
     std::vector<float> noise_scratch_;
     std::vector<DeferredInfo> deferred_; // record strings of the last move, built while the next launch runs
-    bool defer_info_ = false;
     void flushDeferred();
     struct Held { int action = -1, player = 0; bool resign = false; ActionInfo info; };
     std::vector<Held> held_;  // mz_manual_step: the decision of the completed search of every game
     bool search_done_ = false, stop_now_ = false;
     GumbelView gum_{};        // constants of the device-side Gumbel step (state pointer set per lane)
-    bool dev_gumbel_ = false; // Gumbel root logic inside the simulation kernel
-    int raw_bytes_ = 0;             // > 0: root observations travel as bytes (GameEnv::rawFeatures) and are expanded on the device
-    bool sim_root_host_ = false;    // muzero_atari on sim_kernel_mz: the root (96x96 representation) is evaluated by a lock-step cycle
-    bool root_host_pending_ = false; // ... whose outputs the next phase1 still has to turn into the root's children (host candidate lists)
+    bool root_host_pending_ = false; // plan_.sim_root_host: the root's outputs the next phase1 still has to turn into the root's children (host candidate lists)
     int syncGumbel(Lane& L, bool to_device);
-    bool sim_mz_ = false;     // MuZero board game on sim_kernel_mz (no device rules needed: the leaves have no environment)
     struct Round { int s0, R; float p_event = 0.0f; bool alt = false; }; // p_event: share of the recent moves in which a simulation of the round missed its leaf / took the second one
     std::vector<unsigned> prestat_prev_; // the counters as of the previous move (summed over the lanes)
     void adaptRounds();
     bool pairsUsable() // two workgroups per leaf (sim.hip sim_pre_pair_kernel_mz)
     {
-        if (!(cfg_.mz_sim_round_pairs && lanes_.size() == 1 && net0().pairsAvailable())) { return false; }
+        if (!(cfg_.mz_sim_round_pairs && plan_.lanes == 1 && net0().pairsAvailable())) { return false; }
         const int sharing = counted_device_ < 0 ? 1 : g_workers_on_device[counted_device_].load();
         if (sharing == 1) { return true; }
         if (!pairs_off_logged_) { // said once: otherwise nothing explains the slower rounds (an idle or not yet collected worker object on the device is enough)
@@ -339,12 +318,30 @@ private:
         return false;
     }
     bool pairs_off_logged_ = false;
-    int slab_slots_ = 0;        // hidden-state slots per game
-    std::vector<Round> rounds_; // mz_sim_rounds: the rounds of a move whose leaves are evaluated ahead (first simulation, size), from the Gumbel schedule of (n, m)
-    void planRounds();
-    SimMzMode sim_mode_;      // this worker's choice of MuZero simulation kernels (launch arguments: the network may be shared with other workers)
+    std::vector<Round> rounds_; // plan_.rounds as adaptRounds tunes them from move to move
     bool shared_net_ = false; // the network belongs to the caller (mz_worker_create_shared): load_model only renames, the caller reloads
-    bool sim_kernel_ = false; // ... and whole runs of cycles are ONE launch of the per-game simulation kernel (sim.hip)
+
+    // How this worker runs: every execution choice, resolved in one place (resolvePlan) before anything that depends on it is allocated, and fixed afterwards.
+    // None of it shows in a record.
+    struct Plan {
+        int lanes = 1, lane_size = 1;   // the games cut into `lanes` contiguous slices of lane_size (the last one may be shorter)
+        bool feat_bits = false;         // AlphaZero leaves travel host->device as bit-packed planes (all board-game planes are 0/1)
+        int raw_bytes = 0;              // > 0: root observations travel as bytes (GameEnv::rawFeatures) and are expanded on the device
+        bool resident = false;          // AlphaZero: the whole cycle runs on the device (go_dev.hip): the host only does the RNG-ordered per-move logic
+        bool sim_mz = false;            // MuZero on sim_kernel_mz (no device rules needed: the leaves have no environment)
+        bool sim_kernel = false;        // whole runs of cycles are ONE launch of a per-game simulation kernel (sim.hip): resident with an instance, or sim_mz
+        bool sim_root_host = false;     // muzero_atari on sim_kernel_mz: the root (96x96 representation) is evaluated by a lock-step cycle
+        bool dev_gumbel = false;        // Gumbel root logic inside the simulation kernel
+        bool defer_info = false;        // the record strings of a move are built while the next launch runs
+        int slab_slots = 0;             // MuZero: hidden-state slots per game
+        std::vector<Round> rounds;      // mz_sim_rounds: the rounds of a move whose leaves are evaluated ahead (first simulation, size), from the Gumbel schedule of (n, m)
+        SimMzMode sim_mode;             // the MuZero simulation kernels' launch mode (launch arguments: the network may be shared with other workers)
+        long split_min_draws = 32768;   // mz_sim_split: AlphaZero rotation draws a move needs before its launch gets a third part (MZ_SIM_SPLIT_MIN_DRAWS: tests, 0 = always)
+    };
+    Plan plan_;
+    Plan resolvePlan(int lanes) const;
+    int addLane(Net* shared, const float* weights, size_t count);
+    int allocLane(int l, const mz_search_cfg& sc);
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -353,71 +350,21 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     if (!conf || !cfg_.loadFromString(conf)) { return MZ_ERR_ARG; }
     desc_ = desc;
     device_ = device;
-    if (counted_device_ < 0 && device >= 0 && device < 64) { counted_device_ = device; g_workers_on_device[device].fetch_add(1); }
+    if (device >= 0 && device < 64) { counted_device_ = device; g_workers_on_device[device].fetch_add(1); }
     if (cfg_.nn_type_name == "muzero" && desc.type == 0) { setError("nn_type_name=muzero but the network descriptor is alphazero"); return MZ_ERR_ARG; }
     if (cfg_.zero_num_parallel_games <= 0 || cfg_.actor_num_simulation <= 0) { setError("zero_num_parallel_games and actor_num_simulation must be > 0"); return MZ_ERR_ARG; }
     if (cfg_.zero_num_parallel_games > 4096) { setError("zero_num_parallel_games > 4096 (ref alphazero_network.h:120 kReserved_batch_size)"); return MZ_ERR_ARG; }
+    if (cfg_.mz_nn_precision != "f32" && cfg_.mz_nn_precision != "bf16x3") { setError("mz_nn_precision '%s' unknown (f32 | bf16x3)", cfg_.mz_nn_precision.c_str()); return MZ_ERR_ARG; }
+    if (shared && shared->device_ != device) { setError("worker: the shared network lives on device %d, the worker on %d", shared->device_, device); return MZ_ERR_ARG; }
     G_ = cfg_.zero_num_parallel_games;
     A_ = desc.action_size;
     n_ = cfg_.actor_num_simulation;
     flipping_player_ = (cfg_.actor_mcts_value_flipping_player == 'B' || cfg_.actor_mcts_value_flipping_player == 'b') ? 1
                        : (cfg_.actor_mcts_value_flipping_player == 'W' || cfg_.actor_mcts_value_flipping_player == 'w') ? 2 : 3;
-    mz_search_cfg sc{};
-    sc.num_simulation = n_;
-    sc.puct_base = cfg_.actor_mcts_puct_base;
-    sc.puct_init = cfg_.actor_mcts_puct_init;
-    sc.reward_discount = cfg_.actor_mcts_reward_discount;
-    sc.value_rescale = cfg_.actor_mcts_value_rescale;
-    sc.flipping_player = flipping_player_;
-    sc.atari_init_q = cfg_.atari_init_q;
-    int nl = std::max(1, cfg_.mz_pipeline_lanes); // (0 = automatic: one lane here; mz_worker_create asks wantsTwoLanes() afterwards)
-    if (G_ < 2 * nl || shared) { nl = 1; } // a shared network has one stream: one lane
     shared_net_ = shared != nullptr;
-    lane_size_ = (G_ + nl - 1) / nl;
-    lanes_.clear();
-    for (int l = 0; l < nl; ++l) {
-        auto L = std::make_unique<Lane>();
-        L->g0 = l * lane_size_;
-        L->n = std::min(lane_size_, G_ - L->g0);
-        int rc = MZ_OK;
-        if (shared) {
-            if (shared->device_ != device) { setError("worker: the shared network lives on device %d, the worker on %d", shared->device_, device); return MZ_ERR_ARG; }
-            L->net = shared;
-        } else {
-            L->own_net = std::make_unique<Net>();
-            L->net = L->own_net.get();
-            if ((rc = L->net->init(device, desc, weights, count))) { return rc; }
-        }
-        if (cfg_.mz_nn_precision != "f32" && cfg_.mz_nn_precision != "bf16x3") { setError("mz_nn_precision '%s' unknown (f32 | bf16x3)", cfg_.mz_nn_precision.c_str()); return MZ_ERR_ARG; }
-        // (a shared network keeps the precision its owner chose with mz_net_set_precision)
-        if (!shared && (rc = L->net->setPrecision(cfg_.mz_nn_precision == "bf16x3" ? 1 : 0))) { return rc; }
-        if (!cfg_.mz_sim_cluster || nl > 1) { sim_mode_.cluster = false; } // two lanes = two concurrent cooperative launches: not with clusters that wait for each other
-        L->stream = L->net->stream_;
-        // ref actor_group.cpp:183: tree_node_size = (n + 1) * action_size; tree.h:66: 1 + tree_node_size nodes
-        rc = L->pool.init(device, L->n, 1 + (n_ + 1) * A_, A_, sc, L->stream);
-        if (rc) { return rc; }
-        // kernels talk to the pinned staging directly: no memcpy operations on the per-cycle path
-        if (cfg_.mz_zero_copy & 1) { L->pool.zero_copy_ = true; }
-        if (cfg_.mz_zero_copy & 2) {
-            L->pool.v_.host_path_len = L->pool.h_path_len_.p;
-            L->pool.v_.host_path_action = L->pool.h_path_action_.p;
-        }
-        const size_t GA = size_t(L->n) * A_, feat = size_t(L->n) * L->net->featSize(), Gn = L->n;
-#define WALLOC(b, n) \
-    if (!(b).alloc(n)) { setError("worker: allocation failed (%s)", #b); return MZ_ERR_DEVICE; }
-        WALLOC(L->h_feat, feat); WALLOC(L->d_feat, feat); WALLOC(L->h_out, 2 * GA + 2 * Gn); WALLOC(L->d_out, 2 * GA + 2 * Gn);
-        L->h_policy = {L->h_out.p, GA}; L->h_logit = {L->h_out.p + GA, GA}; L->h_value = {L->h_out.p + 2 * GA, Gn}; L->h_reward = {L->h_out.p + 2 * GA + Gn, Gn};
-        L->d_policy = {L->d_out.p, GA}; L->d_logit = {L->d_out.p + GA, GA}; L->d_value = {L->d_out.p + 2 * GA, Gn}; L->d_reward = {L->d_out.p + 2 * GA + Gn, Gn};
-        MZ_HIP(hipMemset(L->d_out.p, 0, L->d_out.n * sizeof(float)));
-        if (desc.type >= 1) {
-            // hidden-state slab: one slot per expanded node; with Gumbel rounds on muzero_atari a second bank for the rounds' second expected leaves
-            slab_slots_ = (n_ + 1) * ((desc.type == 2 && cfg_.actor_use_gumbel && cfg_.mz_sim_rounds && cfg_.mz_sim_round_alt) ? 2 : 1);
-            WALLOC(L->d_hidden, Gn * slab_slots_ * L->net->hiddenSize());
-            WALLOC(L->d_src_idx, Gn); WALLOC(L->d_dst_idx, Gn); WALLOC(L->d_action_ids, Gn);
-        }
-#undef WALLOC
-        lanes_.push_back(std::move(L));
-    }
+    // the first lane's network: the plan asks it which kernels the shape has (at its precision: hasSimKernelWide depends on it)
+    int rc = addLane(shared, weights, count);
+    if (rc) { return rc; }
     // the pool spins: never more spinners than CPUs the container may use, minus one for the HIP runtime's helper threads
     threads_ = std::make_unique<ThreadPool>(hostThreads(), cfg_.mz_cpu_base);
     const size_t GA = size_t(G_) * A_;
@@ -427,125 +374,186 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     noise_mask_.assign(G_, 1);
     held_.assign(G_, Held());
     noise_policy_.resize(GA); noise_logit_.resize(GA); noise_noise_.resize(GA);
-    int rcc = createActors();
-    if (rcc) { return rcc; }
+    if ((rc = createActors())) { return rc; }
+    plan_ = resolvePlan(std::max(1, cfg_.mz_pipeline_lanes));
+    while (int(lanes_.size()) < plan_.lanes) { if ((rc = addLane(shared, weights, count))) { return rc; } }
+    mz_search_cfg sc{};
+    sc.num_simulation = n_;
+    sc.puct_base = cfg_.actor_mcts_puct_base;
+    sc.puct_init = cfg_.actor_mcts_puct_init;
+    sc.reward_discount = cfg_.actor_mcts_reward_discount;
+    sc.value_rescale = cfg_.actor_mcts_value_rescale;
+    sc.flipping_player = flipping_player_;
+    sc.atari_init_q = cfg_.atari_init_q;
+    for (int l = 0; l < plan_.lanes; ++l) { if ((rc = allocLane(l, sc))) { return rc; } }
+    if (plan_.dev_gumbel) { // the constants of gumbel_zero.cpp:101,110 in the host's double arithmetic
+        const int m = cfg_.actor_gumbel_sample_size;
+        gum_.sample_size = m;
+        gum_.sigma_visit_c = cfg_.actor_gumbel_sigma_visit_c;
+        gum_.sigma_scale_c = cfg_.actor_gumbel_sigma_scale_c;
+        gum_.budget0 = static_cast<int>(std::max(1.0, std::floor(n_ / (std::log2(m) * m))));
+        gum_.num_simulation = n_;
+        gum_.log2_m = std::log2(m);
+    }
+    rounds_ = plan_.rounds;
+    return resetAllSearches();
+}
+
+// Every execution choice of the worker, from the configuration, the descriptor, the game, the first lane's network (which kernels its shape has), the pool's
+// size and whether the network is shared.  Pure — nothing is allocated — so the automatic lane count can resolve the plan for one lane and then for two.
+Worker::Plan Worker::resolvePlan(int lanes) const
+{
+    Plan p;
+    const GameEnv& e = *games_[0].env;
+    const Net& net = *lanes_[0]->net;
+    p.lanes = (G_ < 2 * lanes || shared_net_) ? 1 : lanes; // a shared network has one stream: one lane
+    p.lane_size = (G_ + p.lanes - 1) / p.lanes;
+    p.sim_mode.cluster = cfg_.mz_sim_cluster && p.lanes == 1; // two lanes = two concurrent cooperative launches: not with clusters that wait for each other
     // AlphaZero board games: every plane is 0 / 1, so leaves reach the network bit-packed whatever kernels serve its shape — the fused towers stage the bits
     // themselves, the run-time-shaped per-layer kernels behind every other shape get them unpacked first (Net::runTrunk).  (Until round 6 this was tied to
-    // hasFusedTower(), which also kept the device rules — resident_ below — away from every shape on conv3x3_band: a host hop per lock-step cycle.)
-    feat_bits_ = (desc.type == 0);
-    raw_bytes_ = (desc.type == 2 && cfg_.mz_raw_observations) ? games_[0].env->rawFeatureBytes() : 0;
-    if (raw_bytes_ > 0) {
-        for (auto& L : lanes_) {
-            if (!L->h_raw.alloc(size_t(L->n) * raw_bytes_) || !L->d_raw.alloc(size_t(L->n) * raw_bytes_)) { setError("worker: allocation failed (raw observations)"); return MZ_ERR_DEVICE; }
-            const int fb = games_[0].env->rawFrameBytes(), mb = raw_bytes_ - 8 * fb;
-            if (fb > 0 && mb > 0 && mb <= 64 &&
-                (!L->h_new.alloc(size_t(L->n) * fb) || !L->d_new.alloc(size_t(L->n) * fb) || !L->h_meta.alloc(size_t(L->n) * mb) || !L->d_meta.alloc(size_t(L->n) * mb) ||
-                 !L->d_raw2.alloc(size_t(L->n) * raw_bytes_))) {
-                setError("worker: allocation failed (raw observations)"); return MZ_ERR_DEVICE;
+    // hasFusedTower(), which also kept the device rules — resident below — away from every shape on conv3x3_band: a host hop per lock-step cycle.)
+    p.feat_bits = desc_.type == 0;
+    p.raw_bytes = (desc_.type == 2 && cfg_.mz_raw_observations) ? e.rawFeatureBytes() : 0;
+    const bool gumbel_fits = !cfg_.actor_use_gumbel || (cfg_.actor_gumbel_sample_size >= 2 && cfg_.actor_gumbel_sample_size <= kGumbelMaxSample);
+    p.resident = cfg_.mz_device_env && desc_.type == 0 && e.hasDeviceTwin() && p.lane_size <= kRotPackGames;
+    p.sim_mz = cfg_.mz_sim_kernel && (desc_.type == 1 || desc_.type == 2) && net.hasSimKernelMz(n_) && gumbel_fits;
+    p.sim_kernel = p.sim_mz || (p.resident && cfg_.mz_sim_kernel && net.hasSimKernel(e.boardSize(), e.deviceKind(), n_) && gumbel_fits);
+    p.sim_root_host = p.sim_mz && desc_.type == 2;
+    p.dev_gumbel = p.sim_kernel && cfg_.actor_use_gumbel;
+    p.defer_info = p.sim_kernel && !cfg_.mz_manual_step;
+    // hidden-state slab: one slot per expanded node; with Gumbel rounds on muzero_atari a second bank for the rounds' second expected leaves
+    if (desc_.type >= 1) { p.slab_slots = (n_ + 1) * ((desc_.type == 2 && cfg_.actor_use_gumbel && cfg_.mz_sim_rounds && cfg_.mz_sim_round_alt) ? 2 : 1); }
+    if (p.sim_mz && p.dev_gumbel && (desc_.type == 2 || (desc_.type == 1 && cfg_.mz_sim_rounds_board && net.hasPreBoard())) && cfg_.mz_sim_rounds && cfg_.mz_sim_split) {
+        // The visiting order of a Gumbel root is a function of the visit COUNTS alone (ref gumbel_zero.cpp:74-119: fewest visits first, halving when every
+        // candidate has reached the budget): with m sampled children the simulations of a move fall into rounds in which every remaining candidate is visited
+        // once — m, m/2, ... — e.g. n = 50, m = 16: 16, 8, 4, 4, 4, 2 x 7.  The rounds of >= kMinRound simulations are evaluated ahead (sim.hip
+        // sim_pre_kernel_mz); a root with fewer than m children follows another schedule: its entries simply do not match and its simulations evaluate their
+        // own leaves.
+        const int kMinRound = std::max(1, cfg_.mz_sim_round_min);
+        const int n = n_, m = cfg_.actor_gumbel_sample_size;
+        if (m >= 2 && m <= kGumbelMaxSample && A_ >= m) {
+            std::vector<int> cnt(m, 0);
+            int ncand = m, sample = m;
+            int budget = static_cast<int>(std::max(1.0, std::floor(n / (std::log2(m) * m))));
+            int s = 1;
+            while (s <= n) {
+                if (s > 1) { // the step before simulation s (gumbel_zero.cpp:104-118)
+                    bool all = true;
+                    for (int i = 0; i < ncand; ++i) { if (cnt[i] < budget) { all = false; break; } }
+                    if (all) {
+                        const int next_budget = static_cast<int>(std::floor(n / (std::log2(m) * sample / 2)));
+                        if (next_budget > 0 && sample > 2) {
+                            sample /= 2;
+                            if (ncand > sample) { ncand = sample; } // (which ones survive does not matter here: their counts are equal)
+                            budget = cnt[0] + next_budget;
+                        }
+                    }
+                }
+                // a round: every candidate with the minimum count once
+                int mn = cnt[0];
+                for (int i = 1; i < ncand; ++i) { mn = std::min(mn, cnt[i]); }
+                int R = 0;
+                for (int i = 0; i < ncand; ++i) { if (cnt[i] == mn) { ++cnt[i]; ++R; } }
+                R = std::min(R, n - s + 1);
+                if (R >= kMinRound) { p.rounds.push_back({s, R}); p.rounds.back().alt = 2 * G_ * R <= net.cuCount(); } // (the second leaves from the first move on where they fit: adaptRounds takes them away where they are not used)
+                s += R;
             }
         }
+        int covered = 0;
+        for (const Round& rd : p.rounds) { covered += rd.R; }
+        p.sim_mode.rounds = !p.rounds.empty();
+        p.sim_mode.alt_base = (!p.rounds.empty() && p.slab_slots == 2 * (n_ + 1)) ? n_ + 1 : 0;
+        // every simulation of a move has its leaf evaluated ahead: what is left for the simulation kernel is the tree work of one wave per game, which one
+        // workgroup per game does with less overhead than a cluster of four (no command / result exchange, no cooperative launch): 616 -> 656 k leaf-evals/s
+        if (covered == n_) { p.sim_mode.cluster = false; }
     }
-    use_signal_ = cfg_.mz_signal_wait;
-    resident_ = cfg_.mz_device_env && desc.type == 0 && feat_bits_ && games_[0].env->hasDeviceTwin() && lane_size_ <= kRotPackGames;
-    if (resident_) {
+    if (const char* md = getenv("MZ_SIM_SPLIT_MIN_DRAWS")) { p.split_min_draws = atol(md); }
+    // mz_pipeline_lanes = 0 (automatic): a pool that plays in the lock-step mode with the device rules — a shape without a simulation-kernel instance — and whose
+    // cycle is dominated by long convolution kernels runs faster as TWO lanes on two streams: one lane's single-wave tree kernels (select, leaf, candidates, expand:
+    // ~0.3 ms per cycle with 255 CUs idle) run under the other lane's convolutions.  Measured (profiles/r06_lockstep_lanes.json): 19x19 6b x 128, 256 games, 331 GFLOP
+    // per cycle: 64.1 -> 67.1 k leaf-evals/s; 13x13 6b x 96, 73 GFLOP per cycle: 182 -> 167 k (its convolutions at 128 samples no longer fill the chip) — hence the bound.
+    if (cfg_.mz_pipeline_lanes == 0 && p.lanes == 1 && !shared_net_ && p.resident && !p.sim_kernel && G_ >= 64) {
+        const double P = double(desc_.hidden_channel_height) * desc_.hidden_channel_width, C = desc_.num_hidden_channels;
+        const double conv_flops = 2.0 * 9.0 * P * (double(desc_.num_input_channels) * C + 2.0 * desc_.num_blocks * C * C);
+        if (double(G_) * conv_flops >= 2.0e11) { return resolvePlan(2); }
+    }
+    return p;
+}
+
+// A lane's network: the caller's (then the only lane; it keeps the precision its owner chose with mz_net_set_precision) or an instance of its own
+int Worker::addLane(Net* shared, const float* weights, size_t count)
+{
+    auto L = std::make_unique<Lane>();
+    if (shared) {
+        L->net = shared;
+    } else {
+        L->own_net = std::make_unique<Net>();
+        L->net = L->own_net.get();
+        int rc = L->net->init(device_, desc_, weights, count);
+        if (!rc) { rc = L->net->setPrecision(cfg_.mz_nn_precision == "bf16x3" ? 1 : 0); }
+        if (rc) { return rc; }
+    }
+    L->stream = L->net->stream_;
+    lanes_.push_back(std::move(L));
+    return MZ_OK;
+}
+
+// Lane l's slice of the games, device pool and staging, as the plan asks for them
+int Worker::allocLane(int l, const mz_search_cfg& sc)
+{
+    Lane& L = *lanes_[l];
+    L.g0 = l * plan_.lane_size;
+    L.n = std::min(plan_.lane_size, G_ - L.g0);
+    // ref actor_group.cpp:183: tree_node_size = (n + 1) * action_size; tree.h:66: 1 + tree_node_size nodes
+    int rc = L.pool.init(device_, L.n, 1 + (n_ + 1) * A_, A_, sc, L.stream);
+    if (rc) { return rc; }
+    // kernels talk to the pinned staging directly: no memcpy operations on the per-cycle path (the device rules: nobody on the host reads the paths)
+    if (cfg_.mz_zero_copy & 1) { L.pool.zero_copy_ = true; }
+    if ((cfg_.mz_zero_copy & 2) && !plan_.resident) {
+        L.pool.v_.host_path_len = L.pool.h_path_len_.p;
+        L.pool.v_.host_path_action = L.pool.h_path_action_.p;
+    }
+    const size_t n = L.n, GA = n * A_, feat = n * L.net->featSize(), rb = plan_.raw_bytes, sims = n_ + 1;
+#define WALLOC(b, k) \
+    if (!(b).alloc(k)) { setError("worker: allocation failed (%s)", #b); return MZ_ERR_DEVICE; }
+    WALLOC(L.h_feat, feat); WALLOC(L.d_feat, feat); WALLOC(L.h_out, 2 * GA + 2 * n); WALLOC(L.d_out, 2 * GA + 2 * n);
+    L.h_policy = {L.h_out.p, GA}; L.h_logit = {L.h_out.p + GA, GA}; L.h_value = {L.h_out.p + 2 * GA, n}; L.h_reward = {L.h_out.p + 2 * GA + n, n};
+    L.d_policy = {L.d_out.p, GA}; L.d_logit = {L.d_out.p + GA, GA}; L.d_value = {L.d_out.p + 2 * GA, n}; L.d_reward = {L.d_out.p + 2 * GA + n, n};
+    MZ_HIP(hipMemset(L.d_out.p, 0, L.d_out.n * sizeof(float)));
+    if (desc_.type >= 1) { WALLOC(L.d_hidden, n * plan_.slab_slots * L.net->hiddenSize()); WALLOC(L.d_src_idx, n); WALLOC(L.d_dst_idx, n); WALLOC(L.d_action_ids, n); }
+    if (rb > 0) {
+        WALLOC(L.h_raw, n * rb); WALLOC(L.d_raw, n * rb);
+        const int fb = games_[0].env->rawFrameBytes(), mb = plan_.raw_bytes - 8 * fb;
+        if (fb > 0 && mb > 0 && mb <= 64) { WALLOC(L.h_new, n * fb); WALLOC(L.d_new, n * fb); WALLOC(L.h_meta, n * mb); WALLOC(L.d_meta, n * mb); WALLOC(L.d_raw2, n * rb); }
+    }
+    if (plan_.resident) {
         const GameEnv& e = *games_[0].env;
         const int* inv[8];
         const int* fwd[8];
         for (int r = 0; r < 8; ++r) { inv[r] = e.rot()->inv[r].data(); fwd[r] = e.rot()->fwd[r].data(); }
-        for (auto& L : lanes_) {
-            int rc = L->godev.init(device, L->n, e.boardSize(), cfg_.env_go_komi, A_, n_ + 1, L->pool.v_.max_depth, L->stream, inv, fwd, e.zobristKeys(),
-                                   e.deviceKind(), e.turnKey());
-            if (rc) { return rc; }
-            L->pool.v_.host_path_len = nullptr; // nobody on the host reads the paths any more
-            L->pool.v_.host_path_action = nullptr;
-            if ((rc = uploadRoots(*L))) { return rc; }
-        }
-        sim_kernel_ = cfg_.mz_sim_kernel && net0().hasSimKernel(e.boardSize(), e.deviceKind(), cfg_.actor_num_simulation) &&
-                      (!cfg_.actor_use_gumbel || (cfg_.actor_gumbel_sample_size >= 2 && cfg_.actor_gumbel_sample_size <= kGumbelMaxSample));
-        { int rcg = setupDeviceGumbel(); if (rcg) { return rcg; } }
-        defer_info_ = sim_kernel_ && !cfg_.mz_manual_step;
-        if (sim_kernel_) {
-            for (auto& L : lanes_) {
-                if (!L->h_rot.alloc(size_t(n_ + 1) * L->n) || !L->d_rot.alloc(size_t(n_ + 1) * L->n)) { setError("worker: allocation failed (rot table)"); return MZ_ERR_DEVICE; }
-                if (!L->h_noise.alloc(size_t(L->n) * A_) || !L->d_noise.alloc(size_t(L->n) * A_)) { setError("worker: allocation failed (noise)"); return MZ_ERR_DEVICE; }
-                { int rce = L->makeSimEvents(); if (rce) { return rce; } }
-            }
-        }
+        rc = L.godev.init(device_, L.n, e.boardSize(), cfg_.env_go_komi, A_, n_ + 1, L.pool.v_.max_depth, L.stream, inv, fwd, e.zobristKeys(), e.deviceKind(), e.turnKey());
+        if (rc) { return rc; }
     }
-    sim_mz_ = !resident_ && cfg_.mz_sim_kernel && (desc.type == 1 || desc.type == 2) && net0().hasSimKernelMz(cfg_.actor_num_simulation) &&
-              (!cfg_.actor_use_gumbel || (cfg_.actor_gumbel_sample_size >= 2 && cfg_.actor_gumbel_sample_size <= kGumbelMaxSample));
-    if (sim_mz_) {
-        sim_kernel_ = true;
-        defer_info_ = !cfg_.mz_manual_step;
-        sim_root_host_ = desc.type == 2;
-        { int rcg = setupDeviceGumbel(); if (rcg) { return rcg; } }
-        if (dev_gumbel_ && (desc.type == 2 || (desc.type == 1 && cfg_.mz_sim_rounds_board && net0().hasPreBoard())) && cfg_.mz_sim_rounds && cfg_.mz_sim_split) {
-            planRounds();
-            for (auto& L : lanes_) {
-                if (!L->h_prestat.alloc(512)) { setError("worker: allocation failed (round counters)"); return MZ_ERR_DEVICE; }
-                memset(L->h_prestat.p, 0, 512 * sizeof(unsigned));
-            }
-            int covered = 0;
-            for (const Round& rd : rounds_) { covered += rd.R; }
-            sim_mode_.rounds = !rounds_.empty();
-            sim_mode_.alt_base = (!rounds_.empty() && slab_slots_ == 2 * (n_ + 1)) ? n_ + 1 : 0;
-            // every simulation of a move has its leaf evaluated ahead: what is left for the simulation kernel is the tree work of one wave per game, which one
-            // workgroup per game does with less overhead than a cluster of four (no command / result exchange, no cooperative launch): 616 -> 656 k leaf-evals/s
-            if (covered == n_ && !getenv("MZ_ROUNDS_CLUSTER")) { sim_mode_.cluster = false; }
-        }
-        const int fw = sim_root_host_ ? 1 : games_[0].env->featureWords(), LW = (A_ + 63) / 64;
-        for (auto& L : lanes_) {
-            if (!L->h_rootfeat.alloc(size_t(L->n) * fw) || !L->d_rootfeat.alloc(size_t(L->n) * fw) || !L->h_rootlegal.alloc(size_t(L->n) * LW) ||
-                !L->d_rootlegal.alloc(size_t(L->n) * LW) || !L->h_rootturn.alloc(L->n) || !L->d_rootturn.alloc(L->n) ||
-                !L->h_noise.alloc(size_t(L->n) * A_) || !L->d_noise.alloc(size_t(L->n) * A_) || !L->h_rot.alloc(size_t(n_ + 1) * L->n) ||
-                !L->d_rot.alloc(size_t(n_ + 1) * L->n)) {
-                setError("worker: allocation failed (MuZero root staging)");
-                return MZ_ERR_DEVICE;
-            }
-            { int rce = L->makeSimEvents(); if (rce) { return rce; } }
-            int rc = uploadRoots(*L);
-            if (rc) { return rc; }
-        }
+    if (plan_.sim_kernel) {
+        WALLOC(L.h_rot, sims * n); WALLOC(L.d_rot, sims * n); WALLOC(L.h_noise, GA); WALLOC(L.d_noise, GA);
+        if ((rc = L.makeSimEvents())) { return rc; }
     }
+    if (plan_.dev_gumbel) { // the Gumbel state of every game (gumbel.h)
+        const size_t k = n * (3 + kGumbelMaxSample);
+        WALLOC(L.h_gum, k); WALLOC(L.d_gum, k);
+        memset(L.h_gum.p, 0, k * sizeof(int));
+        MZ_HIP(hipMemset(L.d_gum.p, 0, k * sizeof(int)));
+    }
+    if (plan_.sim_mz) { // root planes (bit-packed), legal mask and player of every game
+        const size_t fw = plan_.sim_root_host ? 1 : games_[0].env->featureWords(), LW = (A_ + 63) / 64;
+        WALLOC(L.h_rootfeat, n * fw); WALLOC(L.d_rootfeat, n * fw); WALLOC(L.h_rootlegal, n * LW); WALLOC(L.d_rootlegal, n * LW); WALLOC(L.h_rootturn, n); WALLOC(L.d_rootturn, n);
+    }
+    if (plan_.sim_mode.rounds) { // the network's counters of leaves evaluated ahead (adaptRounds)
+        WALLOC(L.h_prestat, 512);
+        memset(L.h_prestat.p, 0, 512 * sizeof(unsigned));
+    }
+#undef WALLOC
     return MZ_OK;
-}
-
-// The visiting order of a Gumbel root is a function of the visit COUNTS alone (ref gumbel_zero.cpp:74-119: fewest visits first, halving when every candidate has
-// reached the budget): with m sampled children the simulations of a move fall into rounds in which every remaining candidate is visited once — m, m/2, ... —
-// e.g. n = 50, m = 16: 16, 8, 4, 4, 4, 2 x 7.  The rounds of >= kMinRound simulations are evaluated ahead (sim.hip sim_pre_kernel_mz); a root with fewer than m
-// children follows another schedule: its entries simply do not match and its simulations evaluate their own leaves.
-void Worker::planRounds()
-{
-    rounds_.clear();
-    const int kMinRound = std::max(1, cfg_.mz_sim_round_min);
-    const int n = cfg_.actor_num_simulation, m = cfg_.actor_gumbel_sample_size;
-    if (m < 2 || m > kGumbelMaxSample || A_ < m) { return; }
-    std::vector<int> cnt(m, 0);
-    int ncand = m, sample = m;
-    int budget = static_cast<int>(std::max(1.0, std::floor(n / (std::log2(m) * m))));
-    int s = 1;
-    while (s <= n) {
-        if (s > 1) { // the step before simulation s (gumbel_zero.cpp:104-118)
-            bool all = true;
-            for (int i = 0; i < ncand; ++i) { if (cnt[i] < budget) { all = false; break; } }
-            if (all) {
-                const int next_budget = static_cast<int>(std::floor(n / (std::log2(m) * sample / 2)));
-                if (next_budget > 0 && sample > 2) {
-                    sample /= 2;
-                    if (ncand > sample) { ncand = sample; } // (which ones survive does not matter here: their counts are equal)
-                    budget = cnt[0] + next_budget;
-                }
-            }
-        }
-        // a round: every candidate with the minimum count once
-        int mn = cnt[0];
-        for (int i = 1; i < ncand; ++i) { mn = std::min(mn, cnt[i]); }
-        int R = 0;
-        for (int i = 0; i < ncand; ++i) { if (cnt[i] == mn) { ++cnt[i]; ++R; } }
-        R = std::min(R, n - s + 1);
-        if (R >= kMinRound) { rounds_.push_back({s, R}); rounds_.back().alt = !lanes_.empty() && 2 * G_ * R <= net0().cuCount(); } // (the second leaves from the first move on where they fit: adaptRounds takes them away where they are not used)
-        s += R;
-    }
 }
 
 // A simulation that does not find its leaf evaluated ahead evaluates it itself, on ONE CU, while the round's launch — every other game of the pool — waits: one
@@ -564,7 +572,7 @@ void Worker::adaptRounds()
     // (sim_pre_pair_kernel_mz: a partner workgroup stayed out — the GPU is shared.  Looked at whatever the second-leaf settings are: with mz_sim_round_alt=false every
     // small round goes to the pairs, and a shared GPU would pay the partner's bounded wait in every round of every move)
     if (now[129] != 0) { for (auto& L : lanes_) { L->net->pairTrouble(); } }
-    if (!cfg_.mz_sim_round_alt || sim_mode_.alt_base == 0) { return; }
+    if (!cfg_.mz_sim_round_alt || plan_.sim_mode.alt_base == 0) { return; }
     if (prestat_prev_.size() == 512) {
         const int cus = net0().cuCount();
         for (Round& rd : rounds_) {
@@ -582,35 +590,14 @@ void Worker::adaptRounds()
     prestat_prev_.assign(now, now + 512);
 }
 
-int Worker::setupDeviceGumbel() // the constants of the device-side Gumbel step + its per-lane state buffers
-{
-    dev_gumbel_ = sim_kernel_ && cfg_.actor_use_gumbel;
-    if (dev_gumbel_) { // the constants of gumbel_zero.cpp:101,110 in the host's double arithmetic
-        const int m = cfg_.actor_gumbel_sample_size;
-        gum_.sample_size = m;
-        gum_.sigma_visit_c = cfg_.actor_gumbel_sigma_visit_c;
-        gum_.sigma_scale_c = cfg_.actor_gumbel_sigma_scale_c;
-        gum_.budget0 = static_cast<int>(std::max(1.0, std::floor(cfg_.actor_num_simulation / (std::log2(m) * m))));
-        gum_.num_simulation = cfg_.actor_num_simulation;
-        gum_.log2_m = std::log2(m);
-        for (auto& L : lanes_) {
-            const size_t n = size_t(L->n) * (3 + kGumbelMaxSample);
-            if (!L->h_gum.alloc(n) || !L->d_gum.alloc(n)) { setError("worker: allocation failed (gumbel state)"); return MZ_ERR_DEVICE; }
-            memset(L->h_gum.p, 0, n * sizeof(int));
-            MZ_HIP(hipMemset(L->d_gum.p, 0, n * sizeof(int)));
-        }
-    }
-    return MZ_OK;
-}
-
 int Worker::uploadRoots(Lane& L)
 {
     const int g0 = L.g0;
-    if (sim_mz_) { // MuZero: what the initial inference and the root expansion need from the host engine
-        const int fw = sim_root_host_ ? 1 : games_[0].env->featureWords(), LW = (A_ + 63) / 64;
+    if (plan_.sim_mz) { // MuZero: what the initial inference and the root expansion need from the host engine
+        const int fw = plan_.sim_root_host ? 1 : games_[0].env->featureWords(), LW = (A_ + 63) / 64;
         threads_->parallelFor(L.n, [this, &L, g0, fw, LW](int j) {
             Game& gm = games_[g0 + j];
-            if (!sim_root_host_) { gm.env->featureBits(0, L.h_rootfeat.p + size_t(j) * fw); }
+            if (!plan_.sim_root_host) { gm.env->featureBits(0, L.h_rootfeat.p + size_t(j) * fw); }
             gm.env->legalMask(gm.legal.data());
             for (int w = 0; w < LW; ++w) { L.h_rootlegal.p[size_t(j) * LW + w] = 0; }
             for (int a = 0; a < A_; ++a) { if (gm.legal[a]) { L.h_rootlegal.p[size_t(j) * LW + (a >> 6)] |= 1ull << (a & 63); } }
@@ -631,7 +618,6 @@ int Worker::createActors()
     // from the MAIN thread's generator) + actor_group.cpp:66-70 (slave thread 0 seeds its own generator: seed + 0)
     const int seed = cfg_.program_auto_seed ? static_cast<int>(std::random_device()()) : cfg_.program_seed;
     main_rng_.seed(seed);
-    games_.clear();
     games_.resize(G_);
     for (auto& g : games_) {
         // ref atari.cpp:87: observations kept for the OBS tag of the next record
@@ -661,9 +647,7 @@ int Worker::createActors()
     rngs_.assign(streams_, Rng());
     for (int t = 0; t < streams_; ++t) { rngs_[t].seed(cfg_.program_auto_seed ? static_cast<int>(std::random_device()()) : cfg_.program_seed + t); }
     stream_noise_.assign(streams_, {});
-    sims_done_ = 0;
-    pending_ = false;
-    return resetAllSearches();
+    return MZ_OK;
 }
 
 int Worker::resetAllSearches()
@@ -673,7 +657,7 @@ int Worker::resetAllSearches()
         for (int j = 0; j < L->n; ++j) { rp[j] = rootPlayerFor(games_[L->g0 + j]); }
         int rc = L->pool.resetSearch(nullptr, rp.data());
         if (rc) { return rc; }
-        if ((resident_ || sim_mz_) && (rc = uploadRoots(*L))) { return rc; }
+        if ((plan_.resident || plan_.sim_mz) && (rc = uploadRoots(*L))) { return rc; }
     }
     return MZ_OK;
 }
@@ -760,15 +744,15 @@ void Worker::buildLeaf(int gi)
         g.leaf_reward = g.leaf->reward();
         if (g.leaf_terminal) { g.leaf_eval = g.leaf->evalScore(false); }
         else { g.leaf->legalMask(g.legal.data()); }
-        if (feat_bits_) { g.leaf->featureBits(g.rot, reinterpret_cast<uint32_t*>(L.h_feat.p) + size_t(j) * g.env->featureWords()); }
+        if (plan_.feat_bits) { g.leaf->featureBits(g.rot, reinterpret_cast<uint32_t*>(L.h_feat.p) + size_t(j) * g.env->featureWords()); }
         else { g.leaf->features(g.rot, feat); }
     } else if (sims_done_ == 0) {
-        if (raw_bytes_ > 0 && L.raw_incremental) {
-            const int fb = g.env->rawFrameBytes(), mb = raw_bytes_ - 8 * fb;
+        if (plan_.raw_bytes > 0 && L.raw_incremental) {
+            const int fb = g.env->rawFrameBytes(), mb = plan_.raw_bytes - 8 * fb;
             g.env->rawNewest(L.h_new.p + size_t(j) * fb, L.h_meta.p + size_t(j) * mb);
             g.raw_seen = g.env->rawSerial();
-        } else if (raw_bytes_ > 0) {
-            g.env->rawFeatures(L.h_raw.p + size_t(j) * raw_bytes_);
+        } else if (plan_.raw_bytes > 0) {
+            g.env->rawFeatures(L.h_raw.p + size_t(j) * plan_.raw_bytes);
             g.raw_seen = g.env->rawSerial();
         } else { g.env->features(0, feat); }
         g.env->legalMask(g.legal.data());
@@ -1099,7 +1083,7 @@ void Worker::handleSearchDone(int g) // ref actor_group.cpp:116-134 + base_actor
     if (acted) {
         // the P/V/R strings of this move (no RNG involved) are only needed when the game is printed: for every other game they are
         // built after the next launch has been queued, off the critical path (the root statistics stay valid until the next root read)
-        if (defer_info_ && !is_endgame && !intermediate) { (tl_sink_ ? tl_sink_->deferred : deferred_).push_back({g, mover, gm.action_info_history.size() - 1}); }
+        if (plan_.defer_info && !is_endgame && !intermediate) { (tl_sink_ ? tl_sink_->deferred : deferred_).push_back({g, mover, gm.action_info_history.size() - 1}); }
         else { gm.action_info_history.back() = actionInfo(g, mover); }
     }
     if (is_endgame) {
@@ -1196,9 +1180,9 @@ int Worker::phase1(Lane& L, bool root_expansion, bool done, bool launch_select)
     if (pending_) {
         double t1 = t0, te = t0;
         int rc = MZ_OK;
-        if (!resident_ && (!sim_mz_ || root_host_pending_)) { // resident / simulation kernel: candidates + expand + backup already ran on the device
+        if (!plan_.resident && (!plan_.sim_mz || root_host_pending_)) { // resident / simulation kernel: candidates + expand + backup already ran on the device
             // (root_host_pending_ is cleared by the caller when EVERY lane has had its turn: cleared here, the lanes behind the first kept unexpanded roots)
-            if (use_signal_) { int rcw = L.pool.waitSignal(L.signal_seq); if (rcw) { return rcw; } }
+            if (cfg_.mz_signal_wait) { int rcw = L.pool.waitSignal(L.signal_seq); if (rcw) { return rcw; } }
             else { MZ_HIP(hipStreamSynchronize(L.stream)); } // network outputs of this lane
             t1 = nowMs();
             stats_.ms_forward += t1 - t0;
@@ -1241,7 +1225,7 @@ int Worker::phase1(Lane& L, bool root_expansion, bool done, bool launch_select)
             if ((rc = L.pool.resetSearch(nullptr, rp.data()))) { return rc; }
             const double tr1 = nowMs();
             trace_.add(12, tr1 - tr0);
-            if ((resident_ || sim_mz_) && (rc = uploadRoots(L))) { return rc; }
+            if ((plan_.resident || plan_.sim_mz) && (rc = uploadRoots(L))) { return rc; }
             trace_.add(13, nowMs() - tr1);
         }
         if (done && cfg_.mz_manual_step) { return MZ_OK; } // no next selection: the caller acts and resets the search first
@@ -1269,10 +1253,10 @@ int Worker::phase1(Lane& L, bool root_expansion, bool done, bool launch_select)
         d_start = L.pool.d_start_.p;
     }
     if (!launch_select) { return MZ_OK; } // per-game simulation kernel: selection is part of the launch (runCyclesSim)
-    if (resident_) { for (int g = g0; g < g1; ++g) { rotPackSet(L.rot, g - g0, games_[g].rot); } }
+    if (plan_.resident) { for (int g = g0; g < g1; ++g) { rotPackSet(L.rot, g - g0, games_[g].rot); } }
     int rc = L.pool.selectAsync(d_start);
     if (rc) { return rc; }
-    if (resident_) {
+    if (plan_.resident) {
         const double tz = nowMs();
         stats_.ms_select += tz - t0;
         return MZ_OK;
@@ -1282,7 +1266,7 @@ int Worker::phase1(Lane& L, bool root_expansion, bool done, bool launch_select)
         MZ_HIP(hipMemcpyAsync(L.pool.h_path_arena_.p, L.pool.d_path_arena_.p,
                               (size_t(L.n) + (az ? size_t(L.n) * L.pool.v_.max_depth : 0)) * sizeof(uint32_t), hipMemcpyDeviceToHost, L.stream));
     } // else: select_kernel already wrote path_len / path_action into the pinned mirrors
-    if (use_signal_) { int rcs = L.pool.signalAsync(++L.signal_seq); if (rcs) { return rcs; } }
+    if (cfg_.mz_signal_wait) { int rcs = L.pool.signalAsync(++L.signal_seq); if (rcs) { return rcs; } }
     const double tz = nowMs();
     stats_.ms_select += tz - t0;
     trace_.add(6, tz - t0);
@@ -1312,16 +1296,16 @@ int Worker::phase2Resident(Lane& L)
 
 int Worker::phase2(Lane& L)
 {
-    if (resident_) { return phase2Resident(L); }
+    if (plan_.resident) { return phase2Resident(L); }
     const bool az = desc_.type == 0;
     const int g0 = L.g0;
     const double t0 = nowMs();
-    if (use_signal_) { int rcw = L.pool.waitSignal(L.signal_seq); if (rcw) { return rcw; } }
+    if (cfg_.mz_signal_wait) { int rcw = L.pool.waitSignal(L.signal_seq); if (rcw) { return rcw; } }
     else { MZ_HIP(hipStreamSynchronize(L.stream)); } // paths of this lane
     const double t1 = nowMs();
     stats_.ms_select += t1 - t0;
     trace_.add(7, t1 - t0);
-    if (raw_bytes_ > 0 && sims_done_ == 0) { // root observations: newest screen only when every game's previous block is on the device
+    if (plan_.raw_bytes > 0 && sims_done_ == 0) { // root observations: newest screen only when every game's previous block is on the device
         bool inc = L.raw_have && L.d_raw2.p != nullptr;
         for (int j = 0; inc && j < L.n; ++j) {
             const Game& gm = games_[g0 + j];
@@ -1335,51 +1319,51 @@ int Worker::phase2(Lane& L)
     trace_.add(8, t2 - t1);
     int rc;
     if (az) {
-        const size_t fbytes = feat_bits_ ? size_t(L.n) * games_[0].env->featureWords() * sizeof(uint32_t) : size_t(L.n) * L.net->featSize() * sizeof(float);
+        const size_t fbytes = plan_.feat_bits ? size_t(L.n) * games_[0].env->featureWords() * sizeof(uint32_t) : size_t(L.n) * L.net->featSize() * sizeof(float);
         // zero-copy: the tower kernel stages its LDS tile straight from pinned host memory / the heads kernel writes the outputs there
         const bool zin = cfg_.mz_zero_copy & 1, zout = cfg_.mz_zero_copy & 2;
         if (!zin) { MZ_HIP(hipMemcpyAsync(L.d_feat.p, L.h_feat.p, fbytes, hipMemcpyHostToDevice, L.stream)); }
         if ((rc = L.net->forwardAZ(zin ? L.h_feat.p : L.d_feat.p, L.n, zout ? L.h_policy.p : L.d_policy.p, zout ? L.h_logit.p : L.d_logit.p,
-                                  zout ? L.h_value.p : L.d_value.p, feat_bits_))) {
+                                  zout ? L.h_value.p : L.d_value.p, plan_.feat_bits))) {
             return rc;
         }
         if (zout) {
-            if (use_signal_) { if ((rc = L.pool.signalAsync(++L.signal_seq))) { return rc; } }
+            if (cfg_.mz_signal_wait) { if ((rc = L.pool.signalAsync(++L.signal_seq))) { return rc; } }
             const double t3z = nowMs();
             stats_.ms_forward += t3z - t2;
             trace_.add(9, t3z - t2);
             return MZ_OK;
         }
     } else if (sims_done_ == 0) {
-        if (raw_bytes_ > 0 && L.raw_incremental) {
-            const int fb = games_[g0].env->rawFrameBytes(), mb = raw_bytes_ - 8 * fb;
+        if (plan_.raw_bytes > 0 && L.raw_incremental) {
+            const int fb = games_[g0].env->rawFrameBytes(), mb = plan_.raw_bytes - 8 * fb;
             uint8_t* prev = L.raw_cur == 0 ? L.d_raw.p : L.d_raw2.p;
             uint8_t* cur = L.raw_cur == 0 ? L.d_raw2.p : L.d_raw.p;
             MZ_HIP(hipMemcpyAsync(L.d_new.p, L.h_new.p, size_t(L.n) * fb, hipMemcpyHostToDevice, L.stream));
             MZ_HIP(hipMemcpyAsync(L.d_meta.p, L.h_meta.p, size_t(L.n) * mb, hipMemcpyHostToDevice, L.stream));
-            if ((rc = L.net->shiftExpandAtariFeatures(prev, L.d_new.p, L.d_meta.p, cur, raw_bytes_, L.n, L.d_feat.p))) { return rc; }
+            if ((rc = L.net->shiftExpandAtariFeatures(prev, L.d_new.p, L.d_meta.p, cur, plan_.raw_bytes, L.n, L.d_feat.p))) { return rc; }
             L.raw_cur ^= 1;
-        } else if (raw_bytes_ > 0) {
+        } else if (plan_.raw_bytes > 0) {
             uint8_t* cur = L.raw_cur == 0 ? L.d_raw.p : L.d_raw2.p;
-            MZ_HIP(hipMemcpyAsync(cur, L.h_raw.p, size_t(L.n) * raw_bytes_, hipMemcpyHostToDevice, L.stream));
-            if ((rc = L.net->expandAtariFeatures(cur, raw_bytes_, L.n, L.d_feat.p))) { return rc; }
+            MZ_HIP(hipMemcpyAsync(cur, L.h_raw.p, size_t(L.n) * plan_.raw_bytes, hipMemcpyHostToDevice, L.stream));
+            if ((rc = L.net->expandAtariFeatures(cur, plan_.raw_bytes, L.n, L.d_feat.p))) { return rc; }
             L.raw_have = true;
         } else {
             MZ_HIP(hipMemcpyAsync(L.d_feat.p, L.h_feat.p, size_t(L.n) * L.net->featSize() * sizeof(float), hipMemcpyHostToDevice, L.stream));
         }
-        if ((rc = L.pool.hiddenIndexAsync(slab_slots_, 0, L.d_src_idx.p, L.d_dst_idx.p, L.d_action_ids.p))) { return rc; }
+        if ((rc = L.pool.hiddenIndexAsync(plan_.slab_slots, 0, L.d_src_idx.p, L.d_dst_idx.p, L.d_action_ids.p))) { return rc; }
         if ((rc = L.net->initial(L.d_feat.p, L.n, L.d_policy.p, L.d_logit.p, L.d_value.p, L.d_hidden.p, L.d_dst_idx.p))) { return rc; }
         MZ_HIP(hipMemsetAsync(L.d_reward.p, 0, L.n * sizeof(float), L.stream));
     } else {
         // device-resident MuZero step: parent hidden state gathered from the slab, action plane synthesised on device
-        if ((rc = L.pool.hiddenIndexAsync(slab_slots_, sims_done_, L.d_src_idx.p, L.d_dst_idx.p, L.d_action_ids.p))) { return rc; }
+        if ((rc = L.pool.hiddenIndexAsync(plan_.slab_slots, sims_done_, L.d_src_idx.p, L.d_dst_idx.p, L.d_action_ids.p))) { return rc; }
         if ((rc = L.net->recurrent(L.d_hidden.p, L.d_src_idx.p, nullptr, L.d_action_ids.p, L.n, L.d_policy.p, L.d_logit.p, L.d_value.p, L.d_reward.p,
                                   L.d_hidden.p, L.d_dst_idx.p))) {
             return rc;
         }
     }
     MZ_HIP(hipMemcpyAsync(L.h_out.p, L.d_out.p, L.h_out.n * sizeof(float), hipMemcpyDeviceToHost, L.stream));
-    if (use_signal_) { if ((rc = L.pool.signalAsync(++L.signal_seq))) { return rc; } }
+    if (cfg_.mz_signal_wait) { if ((rc = L.pool.signalAsync(++L.signal_seq))) { return rc; } }
     const double t3 = nowMs();
     stats_.ms_forward += t3 - t2;
     trace_.add(9, t3 - t2);
@@ -1505,11 +1489,11 @@ int Worker::runCyclesSim(int n)
         sim_pre_ = sims_done_;
         sim_post_ = sims_done_ + 1;
         const bool root_expansion = pending_ && (sim_post_ == 1), done = pending_ && (sim_post_ == n_ + 1);
-        const bool host_gumbel = dev_gumbel_ && pending_; // the host runs this cycle's Gumbel step itself: state down, step, state up
+        const bool host_gumbel = plan_.dev_gumbel && pending_; // the host runs this cycle's Gumbel step itself: state down, step, state up
         // muzero_atari: the root's 96x96 representation is not part of the kernel; simulation 0 of a move runs as one lock-step cycle
         // (select, host planes, stand-alone kernels); its outputs are expanded on the device when simulations follow in this call (below), otherwise by
         // the next phase1 on the host; the other n simulations are one launch
-        const bool root_cycle = sim_root_host_ && (!pending_ || done);
+        const bool root_cycle = plan_.sim_root_host && (!pending_ || done);
         for (auto& L : lanes_) {
             int rc = MZ_OK;
             if (host_gumbel && (rc = syncGumbel(*L, false))) { return rc; }
@@ -1546,10 +1530,10 @@ int Worker::runCyclesSim(int n)
                 GumbelView gv = gum_;
                 gv.state = L->d_gum.p;
                 bool launched = false;
-                int rc = L->net->simLaunchMz(L->pool, L->d_hidden.p, slab_slots_, L->d_rootfeat.p, L->d_rootlegal.p, L->d_rootturn.p, games_[0].env->numPlayers(), L->d_policy.p,
+                int rc = L->net->simLaunchMz(L->pool, L->d_hidden.p, plan_.slab_slots, L->d_rootfeat.p, L->d_rootlegal.p, L->d_rootturn.p, games_[0].env->numPlayers(), L->d_policy.p,
                                             L->d_logit.p, L->d_value.p, L->d_reward.p, 0, 1, &launched, noise_cfg ? L->d_noise.p : nullptr,
-                                            cfg_.actor_dirichlet_noise_epsilon, cfg_.actor_use_dirichlet_noise ? 1 : 2, dev_gumbel_ ? &gv : nullptr, L->pool.d_start_.p,
-                                            host_gumbel, true, 0, false, sim_mode_);
+                                            cfg_.actor_dirichlet_noise_epsilon, cfg_.actor_use_dirichlet_noise ? 1 : 2, plan_.dev_gumbel ? &gv : nullptr, L->pool.d_start_.p,
+                                            host_gumbel, true, 0, false, plan_.sim_mode);
                 if (rc) { return rc; }
                 if (!launched) { const std::string why = mz_last_error(); setError("worker: the root expansion kernel was not launched (%s)", why.c_str()); return MZ_ERR_STATE; }
             }
@@ -1581,15 +1565,14 @@ int Worker::runCyclesSim(int n)
         if (cfg_.mz_sim_split && sim0 == 0 && batch > 1 && (noise_in_batch || az_draws)) {
             constexpr int kSecond = 16; // simulations of the middle part: 3 ms on BASELINE configs[1], three times what the draws of the rest take on this host
             cuts[parts++] = 1;
-            static const long min_draws = getenv("MZ_SIM_SPLIT_MIN_DRAWS") ? atol(getenv("MZ_SIM_SPLIT_MIN_DRAWS")) : 32768; // (tests: 0 = three parts on small pools too)
-            if (az_draws && batch > 1 + kSecond && long(batch - 1 - kSecond) * G_ >= min_draws) { cuts[parts++] = 1 + kSecond; }
+            if (az_draws && batch > 1 + kSecond && long(batch - 1 - kSecond) * G_ >= plan_.split_min_draws) { cuts[parts++] = 1 + kSecond; }
             cuts[parts] = batch;
         }
         // Gumbel rounds (mz_sim_rounds, muzero_atari): the launch is cut at the rounds whose leaves are evaluated ahead — [evaluation of the round's leaves]
         // [its simulations, which consume them in order] — with the stretches between them as ordinary parts; all queued back to back, no host step between
         // (muzero_atari: the launch starts at simulation 1, behind the device-side root expansion; MuZero board games: at simulation 0, the root's initial inference,
         // which goes out as a part of its own in front of the first round — a call that covers the whole move)
-        const bool use_rounds = !rounds_.empty() && ((root_on_device && sim0 == 1) || (!sim_root_host_ && sim_mz_ && sim0 == 0 && batch == n_ + 1 && cfg_.mz_sim_split));
+        const bool use_rounds = !rounds_.empty() && ((root_on_device && sim0 == 1) || (!plan_.sim_root_host && plan_.sim_mz && sim0 == 0 && batch == n_ + 1 && cfg_.mz_sim_split));
         if (use_rounds) {
             parts = 0;
             int at = 0; // offset inside the batch
@@ -1641,13 +1624,13 @@ int Worker::runCyclesSim(int n)
                         if (pre) { ++stats_.sim_launches; ++stats_.pre_launches; }
                     }
                 }
-                int rc = sim_mz_ ? L->net->simLaunchMz(L->pool, L->d_hidden.p, slab_slots_, L->d_rootfeat.p, L->d_rootlegal.p, L->d_rootturn.p,
+                int rc = plan_.sim_mz ? L->net->simLaunchMz(L->pool, L->d_hidden.p, plan_.slab_slots, L->d_rootfeat.p, L->d_rootlegal.p, L->d_rootturn.p,
                                                       games_[0].env->numPlayers(), L->d_policy.p, L->d_logit.p, L->d_value.p, L->d_reward.p, sim0 + c0, c1 - c0,
                                                       &launched, noise_in_batch ? L->d_noise.p : nullptr, cfg_.actor_dirichlet_noise_epsilon, noise_kind,
-                                                      dev_gumbel_ ? &gv : nullptr, L->pool.d_start_.p, hg, false, use_rounds ? L->pre_epoch : 0, use_rounds && noise_in_batch, sim_mode_)
+                                                      plan_.dev_gumbel ? &gv : nullptr, L->pool.d_start_.p, hg, false, use_rounds ? L->pre_epoch : 0, use_rounds && noise_in_batch, plan_.sim_mode)
                                   : L->net->simLaunch(L->pool, L->godev.v_, L->d_policy.p, L->d_logit.p, L->d_value.p, L->d_rot.p + size_t(c0) * L->n, sim0 + c0, c1 - c0,
                                                      &launched, noise_in_batch ? L->d_noise.p : nullptr, cfg_.actor_dirichlet_noise_epsilon, noise_kind,
-                                                     dev_gumbel_ ? &gv : nullptr, L->pool.d_start_.p, hg);
+                                                     plan_.dev_gumbel ? &gv : nullptr, L->pool.d_start_.p, hg);
                 if (rc) { return rc; }
                 if (!launched) { const std::string why = mz_last_error(); setError("worker: the simulation kernel was not launched (%s)", why.c_str()); return MZ_ERR_STATE; }
                 if (!use_rounds || part == parts - 1) { MZ_HIP(hipEventRecord(L->ev1[use_rounds ? 0 : part], L->stream)); }
@@ -1655,8 +1638,7 @@ int Worker::runCyclesSim(int n)
                 ++stats_.sim_launches;
                 // the launch that completes the move's search: the root statistics the per-move host logic reads next are queued right behind it
                 L->rr_ahead = false;
-                static const bool rr_ahead_on = !getenv("MZ_NO_RR_AHEAD"); // (A/B switch)
-                if (rr_ahead_on && part == parts - 1 && sim0 + batch == n_ + 1 && !cfg_.mz_manual_step && L->pool.stream_ == L->stream) {
+                if (part == parts - 1 && sim0 + batch == n_ + 1 && !cfg_.mz_manual_step && L->pool.stream_ == L->stream) {
                     int rcr = L->pool.rootReadLaunch();
                     if (rcr) { return rcr; }
                     L->rr_ahead = true;
@@ -1699,14 +1681,14 @@ int Worker::runCyclesSim(int n)
 int Worker::runCycles(int n)
 {
     if (!running_ || search_done_) { return 0; }
-    if (sim_kernel_) { return runCyclesSim(n); }
+    if (plan_.sim_kernel) { return runCyclesSim(n); }
     stop_now_ = false;
     for (int i = 0; i < n; ++i) {
         int rc = cycle();
         if (rc) { return rc; }
         if (stop_now_) { n = i; break; }
     }
-    if (resident_) { // the cycles above were only queued: the call returns when they have run
+    if (plan_.resident) { // the cycles above were only queued: the call returns when they have run
         const double t0 = nowMs();
         for (auto& L : lanes_) {
             MZ_HIP(hipStreamSynchronize(L->stream));
@@ -1795,7 +1777,7 @@ int Worker::finishSearch()
     MZ_HIP(hipSetDevice(device_));
     sim_pre_ = sims_done_;
     sim_post_ = sims_done_ + 1;
-    const bool host_gumbel = dev_gumbel_;
+    const bool host_gumbel = plan_.dev_gumbel;
     for (auto& L : lanes_) {
         int rc = MZ_OK;
         MZ_HIP(hipStreamSynchronize(L->stream));
@@ -2038,11 +2020,6 @@ mz_worker* mz_worker_create(int device, const char* conf, const mz_net_desc* des
         count = file_weights.size();
     }
     if (w->w.init(device, conf, *desc, weights, count) != MZ_OK) { return nullptr; }
-    if (w->w.wantsTwoLanes()) { // (decided after the first initialisation, which is what knows the kernels the shape gets; records do not depend on the lane count)
-        const std::string conf2 = std::string(conf) + ":mz_pipeline_lanes=2";
-        w.reset(new mz_worker());
-        if (w->w.init(device, conf2.c_str(), *desc, weights, count) != MZ_OK) { return nullptr; }
-    }
     return w.release();
 }
 mz_worker* mz_worker_create_shared(int device, const char* conf, mz_net* net)

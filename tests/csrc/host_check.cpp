@@ -83,8 +83,8 @@ static int workerMain(int argc, char** argv)
         if (mz_worker_peek_record(wk, i, buf.data(), static_cast<int>(buf.size())) < 0) { fprintf(stderr, "peek_record: %s\n", mz_last_error()); return 1; }
         printf("R %s\n", buf.data());
     }
-    printf("S cycles=%llu leaf_evals=%llu games=%llu sim_launches=%llu\n", (unsigned long long)st.cycles, (unsigned long long)st.leaf_evals, (unsigned long long)st.games,
-           (unsigned long long)st.sim_launches);
+    printf("S cycles=%llu leaf_evals=%llu games=%llu sim_launches=%llu lanes=%d\n", (unsigned long long)st.cycles, (unsigned long long)st.leaf_evals, (unsigned long long)st.games,
+           (unsigned long long)st.sim_launches, mz_worker_lanes(wk));
     mz_worker_destroy(wk);
     return 0;
 }

@@ -173,6 +173,10 @@ def test_heavy_lock_step_pool_runs_as_two_lanes(mz, oracle):
     conf = "env_game=go:env_board_size=19:actor_num_simulation=2:zero_num_parallel_games=160:program_seed=5:nn_file_name=x.pt"
     wk = mz.Worker(conf + ":zero_num_threads=4", d, w)
     assert wk.lanes() == 2
+    # the lane count is resolved by the worker, not written into its configuration: the user's own value still passes update_config, another is refused
+    assert wk.command("update_config mz_pipeline_lanes=0") == 0
+    with pytest.raises(mz.MzError, match="mz_pipeline_lanes is fixed"):
+        wk.command("update_config mz_pipeline_lanes=2")
     light = mz.Worker(conf.replace("zero_num_parallel_games=160", "zero_num_parallel_games=64") + ":zero_num_threads=4", d, w)
     assert light.lanes() == 1
     light.close()

@@ -69,6 +69,7 @@ def worker_vs_oracle(oracle, binary, conf, args, T, steps, seed=3, wseed=0):
     assert lines == og.lines(), (len(lines), len(og.lines()))
     assert recs == og.peek_records(games)
     assert int(stats["leaf_evals"]) == og.leaf_evals() and int(stats["sim_launches"]) == 0
+    assert int(stats["lanes"]) == (2 if "mz_pipeline_lanes=2" in conf else 1)
     return lines
 
 
@@ -77,6 +78,9 @@ WORKER_CASES = {
     "tictactoe": (TTT, "env_game=tictactoe:actor_num_simulation=16:zero_num_parallel_games=32", [17 * 6 + 5, 17 * 14 - 5], 40),
     "go_noise_resign": (GO7_AZ, "env_game=go:env_board_size=7:actor_num_simulation=6:zero_num_parallel_games=19:actor_resign_threshold=0.6:zero_disable_resign_ratio=0.5",
                         [7 * 40 + 3, 7 * 60 - 3], 10),
+    # the same pool cut into two lanes of 10 and 9 games (own pool, network instance and stream each), the plan resolved before either is allocated
+    "go_noise_resign_two_lanes": (GO7_AZ, "env_game=go:env_board_size=7:actor_num_simulation=6:zero_num_parallel_games=19:actor_resign_threshold=0.6:zero_disable_resign_ratio=0.5:"
+                                  "mz_pipeline_lanes=2", [7 * 40 + 3, 7 * 60 - 3], 10),
     "othello_gumbel": (OTH_AZ, f"env_game=othello:env_board_size=8:actor_num_simulation=12:{GUMBEL}:zero_num_parallel_games=17", [13 * 64], 10),
     "go_muzero": (GO_MZ, "env_game=go:env_board_size=7:nn_type_name=muzero:actor_num_simulation=6:zero_num_parallel_games=16", [7 * 30], 0),
     "tictactoe_muzero_gumbel": (TTT_MZ, f"env_game=tictactoe:nn_type_name=muzero:actor_num_simulation=8:{GUMBEL.replace('sample_size=8', 'sample_size=4')}:zero_num_parallel_games=24",
@@ -99,8 +103,8 @@ WORKER_CASES = {
 def test_worker_host_half_under_tsan(oracle, binaries, name, T):
     """clean under ThreadSanitizer at T in {2, 8, 16} RNG streams / host threads, records equal to the oracle's"""
     args, conf, steps, min_lines = WORKER_CASES[name]
-    if T == 16 and name not in ("tictactoe", "go_noise_resign", "tictactoe_iteration"):
-        pytest.skip("16 streams: three cases are enough for the CPU suite's time budget")
+    if T == 16 and name not in ("tictactoe", "go_noise_resign", "go_noise_resign_two_lanes", "tictactoe_iteration"):
+        pytest.skip("16 streams: four cases are enough for the CPU suite's time budget")
     lines = worker_vs_oracle(oracle, binaries["tsan"], conf, args, T, steps)
     assert len(lines) >= min_lines
 
