@@ -69,6 +69,9 @@ inline std::string mzgpuCollectConfiguration()
     o << "env_game=go";
 #elif defined(OTHELLO) && OTHELLO
     o << "env_game=othello";
+#elif defined(GOMOKU) && GOMOKU
+    // the two keys the reference registers for this game only (configuration.cpp:179-181)
+    o << "env_gomoku_rule=" << env_gomoku_rule << ":env_gomoku_exactly_five_stones=" << env_gomoku_exactly_five_stones << ":env_game=gomoku";
 #elif defined(ATARI) && ATARI
     o << "env_game=atari:atari_init_q=true"; // the #if ATARI init-Q rule of mcts.cpp:211-216
 #else

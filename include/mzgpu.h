@@ -321,6 +321,8 @@ int mz_env_features(const mz_env* e, int rotation, float* out);
 int mz_env_action_from_string(const mz_env* e, const char* action_string);
 /* the same planes bit-packed (the device format): channel c = ceil(P/32) words, bit p%32 of word p/32 */
 int mz_env_feature_bits(const mz_env* e, int rotation, uint32_t* out);
+/* the environment's name (the GM tag of its records, e.g. "gomoku_oo_15x15") into out[cap] (NUL-terminated, truncated); returns its full length */
+int mz_env_name(const mz_env* e, char* out, int cap);
 
 /* ------------------------------------------------------------------------------------------
  * Device-resident leaf environment (AlphaZero Go): test access.  The worker uses it when
@@ -341,6 +343,9 @@ int mz_godev_playout(int device, int board_size, float komi, const int* actions,
 /* the same for any game with a device engine ("go", "othello", "tictactoe"): feat_out [steps][channels*ceil(P/32)], legal_out [steps][actions] */
 int mz_envdev_playout(int device, const char* game, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots,
                       uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
+/* ... with the game and its rules from a configuration string as mz_env_create takes it (env_game=gomoku:env_gomoku_rule=outer_open:...) */
+int mz_envdev_playout_conf(int device, const char* conf, const int* actions, int count, int root_prefix, const int* rots,
+                           uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
 int mz_sort_candidates(int device, const float* policy, int n, int* order_out);
 int mz_invert_values_device(int device, const float* values, int n, float* out);
 

@@ -52,6 +52,8 @@ struct WorkerConfig {
     int env_board_size = 0;
     float env_go_komi = 7.5;
     std::string env_go_ko_rule = "positional";
+    std::string env_gomoku_rule = "standard"; // env_game=gomoku only: "outer_open" restricts the first move, any other value is the standard rule
+    bool env_gomoku_exactly_five_stones = true;
     // run-time replacements of the reference's compile-time switches (-D<GAME>, #if ATARI in mcts.cpp:211)
     std::string env_game = "tictactoe";
     bool atari_init_q = false;

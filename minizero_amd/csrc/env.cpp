@@ -5,6 +5,7 @@
 //             8-deep ring of stone bitboards for the history planes.
 //   Othello : two 64-bit bitboards, shift-and-mask move generation (8x8 and smaller).
 //   TicTacToe: two 9-bit masks.
+//   Gomoku  : two bitboards of up to 6 words, the winner from the four lines through the last stone.
 // All feature planes are written straight into caller memory (the worker's pinned staging buffer).
 #include "env.h"
 #include "go_dev.h"
@@ -298,6 +299,137 @@ public:
 private:
     int n_;
     uint64_t full_, not_left_, not_right_, s_[2];
+};
+
+// ---------------------------------------------------------------------------------------------
+// Gomoku, board <= 19x19 (ref gomoku.cpp:14-185): two bitboards of up to 6 words.  The winner is decided by the move just played alone,
+// along each of the four lines through its stone (gomoku.cpp:140-162); a win on the move that fills the board is a win.  Outer-open
+// restricts the game's first move (no move played yet) to the outer two rings.  No pass action: policySize() == P.
+// ---------------------------------------------------------------------------------------------
+class Gomoku final : public GameEnv {
+    static constexpr int kW = (19 * 19 + 63) / 64;
+public:
+    Gomoku(int n, bool outer_open, bool exactly_five) : n_(n), P_(n * n), outer_open_(outer_open), exactly_five_(exactly_five)
+    {
+        rot_ = rotationTables(n, n * n);
+        reset();
+    }
+    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<Gomoku>(*this); }
+    void copyFrom(const GameEnv& o) override { *this = static_cast<const Gomoku&>(o); }
+    void reset() override
+    {
+        turn_ = 1;
+        action_ids_.clear();
+        action_players_.clear();
+        memset(s_, 0, sizeof(s_));
+        winner_ = 0;
+    }
+    bool stone(int c, int p) const { return (s_[c][p >> 6] >> (p & 63)) & 1; }
+    bool isLegal(int a, int) const override // ref gomoku.cpp:48-58: the first move under outer-open is any point of the outer two rings
+    {
+        if (a < 0 || a >= P_) { return false; }
+        if (outer_open_ && action_ids_.empty()) {
+            const int i = a / n_, j = a % n_;
+            return i < 2 || i >= n_ - 2 || j < 2 || j >= n_ - 2;
+        }
+        return !stone(0, a) && !stone(1, a);
+    }
+    bool act(int a, int player) override
+    {
+        if (!isLegal(a, player)) { return false; }
+        actUnchecked(a, player);
+        return true;
+    }
+    void actUnchecked(int a, int player) override
+    {
+        s_[player - 1][a >> 6] |= 1ull << (a & 63);
+        action_ids_.push_back(static_cast<int16_t>(a));
+        action_players_.push_back(static_cast<uint8_t>(player));
+        turn_ = 3 - player;
+        winner_ = wins(a, player - 1) ? player : 0; // ref gomoku.cpp:29: replaced on every move
+    }
+    // the stones of colour c on the line through p in direction (dx, dy), p included (ref gomoku.cpp:140-162)
+    int lineLength(int p, int c, int dx, int dy) const
+    {
+        int len = 1;
+        for (int sgn = -1; sgn <= 1; sgn += 2) {
+            int x = p % n_ + sgn * dx, y = p / n_ + sgn * dy;
+            while (x >= 0 && x < n_ && y >= 0 && y < n_ && stone(c, y * n_ + x)) { ++len; x += sgn * dx; y += sgn * dy; }
+        }
+        return len;
+    }
+    bool wins(int p, int c) const
+    {
+        static const int dirs[4][2] = {{1, 0}, {0, 1}, {1, 1}, {1, -1}};
+        for (const auto& d : dirs) {
+            const int len = lineLength(p, c, d[0], d[1]);
+            if (exactly_five_ ? len == 5 : len >= 5) { return true; }
+        }
+        return false;
+    }
+    int stonesPlayed() const
+    {
+        int k = 0;
+        for (int w = 0; w < kW; ++w) { k += __builtin_popcountll(s_[0][w] | s_[1][w]); }
+        return k;
+    }
+    void legalMask(uint8_t* out) const override { for (int a = 0; a < P_; ++a) { out[a] = isLegal(a, turn_); } }
+    bool isTerminal() const override { return winner_ != 0 || stonesPlayed() == P_; }
+    float evalScore(bool is_resign) const override { return scoreOf(is_resign ? 3 - turn_ : winner_); } // ref gomoku.cpp:65-73
+    void features(int r, float* out) const override // ref gomoku.cpp:75-98: own, opponent, black to move, white to move
+    {
+        const int* map = rot_->inv[r].data();
+        for (int p = 0; p < P_; ++p) {
+            out[p] = stone(turn_ - 1, map[p]) ? 1.0f : 0.0f;
+            out[P_ + p] = stone(2 - turn_, map[p]) ? 1.0f : 0.0f;
+            out[2 * P_ + p] = turn_ == 1 ? 1.0f : 0.0f;
+            out[3 * P_ + p] = turn_ == 2 ? 1.0f : 0.0f;
+        }
+    }
+    void featureBits(int r, uint32_t* out) const override
+    {
+        const int W32 = (P_ + 31) / 32;
+        const int* map = rot_->inv[r].data();
+        for (int i = 0; i < 4 * W32; ++i) { out[i] = 0; }
+        for (int p = 0; p < P_; ++p) {
+            const uint32_t b = 1u << (p & 31);
+            if (stone(turn_ - 1, map[p])) { out[p >> 5] |= b; }
+            if (stone(2 - turn_, map[p])) { out[W32 + (p >> 5)] |= b; }
+            out[(turn_ == 1 ? 2 : 3) * W32 + (p >> 5)] |= b;
+        }
+    }
+    int actionFromString(const std::string& str) const override
+    {
+        std::string up = str;
+        for (char& c : up) { c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
+        return up == "PASS" ? -1 : GameEnv::actionFromString(str); // no pass action
+    }
+    bool hasDeviceTwin() const override { return n_ >= 2; }
+    int deviceKind() const override { return 3; }
+    void exportDeviceRoot(void* dst) const override // the fields of GoRootSnapshot the Gomoku device engine reads (go_body.h gmkLeafBody)
+    {
+        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
+        for (int w = 0; w < kGoMaxW; ++w) {
+            s.stones[0][w] = w < kW ? s_[0][w] : 0;
+            s.stones[1][w] = w < kW ? s_[1][w] : 0;
+        }
+        s.hash = 0;
+        s.hist_len = (outer_open_ ? kGmkOuterOpen : 0) | (exactly_five_ ? kGmkExactlyFive : 0);
+        s.turn = turn_;
+        s.nmoves = static_cast<int32_t>(action_ids_.size());
+        s.passes = winner_;
+    }
+    int numInputChannels() const override { return 4; }
+    int boardSize() const override { return n_; }
+    int policySize() const override { return P_; }
+    std::string name() const override { return "gomoku" + std::string(outer_open_ ? "_oo_" : "_") + std::to_string(n_) + "x" + std::to_string(n_); }
+    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", std::to_string(n_)}}; }
+
+private:
+    int n_, P_;
+    bool outer_open_, exactly_five_;
+    int winner_;
+    uint64_t s_[2][kW];
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -861,7 +993,7 @@ private:
 };
 
 std::unique_ptr<GameEnv> createGameEnv(const std::string& game, int board_size, float go_komi, const std::string& atari_name, int atari_episode_length,
-                                       const std::string& go_ko_rule, size_t atari_recent_observations)
+                                       const std::string& go_ko_rule, size_t atari_recent_observations, const std::string& gomoku_rule, bool gomoku_exactly_five)
 {
     if (game == "atari") { return std::make_unique<AtariSynth>(atari_name, atari_episode_length, std::max<size_t>(1, atari_recent_observations)); }
     if (game == "tictactoe") { return std::make_unique<TicTacToe>(); }
@@ -876,7 +1008,12 @@ std::unique_ptr<GameEnv> createGameEnv(const std::string& game, int board_size, 
         if (go_ko_rule != "positional" && go_ko_rule != "situational") { setError("env_go_ko_rule '%s' not supported (positional | situational, ref go.cpp:47)", go_ko_rule.c_str()); return nullptr; }
         return std::make_unique<Go>(n, go_komi, go_ko_rule == "situational");
     }
-    setError("unknown env_game '%s' (tictactoe | go | othello | atari)", game.c_str());
+    if (game == "gomoku") { // ref gomoku.h:13,21,44
+        const int n = board_size > 0 ? board_size : 15;
+        if (n > kMaxN) { setError("gomoku board size %d not supported (up to 19)", n); return nullptr; }
+        return std::make_unique<Gomoku>(n, gomoku_rule == "outer_open", gomoku_exactly_five);
+    }
+    setError("unknown env_game '%s' (tictactoe | go | othello | gomoku | atari)", game.c_str());
     return nullptr;
 }
 

@@ -679,6 +679,113 @@ __device__ __forceinline__ void tttLeafBody(const GoDevView& v, const PoolView& 
     }
 }
 
+// ---- Gomoku (ref environment/gomoku/gomoku.cpp:23-105,140-162): two bitboards of up to kGoMaxW words per slot, `meta` (moves played, the winner).  The
+// position is wave-uniform (every lane carries the words; a lane picks the word of its own point with selects, never a dynamic register index).  The
+// winner is decided by the move just played alone: lanes 0 .. 3 walk the four lines through its stone.  No pass: the legal mask is the empty points or,
+// for the game's first move under outer-open, the outer two rings (gomoku.cpp:48-58) — like the host's, also at a terminal leaf.
+__device__ __forceinline__ unsigned long long gmkWord(const unsigned long long (&b)[kGoMaxW], int w)
+{
+    unsigned long long x = b[0];
+#pragma unroll
+    for (int i = 1; i < kGoMaxW; ++i) { x = w == i ? b[i] : x; }
+    return x;
+}
+__device__ __forceinline__ bool gmkStone(const unsigned long long (&b)[kGoMaxW], int p) { return (gmkWord(b, p >> 6) >> (p & 63)) & 1; }
+
+__device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane)
+{
+    const int P = v.P, n = v.n, W = v.W, MD = pv.max_depth;
+    const int len = pv.path_len[g];
+    const int* path = pv.path + size_t(g) * MD;
+    const int* pact = pv.path_action + size_t(g) * MD;
+    const int depth = len - 1;
+    const GoRootSnapshot& S = v.snap[g];
+    const int root_turn = S.turn, rule = S.hist_len;
+    const size_t sb = size_t(g) * v.slots;
+    const int* hs = pv.hslot + size_t(g) * pv.cap;
+    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    unsigned long long blk[kGoMaxW], wht[kGoMaxW];
+#pragma unroll
+    for (int i = 0; i < kGoMaxW; ++i) {
+        blk[i] = i < W ? v.stones[((sb + src) * 2 + 0) * W + i] : 0ull;
+        wht[i] = i < W ? v.stones[((sb + src) * 2 + 1) * W + i] : 0ull;
+    }
+    int nmoves = v.meta[(sb + src) * 2], winner = v.meta[(sb + src) * 2 + 1];
+    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
+    if (depth >= 1) {
+        const int a = pact[len - 1], m = 3 - t; // moved by the other player
+        ++nmoves;
+        unsigned long long mine[kGoMaxW];
+#pragma unroll
+        for (int i = 0; i < kGoMaxW; ++i) {
+            const unsigned long long bit = i == (a >> 6) ? 1ull << (a & 63) : 0ull;
+            if (m == 1) { blk[i] |= bit; } else { wht[i] |= bit; }
+            mine[i] = m == 1 ? blk[i] : wht[i];
+        }
+        // line d of lanes 0 .. 3: (1, 0) row, (0, 1) column, (1, 1) and (1, -1) the diagonals; its length through `a` (a included)
+        const int d = lane & 3, dx = d == 1 ? 0 : 1, dy = d == 0 ? 0 : (d == 3 ? -1 : 1);
+        int run = 1;
+        for (int sgn = -1; sgn <= 1; sgn += 2) {
+            int x = a % n + sgn * dx, y = a / n + sgn * dy;
+            while (x >= 0 && x < n && y >= 0 && y < n && gmkStone(mine, y * n + x)) { ++run; x += sgn * dx; y += sgn * dy; }
+        }
+        const bool five = (rule & kGmkExactlyFive) ? run == 5 : run >= 5;
+        winner = __ballot(lane < 4 && five) != 0 ? m : 0; // ref gomoku.cpp:29: the winner is replaced on every move
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < kGoMaxW; ++i) {
+                if (i < W) {
+                    v.stones[((sb + slot) * 2 + 0) * W + i] = blk[i];
+                    v.stones[((sb + slot) * 2 + 1) * W + i] = wht[i];
+                }
+            }
+            v.meta[(sb + slot) * 2] = nmoves;
+            v.meta[(sb + slot) * 2 + 1] = winner;
+        }
+    }
+    int stones = 0;
+#pragma unroll
+    for (int i = 0; i < kGoMaxW; ++i) { stones += __popcll(blk[i] | wht[i]); }
+    const bool terminal = winner != 0 || stones == P; // ref gomoku.cpp:60-63
+    const bool first_oo = (rule & kGmkOuterOpen) && nmoves == 0;
+    const uint16_t* map = v.inv + size_t(rot) * P;
+    uint32_t* out = v.feat + size_t(g) * 4 * v.W32;
+#pragma unroll
+    for (int i = 0; i < kGoMaxW; ++i) {
+        if (i >= W) { continue; }
+        const int p = 64 * i + lane;
+        bool leg = false;
+        if (p < P) {
+            if (first_oo) {
+                const int r = p / n, c = p % n;
+                leg = r < 2 || r >= n - 2 || c < 2 || c >= n - 2;
+            } else {
+                leg = !(((blk[i] | wht[i]) >> lane) & 1);
+            }
+        }
+        const unsigned long long lw = __ballot(leg);
+        if (lane == 0) { v.legal[size_t(g) * v.LW + i] = lw; }
+        // planes (ref gomoku.cpp:75-98): own, opponent, black to move, white to move — under the cycle's rotation
+        const int q = p < P ? map[p] : 0;
+        const bool b = gmkStone(blk, q), w = gmkStone(wht, q);
+        const unsigned long long own = __ballot(p < P && (t == 1 ? b : w)), opp = __ballot(p < P && (t == 1 ? w : b)), ones = __ballot(p < P);
+        unsigned long long word = 0;
+        if (lane == 0) { word = own; }
+        if (lane == 1) { word = opp; }
+        if (lane == 2) { word = t == 1 ? ones : 0; }
+        if (lane == 3) { word = t == 2 ? ones : 0; }
+        if (lane < 4) {
+            if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(word); }
+            if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(word >> 32); }
+        }
+    }
+    if (lane == 0) {
+        v.leaf_player[g] = t;
+        v.terminal[g] = terminal ? 1 : 0;
+        v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); // ref gomoku.cpp:65-73
+    }
+}
+
 // order `k` candidates in cs[] like the reference's std::sort(policy descending): result in out[]
 __device__ void orderCandidates(Cand* cs, Cand* out, int* stack, int k, int lane, int* err)
 {

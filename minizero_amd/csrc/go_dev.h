@@ -28,6 +28,10 @@ struct GoRootSnapshot {
     uint16_t lab[kGoMaxP + 3];      // group id per point (valid where a stone is): any point of the group
 };
 
+// Gomoku (kind 3) in a GoRootSnapshot: stones = the two bitboards, nmoves, turn; passes = the winner (0 none); hist_len = the rule bits:
+// env_gomoku_rule=outer_open, env_gomoku_exactly_five_stones
+constexpr int kGmkOuterOpen = 1, kGmkExactlyFive = 2;
+
 struct RotPack { uint32_t w[kRotPackGames / 10]; }; // per-game feature rotation of one cycle, passed as a kernel argument
 inline void rotPackSet(RotPack& r, int g, int rot) { r.w[g / 10] = (r.w[g / 10] & ~(7u << (3 * (g % 10)))) | (uint32_t(rot) << (3 * (g % 10))); }
 
@@ -54,7 +58,8 @@ struct GoDevView {
 
 class GoDevice {
 public:
-    // kind 0: Go (keys = Zobrist table [2][P]); kind 1: Othello (board_n <= 8, keys unused); kind 2: TicTacToe (3x3, 9 actions)
+    // kind 0: Go (keys = Zobrist table [2][P]); kind 1: Othello (board_n <= 8, keys unused); kind 2: TicTacToe (3x3, 9 actions);
+    // kind 3: Gomoku (board_n <= 19, P actions, keys unused)
     int init(int device, int games, int board_n, float komi, int action_size, int slots, int max_depth, hipStream_t stream, const int* const inv[8],
              const int* const fwd[8], const uint64_t* keys, int kind = 0, uint64_t turn_key = 0);
     GoRootSnapshot* hostSnap(int g) { return h_snap_.p + g; }

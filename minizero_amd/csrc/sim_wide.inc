@@ -151,6 +151,9 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
 #elif MZ_SIM_WIDE_PART == 3 // Othello (words per plane 0) and TicTacToe (-1: sim_az_body.h simSelectLeaf) at the reference's default width: the same phase functions as sim_kernel's
 #define MZ_SIM_WIDE_PART_CASES(X) X(8, 8, 16, 128, 0) X(8, 8, 16, 256, 0) X(3, 3, 16, 128, -1) X(3, 3, 16, 256, -1)
 #define MZ_SIM_WIDE_PART_FN simWideLaunchPart3
+#elif MZ_SIM_WIDE_PART == 4 // Gomoku (words per plane -2: sim_az_body.h simSelectLeaf) on its default 15x15 board: 64 channels (measured), 32 (tests)
+#define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 16, 64, -2) X(15, 15, 16, 32, -2)
+#define MZ_SIM_WIDE_PART_FN simWideLaunchPart4
 #else // (built with MZ_SPEC_WAYS = 4: the shapes whose tile leaves too little LDS for sixteen remembered paths)
 #define MZ_SIM_WIDE_PART_CASES(X) X(19, 19, 32, 64, 6) X(19, 19, 32, 32, 6) X(13, 13, 32, 128, 3) X(9, 9, 32, 256, 2)
 #define MZ_SIM_WIDE_PART_FN simWideLaunchPart2

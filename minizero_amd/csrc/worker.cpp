@@ -625,7 +625,7 @@ int Worker::createActors()
                                                           ? 108000
                                                           : cfg_.zero_actor_intermediate_sequence_length + 8 + cfg_.learner_n_step_return + cfg_.learner_muzero_unrolling_step) + 1;
         g.env = createGameEnv(cfg_.env_game, cfg_.env_board_size, cfg_.env_go_komi, cfg_.env_atari_name, cfg_.env_atari_episode_length, cfg_.env_go_ko_rule,
-                              recent_obs);
+                              recent_obs, cfg_.env_gomoku_rule, cfg_.env_gomoku_exactly_five_stones);
         if (!g.env) { return MZ_ERR_ARG; }
         if (g.env->policySize() != A_ || g.env->featureSize() != net0().featSize()) {
             setError("network (A=%d, features=%d) does not fit env %s (A=%d, features=%d)", A_, net0().featSize(), g.env->name().c_str(),
@@ -1983,6 +1983,8 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         // the Atari-shaped environments keep a window of screens sized from these three at creation (ref atari.cpp:87); records of a larger window
         // would miss frames, so they are fixed where observations are kept (board games: free to change, like the reference)
         if (games_[0].env->hasObservations()) { MZ_FIXED(zero_actor_intermediate_sequence_length) MZ_FIXED(learner_n_step_return) MZ_FIXED(learner_muzero_unrolling_step) }
+        // Gomoku's rules live in its engines (host and device) from creation; for every other game the two keys are inert
+        if (games_[0].env->deviceKind() == 3) { MZ_FIXED(env_gomoku_rule) MZ_FIXED(env_gomoku_exactly_five_stones) }
 #undef MZ_FIXED
         if (fixed) { setError("update_config: %s is fixed when the worker is created (restart the worker to change it)", fixed); return MZ_ERR_ARG; }
         cfg_ = nc;
@@ -1999,6 +2001,9 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
 struct mz_worker { mz::Worker w; };
 struct mz_net { mz::Net net; };
 struct mz_env { std::unique_ptr<mz::GameEnv> e; };
+
+static int envdevPlayout(int device, mz::GameEnv* env, float komi, const int* actions, int count, int root_prefix, const int* rots, uint32_t* feat_out,
+                         uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
 
 extern "C" {
 
@@ -2155,7 +2160,8 @@ mz_env* mz_env_create(const char* conf)
     mz::WorkerConfig c;
     if (!conf || !c.loadFromString(conf)) { return nullptr; }
     std::unique_ptr<mz_env> e(new mz_env());
-    e->e = mz::createGameEnv(c.env_game, c.env_board_size, c.env_go_komi, c.env_atari_name, c.env_atari_episode_length, c.env_go_ko_rule);
+    e->e = mz::createGameEnv(c.env_game, c.env_board_size, c.env_go_komi, c.env_atari_name, c.env_atari_episode_length, c.env_go_ko_rule, 108001,
+                             c.env_gomoku_rule, c.env_gomoku_exactly_five_stones);
     if (!e->e) { return nullptr; }
     return e.release();
 }
@@ -2187,6 +2193,14 @@ int mz_env_action_from_string(const mz_env* e, const char* action_string)
     return e->e->actionFromString(action_string);
 }
 
+int mz_env_name(const mz_env* e, char* out, int cap)
+{
+    if (!e) { mz::setError("mz_env_name: NULL environment"); return MZ_ERR_ARG; }
+    const std::string s = e->e->name();
+    if (out && cap > 0) { snprintf(out, size_t(cap), "%s", s.c_str()); }
+    return static_cast<int>(s.size());
+}
+
 int mz_env_feature_bits(const mz_env* e, int rotation, uint32_t* out)
 {
     if (rotation < 0 || rotation > 7) { mz::setError("rotation %d out of range", rotation); return MZ_ERR_ARG; }
@@ -2212,6 +2226,29 @@ int mz_envdev_playout(int device, const char* game, int board_size, float komi, 
     if (!actions || !rots || count < 0 || root_prefix < 0 || root_prefix > count) { setError("mz_envdev_playout: bad arguments"); return MZ_ERR_ARG; }
     const bool situational = std::string(game) == "go_situational"; // test access to env_go_ko_rule=situational
     std::unique_ptr<GameEnv> env = createGameEnv(situational ? "go" : game, board_size, komi, "ms_pacman", 1000, situational ? "situational" : "positional");
+    return envdevPlayout(device, env.get(), komi, actions, count, root_prefix, rots, feat_out, legal_out, terminal_out, eval_out, player_out);
+}
+
+int mz_envdev_playout_conf(int device, const char* conf, const int* actions, int count, int root_prefix, const int* rots, uint32_t* feat_out,
+                           uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out)
+{
+    using namespace mz;
+    WorkerConfig c;
+    if (!conf || !c.loadFromString(conf)) { return MZ_ERR_ARG; }
+    if (mz_device_count() < 1) { setError("mz_envdev_playout_conf: no GPU (libmzgpu has no CPU path)"); return MZ_ERR_DEVICE; }
+    if (!actions || !rots || count < 0 || root_prefix < 0 || root_prefix > count) { setError("mz_envdev_playout_conf: bad arguments"); return MZ_ERR_ARG; }
+    std::unique_ptr<GameEnv> env = createGameEnv(c.env_game, c.env_board_size, c.env_go_komi, c.env_atari_name, c.env_atari_episode_length, c.env_go_ko_rule, 1,
+                                                 c.env_gomoku_rule, c.env_gomoku_exactly_five_stones);
+    return envdevPlayout(device, env.get(), c.env_go_komi, actions, count, root_prefix, rots, feat_out, legal_out, terminal_out, eval_out, player_out);
+}
+
+} // extern "C"
+
+// the body of both playout entries: root = actions[:root_prefix] on the host engine, then one device move per remaining action
+static int envdevPlayout(int device, mz::GameEnv* env, float komi, const int* actions, int count, int root_prefix, const int* rots, uint32_t* feat_out,
+                         uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out)
+{
+    using namespace mz;
     if (!env || !env->hasDeviceTwin()) { setError("mz_envdev_playout: no device twin for this board"); return MZ_ERR_ARG; }
     for (int i = 0; i < root_prefix; ++i) {
         if (!env->act(actions[i], env->turn())) { setError("mz_envdev_playout: illegal root action %d at move %d", actions[i], i); return MZ_ERR_ARG; }
@@ -2248,6 +2285,8 @@ int mz_envdev_playout(int device, const char* game, int board_size, float komi, 
     }
     return MZ_OK;
 }
+
+extern "C" {
 
 int mz_godev_playout(int device, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots, uint32_t* feat_out,
                      uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out)

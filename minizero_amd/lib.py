@@ -158,10 +158,12 @@ def load():
         L.mz_env_features.argtypes = [vp, C.c_int, fp]
         L.mz_env_feature_bits.argtypes = [vp, C.c_int, C.POINTER(C.c_uint32)]
         L.mz_env_action_from_string.argtypes = [vp, C.c_char_p]
+        L.mz_env_name.argtypes = [vp, C.c_char_p, C.c_int]
         L.mz_worker_create_shared.restype = vp
         L.mz_worker_create_shared.argtypes = [C.c_int, C.c_char_p, vp]
         L.mz_godev_playout.argtypes = [C.c_int, C.c_int, C.c_float, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
         L.mz_envdev_playout.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_float, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
+        L.mz_envdev_playout_conf.argtypes = [C.c_int, C.c_char_p, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
         L.mz_sort_candidates.argtypes = [C.c_int, fp, C.c_int, ip]
         L.mz_invert_values_device.argtypes = [C.c_int, fp, C.c_int, fp]
     L.mz_loader_create.restype = vp
@@ -577,6 +579,11 @@ class Env:
     def policy_size(self): return self.L.mz_env_policy_size(self.h)
     def action_from_string(self, s): return self.L.mz_env_action_from_string(self.h, s.encode())
 
+    def name(self):
+        buf = C.create_string_buffer(256)
+        _check(self.L, self.L.mz_env_name(self.h, buf, len(buf)))
+        return buf.value.decode()
+
     def legal_mask(self):
         m = np.zeros(self.policy_size(), np.uint8)
         self.L.mz_env_legal_mask(self.h, m.ctypes.data_as(C.POINTER(C.c_uint8)))
@@ -630,6 +637,25 @@ def envdev_playout(game, board_size, komi, actions, root_prefix, rots, channels,
     pl = np.zeros(steps, np.int32)
     _check(L, L.mz_envdev_playout(device, game.encode(), board_size, komi, _i(acts), len(acts), root_prefix, _i(rots),
                                   feat.ctypes.data_as(C.POINTER(C.c_uint32)), legal.ctypes.data_as(C.POINTER(C.c_uint8)), _i(term), _f(ev), _i(pl)))
+    return feat, legal, term, ev, pl
+
+
+def envdev_playout_conf(conf, board_size, actions, root_prefix, rots, channels, num_actions, device=0):
+    """envdev_playout with the game and its rules from a configuration string, as Env takes it (e.g. "env_game=gomoku:env_gomoku_rule=outer_open")."""
+    L = load()
+    P = board_size * board_size
+    acts = np.ascontiguousarray(actions, np.int32)
+    steps = len(acts) - root_prefix + 1
+    rots = np.ascontiguousarray(rots, np.int32)
+    assert len(rots) >= steps
+    W32 = (P + 31) // 32
+    feat = np.zeros((steps, channels * W32), np.uint32)
+    legal = np.zeros((steps, num_actions), np.uint8)
+    term = np.zeros(steps, np.int32)
+    ev = np.zeros(steps, np.float32)
+    pl = np.zeros(steps, np.int32)
+    _check(L, L.mz_envdev_playout_conf(device, conf.encode(), _i(acts), len(acts), root_prefix, _i(rots), feat.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                       legal.ctypes.data_as(C.POINTER(C.c_uint8)), _i(term), _f(ev), _i(pl)))
     return feat, legal, term, ev, pl
 
 

@@ -56,6 +56,10 @@ EXTRA_CONFIGS = {
     # no simulation-kernel launches to time, the block's roofline.wall_frac is the figure
     "l19x128": ("l19x128", "env_game=go:env_board_size=19:actor_num_simulation=400:zero_num_parallel_games=256"),  # 19x19 Go, 6 blocks x 128 channels (one tile = 237 KB)
     "l13x96": ("l13x96", "env_game=go:env_board_size=13:actor_num_simulation=400:zero_num_parallel_games=256"),    # 13x13 Go, 6 blocks x 96 channels (no 16 * 2^k)
+    # Gomoku on its default 15x15 board, BASELINE configs[1]'s search: 6 blocks x 64 channels on the simulation kernel, the reference's default network
+    # (1 block x 256 channels, whose 15x15 tile does not fit the LDS) on the lock-step cycle with the device rules
+    "g15x64": ("g15x64", "env_game=gomoku:actor_num_simulation=400:zero_num_parallel_games=256"),
+    "g15x256": ("g15x256", "env_game=gomoku:actor_num_simulation=400:zero_num_parallel_games=256"),
 }
 # ... and BASELINE configs[4]'s whole node (512 games) on ONE GPU — NOT the BASELINE shard (64 games per GPU): what the same kernels reach when the pool fills the chip
 EXTRA_CONFIGS["c5x512"] = ("c5", mz.CONFIGS["c5"].replace("zero_num_parallel_games=64", "zero_num_parallel_games=512"))
@@ -69,12 +73,15 @@ EXTRA_DESCS = {
     "w3x256ttt": lambda: mz.make_desc("tictactoe", 4, 3, 3, 256, 3, 3, 1, 1, 9),
     "l19x128": lambda: mz.make_desc("go_19x19", 18, 19, 19, 128, 19, 19, 1, 6, 362),
     "l13x96": lambda: mz.make_desc("go_13x13", 18, 13, 13, 96, 13, 13, 1, 6, 170),
+    "g15x64": lambda: mz.make_desc("gomoku_15x15", 4, 15, 15, 64, 15, 15, 1, 6, 225),
+    "g15x256": lambda: mz.make_desc("gomoku_15x15", 4, 15, 15, 256, 15, 15, 1, 1, 225),
 }
-MOVES.update({"w9x128": 3, "w9x256": 3, "w19x64": 2, "c5x512": 30, "w9x128mz": 10, "l19x128": 1, "l13x96": 2, "w8x256oth": 30, "w3x256ttt": 100})
-WARM.update({"w9x128": 1, "w9x256": 1, "w19x64": 1, "c5x512": 14, "l19x128": 1, "l13x96": 1, "w8x256oth": 3, "w3x256ttt": 20})
+MOVES.update({"w9x128": 3, "w9x256": 3, "w19x64": 2, "c5x512": 30, "w9x128mz": 10, "l19x128": 1, "l13x96": 2, "w8x256oth": 30, "w3x256ttt": 100, "g15x64": 3, "g15x256": 2})
+WARM.update({"w9x128": 1, "w9x256": 1, "w19x64": 1, "c5x512": 14, "l19x128": 1, "l13x96": 1, "w8x256oth": 3, "w3x256ttt": 20, "g15x64": 1, "g15x256": 1})
 KERNEL.update({"w9x128mz": "sim_kernel_mz_wide<9,9,32,144,128>", "w9x128": "sim_kernel_wide<9,9,32,128,2>", "w9x256": "sim_kernel_wide<9,9,32,256,2>", "w19x64": "sim_kernel_wide<19,19,32,64,6>",
                "w8x256oth": "sim_kernel_wide<8,8,16,256,0>", "w3x256ttt": "sim_kernel_wide<3,3,16,256,-1>",
-               "l19x128": "conv3x3_band (lock-step worker: per-layer kernels)", "l13x96": "conv3x3_band (lock-step worker: per-layer kernels)"})
+               "l19x128": "conv3x3_band (lock-step worker: per-layer kernels)", "l13x96": "conv3x3_band (lock-step worker: per-layer kernels)",
+               "g15x64": "sim_kernel_wide<15,15,16,64,-2>", "g15x256": "conv3x3_band (lock-step worker: per-layer kernels, device rules gmk_leaf_kernel)"})
 
 
 def _by_kernel(s0, s1, launches):
