@@ -197,8 +197,9 @@ private:
     bool conv_only_ = false;    // timing mode: skip the heads
     DevBuf<char> sim_args_;     // SimArgs block of sim_kernel in device memory + the host copy it was uploaded from
     std::vector<char> sim_args_host_;
-    DevBuf<unsigned long long> sim_prof_; // MZ_SIM_PROF=1: per-phase tick counters of sim_kernel
+    DevBuf<unsigned long long> sim_prof_; // MZ_SIM_PROF=1: per-phase tick counters of sim_kernel (8 words per game) + the launches' finish times (kSimProfTail words)
     void dumpSimProf();
+    int simProfBuffer(int games, unsigned long long** prof); // allocates it at the first launch; folds the previous launch's finish times (sim.hip sim_prof_fold)
     void dumpRoundsProf(); // sim_rounds.hip: MZ_SIM_PROF=1, the shader clock under the multi-leaf trunks
     DevBuf<unsigned> sim_sink_;
     DevBuf<char> sim_cluster_mem_; // cluster mode of the MuZero simulation kernel (sim_cluster.h): per-game exchange blocks

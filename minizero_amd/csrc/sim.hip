@@ -463,6 +463,35 @@ static int launchSimT(const SimArgs* d_args, int games, const uint8_t* d_rot, in
     X(8, 8, 4, 8, 0)    /* small 8x8 Othello test nets */ \
     X(3, 3, 4, 16, -1)  /* TicTacToe, 16 channels (BASELINE configs[0]); CPL -1 = the TicTacToe rules */
 
+// MZ_SIM_PROF: between two launches (stream order), the running launch's words of the profile's tail (sim_az_body.h simProfEnter / simProfExit) are added to the
+// sums — [8] launches, [9] / [10] / [11] ticks from the earliest start of a game to the first exit, the last exit and the mean exit — and cleared for the next one
+__global__ void sim_prof_fold(unsigned long long* tail)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) { return; }
+    const unsigned long long n = tail[5];
+    if (n > 0) {
+        const unsigned long long start = tail[0];
+        tail[8] += 1;
+        tail[9] += tail[1] - start;
+        tail[10] += tail[2] - start;
+        tail[11] += tail[3] / n - start;
+    }
+    tail[0] = ~0ull; tail[1] = ~0ull; tail[2] = 0; tail[3] = 0; tail[5] = 0;
+    tail[4] = wall_clock64();
+}
+
+int Net::simProfBuffer(int games, unsigned long long** prof)
+{
+    if (sim_prof_.n == 0) {
+        if (!sim_prof_.alloc(size_t(games) * 8 + kSimProfTail)) { setError("hipMalloc of the profile buffer failed"); return MZ_ERR_DEVICE; }
+        MZ_HIP(hipMemsetAsync(sim_prof_.p, 0, sim_prof_.n * sizeof(unsigned long long), stream_));
+    }
+    hipLaunchKernelGGL(sim_prof_fold, dim3(1), dim3(1), 0, stream_, sim_prof_.p + sim_prof_.n - kSimProfTail);
+    MZ_HIP(hipGetLastError());
+    *prof = sim_prof_.p;
+    return MZ_OK;
+}
+
 void Net::dumpSimProf()
 {
 #ifdef MZ_SIM_BPROF
@@ -511,8 +540,20 @@ void Net::dumpSimProf()
     }
 #endif
     if (sim_prof_.n == 0) { return; }
+    hipLaunchKernelGGL(sim_prof_fold, dim3(1), dim3(1), 0, stream_, sim_prof_.p + sim_prof_.n - kSimProfTail); // the last launch's words
+    if (hipStreamSynchronize(stream_) != hipSuccess) { return; }
     std::vector<unsigned long long> h(sim_prof_.n);
     if (hipMemcpy(h.data(), sim_prof_.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) { return; }
+    const std::vector<unsigned long long> tail(h.end() - kSimProfTail, h.end());
+    h.resize(h.size() - kSimProfTail);
+    // word 4 of a game: its simulations, and above bit 32 those whose leaf was terminal, i.e. whose planes, tower and heads did not run (sim_kernel)
+    double skipped = 0, skipped_max = 0, sims_all = 0;
+    for (size_t g = 0; g < h.size() / 8; ++g) {
+        const double sk = double(h[g * 8 + 4] >> 32);
+        h[g * 8 + 4] &= 0xFFFFFFFFull;
+        skipped += sk; sims_all += double(h[g * 8 + 4]);
+        skipped_max = std::max(skipped_max, sk / std::max(1.0, double(h[g * 8 + 4])));
+    }
     { double ps = 0, ac = 0, kk = 0; for (size_t g = 0; g < h.size() / 8; ++g) { ps += double(h[g * 8 + 7] >> 40); ac += double((h[g * 8 + 7] >> 20) & 0xFFFFF); kk += double(h[g * 8 + 7] & 0xFFFFF); } fprintf(stderr, "[mz sim prof] path speculation: %.0f passes, %.0f levels taken, %.0f walks that found a remembered path\n", ps, ac, kk); }
     const char* names[4] = {"select+leaf", "tower", "heads", "cand+expand"};
     const size_t G = h.size() / 8;
@@ -535,6 +576,18 @@ void Net::dumpSimProf()
     }
     for (size_t g = 0; g < G; ++g) { tot_max = std::max(tot_max, double(h[g * 8] + h[g * 8 + 1] + h[g * 8 + 2] + h[g * 8 + 3]) / std::max(1.0, double(h[g * 8 + 4])) * 0.01); }
     fprintf(stderr, "[mz sim prof] total        avg %8.2f us per simulation (slowest game %8.2f us)\n", tot_all, tot_max);
+    {
+        double tw = 0, hd = 0;
+        for (size_t g = 0; g < G; ++g) { tw += double(h[g * 8 + 1]); hd += double(h[g * 8 + 2]); }
+        const double ran = std::max(1.0, sims_all - skipped);
+        fprintf(stderr, "[mz sim prof] terminal leaves: network skipped in %.0f of %.0f simulations (%.2f %%; the game with the most: %.2f %%) -> per simulation that ran them: tower %.2f us, heads %.2f us\n",
+                skipped, sims_all, 100.0 * skipped / std::max(1.0, sims_all), 100.0 * skipped_max, tw / ran * 0.01, hd / ran * 0.01);
+    }
+    if (tail[8] > 0) {
+        const double L = double(tail[8]), first = double(tail[9]) / L * 0.01, last = double(tail[10]) / L * 0.01, mean = double(tail[11]) / L * 0.01;
+        fprintf(stderr, "[mz sim prof] launches: %llu, avg per launch from the first game's start: first game done %.1f us, mean %.1f us, last %.1f us -> %.1f %% of the CU time idles at the end of a launch\n",
+                tail[8], first, mean, last, 100.0 * (last - mean) / std::max(1e-9, last));
+    }
 }
 
 // upper bound of the dynamic LDS a simulation kernel needs for searches of n simulations (the launch computes the exact figure)
@@ -626,11 +679,8 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     a.start = d_start;
     a.no_spec = getenv("MZ_NO_SPEC") ? atoi(getenv("MZ_NO_SPEC")) : 0;
     if (getenv("MZ_SIM_PROF")) {
-        if (sim_prof_.n == 0) {
-            if (!sim_prof_.alloc(size_t(gv.games) * 8)) { setError("hipMalloc of the profile buffer failed"); return MZ_ERR_DEVICE; }
-            MZ_HIP(hipMemset(sim_prof_.p, 0, sim_prof_.n * sizeof(unsigned long long)));
-        }
-        a.prof = sim_prof_.p;
+        rc = simProfBuffer(gv.games, &a.prof);
+        if (rc) { return rc; }
     }
     if (wide) { // sim_kernel_wide: its own LDS plan (sim_wide_a.hip)
         size_t scratch = std::max(std::max(goLeafSmemBytes(gv, pool.v_.max_depth), azCandSmemBytes(gv.A)), gumbelSmemBytes(gv.A));
@@ -794,11 +844,8 @@ int Net::simLaunchMz(Pool& pool, float* d_hidden, int slots, const unsigned* d_r
     }
     a.no_spec = getenv("MZ_NO_SPEC") ? atoi(getenv("MZ_NO_SPEC")) : 0;
     if (getenv("MZ_SIM_PROF")) {
-        if (sim_prof_.n == 0) {
-            if (!sim_prof_.alloc(size_t(pool.v_.games) * 8)) { setError("hipMalloc of the profile buffer failed"); return MZ_ERR_DEVICE; }
-            MZ_HIP(hipMemset(sim_prof_.p, 0, sim_prof_.n * sizeof(unsigned long long)));
-        }
-        a.prof = sim_prof_.p;
+        rc = simProfBuffer(pool.v_.games, &a.prof);
+        if (rc) { return rc; }
     }
     if (wide) { // sim_kernel_mz_wide (sim_wide_mz.hip): no leaves evaluated ahead (pre_epoch is ignored: every simulation evaluates its own leaf)
         a.cand_coop = candCoopSmemBytes(a.A, 8) <= wide_tile ? 1 : 0;

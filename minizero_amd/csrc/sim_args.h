@@ -42,7 +42,8 @@ struct SimArgs {
     int atari, action_planes;
     AtariHeadParams ahp;
     float* reward;                    // [games] reward head output (game scale)
-    int no_spec;                      // MZ_NO_SPEC=1: path speculation of the walk off (experiments)
+    int no_spec;                      // MZ_NO_SPEC bits (experiments, tests): 1 path speculation of the walk off, 2 helper waves off, 4 fault injection (sim_cluster.h),
+                                      // 8 the Go leaf in one piece, 16 the network also runs at terminal leaves (sim_kernel)
     int cand_coop;                    // the candidate rank sort is shared by the 8 waves (its scratch fits the tower tiles)
     // opt-in bf16x3 tower (net_bf16_body.h): fragments + layer table; used by the BF instantiations of sim_kernel
     const uint4* wfrag;
@@ -50,7 +51,7 @@ struct SimArgs {
     unsigned* cluster;                // cluster mode (sim_cluster.h): per-game exchange block of `cluster_words` words; nullptr: one workgroup per game
     int cluster_words, oct_words;
     unsigned* cluster_oct;            // cluster mode: the blocks of the octet-wide 601-bin heads ([8 octets][2 heads][oct_words]); nullptr: per-game heads
-    unsigned long long* prof;         // optional (MZ_SIM_PROF=1): per game, 100-MHz ticks spent in [select+leaf, tower, heads, cand+expand] + sims
+    unsigned long long* prof;         // optional (MZ_SIM_PROF=1): per game, 100-MHz ticks spent in [select+leaf, tower, heads, cand+expand] + sims; kSimProfTail words behind the games
     // leaves evaluated AHEAD of their simulations (sim_pre_kernel_mz below): one entry per (game, slot of the simulation) of the current move
     int* pre_key;                     // [games][slots][4] = {parent's slab slot, action, epoch of the move, -}
     float *pre_policy, *pre_logit;    // [games][slots][A]: the leaf's children in the reference's sort order (policy descending, zero_actor.cpp:241-243) ...

@@ -358,6 +358,32 @@ __device__ __noinline__ void simHeads(CSimArgs* __restrict__ a, int g, int tid, 
     simHeadsImpl<WPE, BIGA, FP>(a, g, tid, tiles, xtile, xcs, xpw, xchg);
 }
 
+// The terminal flag of the simulation's leaf: wave 0 wrote it into the hand-over block before the first barrier of the simulation (the leaf's first half), every
+// wave reads it behind that barrier.  Scalar, so that the branch on it is one s_cbranch.  MZ_NO_SPEC=16: the network runs at terminal leaves too (A/B, tests).
+__device__ __forceinline__ bool simLeafTerminal(CSimArgs* __restrict__ a, const float* xchg)
+{
+    if (a->no_spec & 16) { return false; }
+    const int A = a->gv.A;
+    const SimXchg x{A + (A & 1)};
+    return __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(xchg + x.scalars())[6]) != 0;
+}
+
+// MZ_SIM_PROF: the words behind the per-game counters (kSimProfTail of them).  [0..3] belong to the launch that is running — earliest start, first and last exit
+// of a game (100-MHz ticks from [4], the stamp of the previous fold), sum of the exits; sim_prof_fold (sim.hip) adds them to [8..] between two launches.
+constexpr int kSimProfTail = 16;
+__device__ __forceinline__ void simProfEnter(unsigned long long* tail)
+{
+    atomicMin(tail + 0, wall_clock64() - tail[4]);
+}
+__device__ __forceinline__ void simProfExit(unsigned long long* tail)
+{
+    const unsigned long long t = wall_clock64() - tail[4];
+    atomicMin(tail + 1, t);
+    atomicMax(tail + 2, t);
+    atomicAdd(tail + 3, t);
+    atomicAdd(tail + 5, 1ull);
+}
+
 // 8x8 boards: three tower tiles are 80 KB of LDS, so TWO games share a CU (16 waves) if the kernel stays within 128 VGPRs: one game's
 // tree phases and barrier bubbles are filled by the other's tower
 // waves per SIMD the kernel is compiled for: 4 (= two resident workgroups per CU, 128 VGPRs) for boards up to 64 points, whose tower
@@ -449,6 +475,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     unsigned long long* prof = a->prof ? a->prof + size_t(g) * 8 : nullptr;
     int* const node_count = reinterpret_cast<int*>(xchg) - 1; // (the spare word of the path block: simPathView)
     if (tid == 0) { *node_count = a->pv.num_nodes[g]; }
+    if (prof && tid == 0) { simProfEnter(a->prof + size_t(games) * 8); }
     __syncthreads();
     for (int s = 0; s < nsims; ++s) {
         const int slot = sim0 + s; // simulation index within the move = position slot of its leaf
@@ -463,26 +490,37 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
             simSelectHelper(a, g, lane, wave, s + 1, rcp_lds, spec);
         }
         __syncthreads();
+        // A terminal leaf has no children and its value is the game result (zero_actor.cpp:85): nobody reads the network's outputs, so planes, tower and heads
+        // are not run for it.  The flag is wave 0's (simLeafTerminal), read by every wave behind the barrier: the branches on it are uniform over the workgroup,
+        // and every wave passes the same barriers on either side.  (Each phase is skipped on its own, the barriers behind tower and heads stay where they are:
+        // with one branch around all three the 128-VGPR kernels spilled 34 VGPRs instead of 24 (23 before the skip), and BASELINE configs[2] ran 2-3 % slower.)
+        const bool term = simLeafTerminal(a, xchg);
         if constexpr (CPL > 0) {
-            simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
-            __syncthreads();
+            if (!term) {
+                simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
+                __syncthreads();
+            }
         }
         if (prof) { t1 = wall_clock64(); }
-        const float* xt;
-        if constexpr (BF) { xt = simTowerBf16<H, W>(a, g, tid, tiles, xchg); }
-        else if constexpr (WPE == 4) {
-            // The 128-VGPR build (two games per CU): as a function of its own the tower saved and restored 20 callee-saved VGPRs per call — 8 waves x 5 KB each way
-            // per simulation, most of the 118 KB of HBM traffic per leaf evaluation that rocprofv3 showed for BASELINE configs[2] (profiles/r04_pmc_c3.json).  Its
-            // 2 pixel tiles per wave fit the kernel's own budget.
-            const GoDevView gvt = simLeafView(ldc(&a->gv), xchg, g);
-            xt = towerBody<H, W, CIN0_PAD, CPAD>(reinterpret_cast<const float*>(gvt.feat), a->params, *(const TowerArgs*)&a->ta, nullptr, g, tid, tiles);
+        const float* xt = nullptr;
+        if (!term) {
+            if constexpr (BF) { xt = simTowerBf16<H, W>(a, g, tid, tiles, xchg); }
+            else if constexpr (WPE == 4) {
+                // The 128-VGPR build (two games per CU): as a function of its own the tower saved and restored 20 callee-saved VGPRs per call — 8 waves x 5 KB each way
+                // per simulation, most of the 118 KB of HBM traffic per leaf evaluation that rocprofv3 showed for BASELINE configs[2] (profiles/r04_pmc_c3.json).  Its
+                // 2 pixel tiles per wave fit the kernel's own budget.
+                const GoDevView gvt = simLeafView(ldc(&a->gv), xchg, g);
+                xt = towerBody<H, W, CIN0_PAD, CPAD>(reinterpret_cast<const float*>(gvt.feat), a->params, *(const TowerArgs*)&a->ta, nullptr, g, tid, tiles);
+            }
+            else { xt = simTower<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg); } // its own function: its own register budget
         }
-        else { xt = simTower<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg); } // its own function: its own register budget
         __syncthreads();
         if (prof) { t2 = wall_clock64(); }
-        if constexpr (WPE == 4) { simHeadsImpl<WPE>(a, g, tid, tiles, xt, planeStride(H, W), W + 2, xchg); }
+        // (the leaf's second half — a terminal leaf's score among it — runs on waves 6 and 7 either way; it passes two barriers, like the heads beside it)
+        if constexpr (WPE == 4) { if (!term) { simHeadsImpl<WPE>(a, g, tid, tiles, xt, planeStride(H, W), W + 2, xchg); } }
         else if (leaf_smem && wave >= 6) { simLeafRest<CPL>(a, rot, slot, g, lane, xchg, seen_lds, leaf_smem, 7 - wave); }
-        else { simHeads<WPE, false, (MZ_HEADS_FP != 0)>(a, g, tid, tiles, xt, planeStride(H, W), W + 2, xchg); }
+        else if (!term) { simHeads<WPE, false, (MZ_HEADS_FP != 0)>(a, g, tid, tiles, xt, planeStride(H, W), W + 2, xchg); }
+        else if (leaf_smem) { __syncthreads(); __syncthreads(); }
         __syncthreads();
         if (prof) { t3 = wall_clock64(); }
         if (wave == 0) { simCandGather<WPE>(a, rot, g, lane, tiles, xchg); }
@@ -501,10 +539,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         __syncthreads();
         if (prof && tid == 0) {
             t4 = wall_clock64();
-            prof[0] += t1 - t0; prof[1] += t2 - t1; prof[2] += t3 - t2; prof[3] += t4 - t3; prof[4] += 1;
+            // (a terminal leaf's second half, alone where the heads would be, counts as leaf time: "tower" and "heads" only hold simulations that ran them)
+            prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
+            prof[4] += 1 + (static_cast<unsigned long long>(term) << 32); // simulations | those whose network evaluation was skipped
         }
     }
     if (tid == 0) { a->pv.num_nodes[g] = *node_count; }
+    if (prof && tid == 0) { simProfExit(a->prof + size_t(games) * 8); }
     if (prof && tid == 0 && spec_w) {
         prof[7] += (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 1]) << 40) | (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 5]) << 20) | spec_w[kSpecWays * kSpecWay + 3];
         prof[6] += static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 7]) << 40; // levels taken over from the helper waves (the low bits hold the path lengths)

@@ -80,6 +80,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     unsigned long long* prof = a->prof ? a->prof + size_t(g) * 8 : nullptr;
     int* const node_count = reinterpret_cast<int*>(xchg) - 1; // (the spare word of the path block: simPathView)
     if (tid == 0) { *node_count = a->pv.num_nodes[g]; }
+    if (prof && tid == 0) { simProfEnter(a->prof + size_t(games) * 8); }
     __syncthreads();
     for (int s = 0; s < nsims; ++s) {
         const int slot = sim0 + s; // simulation index within the move = position slot of its leaf
@@ -94,16 +95,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
             simSelectHelper(a, g, lane, wave, s + 1, rcp_lds, spec);
         }
         __syncthreads();
+        const bool term = simLeafTerminal(a, xchg); // a terminal leaf: no planes, tower and heads (sim_az_body.h sim_kernel); the same barriers for every wave either way
         if constexpr (CPL > 0) {
-            simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
-            __syncthreads();
+            if (!term) {
+                simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
+                __syncthreads();
+            }
         }
         if (prof) { t1 = wall_clock64(); }
-        const float* xt = simTowerWide<H, W, CIN0Q, C>(a, g, tid, tiles, xchg); // its own function: its own register budget
+        const float* xt = nullptr;
+        if (!term) { xt = simTowerWide<H, W, CIN0Q, C>(a, g, tid, tiles, xchg); } // its own function: its own register budget
         __syncthreads();
         if (prof) { t2 = wall_clock64(); }
         if (leaf_smem && wave >= 6) { simLeafRest<CPL>(a, rot, slot, g, lane, xchg, seen_lds, leaf_smem, 7 - wave); }
-        else { simHeads<WPE, (H * W + 1 > 128), true>(a, g, tid, hscr, xt, G::CS, G::PW, xchg); }
+        else if (!term) { simHeads<WPE, (H * W + 1 > 128), true>(a, g, tid, hscr, xt, G::CS, G::PW, xchg); }
+        else if (leaf_smem) { __syncthreads(); __syncthreads(); } // (the two barriers of the leaf's second half on waves 6 and 7)
         __syncthreads();
         if (prof) { t3 = wall_clock64(); }
         if (wave == 0) { simCandGather<WPE>(a, rot, g, lane, tiles, xchg); }
@@ -122,10 +128,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         __syncthreads();
         if (prof && tid == 0) {
             t4 = wall_clock64();
-            prof[0] += t1 - t0; prof[1] += t2 - t1; prof[2] += t3 - t2; prof[3] += t4 - t3; prof[4] += 1;
+            // (a terminal leaf's second half, alone where the heads would be, counts as leaf time: "tower" and "heads" only hold simulations that ran them)
+            prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
+            prof[4] += 1 + (static_cast<unsigned long long>(term) << 32); // simulations | those whose network evaluation was skipped
         }
     }
     if (tid == 0) { a->pv.num_nodes[g] = *node_count; }
+    if (prof && tid == 0) { simProfExit(a->prof + size_t(games) * 8); }
     if (prof && tid == 0 && spec_w) {
         prof[7] += (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 1]) << 40) | (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 5]) << 20) | spec_w[kSpecWays * kSpecWay + 3];
         prof[6] += static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 7]) << 40;
