@@ -93,6 +93,9 @@ public:
     int simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_logit, float* d_value, const uint8_t* d_rot, int sim0, int nsims,
                   bool* launched, const float* d_root_noise = nullptr, float noise_eps = 0.0f, int noise_kind = 1, const struct GumbelView* gum = nullptr,
                   int* d_start = nullptr, bool host_start = false);
+    // tail help (sim_help.h): the caller has the GPU to itself and runs one simLaunch at a time — workgroups whose game is done may help the stragglers of their
+    // XCD with their towers (only the 9x9 x 64 f32 instance, launches of at least kSimHelpMinLaunch simulations, one workgroup per CU at most)
+    void allowTailHelp(bool on) { tail_help_ = on; }
     // num_simulation: the kernels keep per-search tables / the path in LDS; searches too long for 160 KB use the lock-step kernels
     bool hasSimKernel(int board_n, int env_kind = 0, int num_simulation = 0) const; // env_kind: GoDevView::kind
     // ... on the one-tile tower (sim_wide.inc, sim_wide_a.hip): Go with 128 / 256 hidden channels or on 7x7 / 13x13 / 19x19 boards
@@ -203,6 +206,8 @@ private:
     void dumpRoundsProf(); // sim_rounds.hip: MZ_SIM_PROF=1, the shader clock under the multi-leaf trunks
     DevBuf<unsigned> sim_sink_;
     DevBuf<char> sim_cluster_mem_; // cluster mode of the MuZero simulation kernel (sim_cluster.h): per-game exchange blocks
+    DevBuf<unsigned> sim_help_mem_; // tail help of sim_kernel (sim_help.h): per-game help blocks
+    bool tail_help_ = false;
     DevBuf<int> pre_key_;          // leaves evaluated ahead: keys [games][slots][4], outputs [policy | logit | value | reward], counters
     DevBuf<float> pre_out_;
     DevBuf<unsigned> pre_stat_;

@@ -456,6 +456,10 @@ static int launchSimT(const SimArgs* d_args, int games, const uint8_t* d_rot, in
     return MZ_OK;
 }
 
+// tail help (sim_help.h): launches shorter than this do not help, and a game with fewer simulations left than that is not claimed any more (a claim costs the
+// helper a scan of its XCD's games, ~2 us, and saves the owner ~50 us per simulation that runs the network: profiles/r08_pair_tower.txt)
+constexpr int kSimHelpMinLaunch = 64, kSimHelpMinLeft = 2;
+
 #define MZ_SIM_CASES(X) \
     X(9, 9, 20, 64, 2)  /* 9x9 Go, 64 channels (BASELINE configs[1]) */ \
     X(9, 9, 20, 8, 2)   /* small 9x9 test nets */ \
@@ -464,7 +468,8 @@ static int launchSimT(const SimArgs* d_args, int games, const uint8_t* d_rot, in
     X(3, 3, 4, 16, -1)  /* TicTacToe, 16 channels (BASELINE configs[0]); CPL -1 = the TicTacToe rules */
 
 // MZ_SIM_PROF: between two launches (stream order), the running launch's words of the profile's tail (sim_az_body.h simProfEnter / simProfExit) are added to the
-// sums — [8] launches, [9] / [10] / [11] ticks from the earliest start of a game to the first exit, the last exit and the mean exit — and cleared for the next one
+// sums — [8] launches, [9] / [10] / [11] ticks from the earliest start of a game to the first exit, the last exit and the mean exit, [12] mean ticks per CU spent
+// helping another game behind that exit — and cleared for the next one.  ([13] simulations that ran a pair tower, [14] their tower ticks, [15] games helped: running sums.)
 __global__ void sim_prof_fold(unsigned long long* tail)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) { return; }
@@ -475,8 +480,9 @@ __global__ void sim_prof_fold(unsigned long long* tail)
         tail[9] += tail[1] - start;
         tail[10] += tail[2] - start;
         tail[11] += tail[3] / n - start;
+        tail[12] += tail[6] / n; // tail help (sim_help.h): ticks per CU spent as a helper behind the own game's exit
     }
-    tail[0] = ~0ull; tail[1] = ~0ull; tail[2] = 0; tail[3] = 0; tail[5] = 0;
+    tail[0] = ~0ull; tail[1] = ~0ull; tail[2] = 0; tail[3] = 0; tail[5] = 0; tail[6] = 0;
     tail[4] = wall_clock64();
 }
 
@@ -585,8 +591,18 @@ void Net::dumpSimProf()
     }
     if (tail[8] > 0) {
         const double L = double(tail[8]), first = double(tail[9]) / L * 0.01, last = double(tail[10]) / L * 0.01, mean = double(tail[11]) / L * 0.01;
+        const double helping = double(tail[12]) / L * 0.01; // a CU that helps another game's tower is busy
         fprintf(stderr, "[mz sim prof] launches: %llu, avg per launch from the first game's start: first game done %.1f us, mean %.1f us, last %.1f us -> %.1f %% of the CU time idles at the end of a launch\n",
-                tail[8], first, mean, last, 100.0 * (last - mean) / std::max(1e-9, last));
+                tail[8], first, mean, last, 100.0 * (last - mean - helping) / std::max(1e-9, last));
+        if (tail[13] > 0 || tail[15] > 0) {
+            double tw = 0;
+            for (size_t g = 0; g < G; ++g) { tw += double(h[g * 8 + 1]); }
+            const double ran = sims_all - skipped, pn = double(tail[13]), pt = double(tail[14]);
+            fprintf(stderr, "[mz sim prof] tail help: %.0f of the %.0f simulations that ran the network had a pair tower (%.2f %%): tower %.2f us with a helper, %.2f us alone; %llu games helped, "
+                            "a CU helps for %.1f us per launch after its own game (%.1f %% of the launch)\n",
+                    pn, ran, 100.0 * pn / std::max(1.0, ran), pt / std::max(1.0, pn) * 0.01, (tw - pt) / std::max(1.0, ran - pn) * 0.01, tail[15], helping,
+                    100.0 * helping / std::max(1e-9, last));
+        }
     }
 }
 
@@ -698,6 +714,24 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
         if (!makeTowerArgsBf16(&a.tb)) { setError("simLaunch: bf16x3 tower not available for this network"); return MZ_OK; }
         a.wfrag = wfrag_.p;
     }
+    // Tail help (sim_help.h): the 9x9 x 64 f32 instance, at most one workgroup per CU (a helper must never keep a game from starting), not with MZ_NO_SPEC=32.
+    // The blocks are part of the argument block whenever the pool qualifies; whether a LAUNCH helps is a launch argument (bit 1 of host_start): only launches of
+    // at least kSimHelpMinLaunch simulations do (of the 1 + 16 + 383 of a BASELINE configs[1] move the last one) — in a short launch the games finish
+    // within a few simulations of each other and there is no tail to fill.  MZ_SIM_HELP_MIN=k (tests, experiments): launches of >= k simulations help, and a
+    // game is claimed while it has >= min(k, kSimHelpMinLeft) simulations left.
+    bool help = false;
+    if (tail_help_ && !bf && !(a.no_spec & 32) && H == 9 && W == 9 && c0 == 20 && C == 64 && a.ta.OT == 4 && gv.n == 9 && gv.kind == 0 && gv.games >= 2 && gv.games <= cu_count_ &&
+        gv.games <= 1024 && helpCmdUnits(gv.channels * gv.W32) <= kHpMaxUnits) {
+        const int env_min = getenv("MZ_SIM_HELP_MIN") ? std::max(1, atoi(getenv("MZ_SIM_HELP_MIN"))) : 0;
+        const size_t words = helpWords(C, H * W);
+        if (!sim_help_mem_.ensure(size_t(gv.games) * words)) { setError("hipMalloc of the help blocks failed"); return MZ_ERR_DEVICE; }
+        a.help = sim_help_mem_.p;
+        a.help_words = static_cast<int>(words);
+        a.help_min_left = env_min ? std::min(env_min, kSimHelpMinLeft) : kSimHelpMinLeft;
+        help = nsims >= (env_min ? env_min : kSimHelpMinLaunch);
+        if (help) { MZ_HIP(hipMemsetAsync(sim_help_mem_.p, 0, size_t(gv.games) * words * sizeof(unsigned), stream_)); }
+    }
+    const int start_bits = (host_start ? 1 : 0) | (help ? 2 : 0);
     // LDS: the tower tiles, and above them the reciprocal table; the heads and wave 0's tree phases take their scratch from the tiles
     const size_t tile_bytes = bf ? size_t(4) * ((((H + 2) * (W + 2) + 16) / 16) * 16) * 128 + size_t(64) * planeStride(H, W) * 4
                                  : size_t(kTowerTiles) * cmax * planeStride(H, W) * sizeof(float);
@@ -729,7 +763,7 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
         return MZ_OK;
     }
 #define MZ_SIM_LAUNCH(h, w, cin0, cpad, cpl) \
-    if (H == h && W == w && c0 == cin0 && C == cpad && gv.n == h && (gv.kind == 3 ? -2 : gv.kind == 2 ? -1 : gv.kind == 1 ? 0 : gv.W) == cpl) { *launched = true; return launchSimT<h, w, cin0, cpad, cpl>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, host_start ? 1 : 0, lds, stream_); }
+    if (H == h && W == w && c0 == cin0 && C == cpad && gv.n == h && (gv.kind == 3 ? -2 : gv.kind == 2 ? -1 : gv.kind == 1 ? 0 : gv.W) == cpl) { *launched = true; return launchSimT<h, w, cin0, cpad, cpl>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, start_bits, lds, stream_); }
     MZ_SIM_CASES(MZ_SIM_LAUNCH)
 #undef MZ_SIM_LAUNCH
     return MZ_OK;

@@ -43,7 +43,7 @@ struct SimArgs {
     AtariHeadParams ahp;
     float* reward;                    // [games] reward head output (game scale)
     int no_spec;                      // MZ_NO_SPEC bits (experiments, tests): 1 path speculation of the walk off, 2 helper waves off, 4 fault injection (sim_cluster.h),
-                                      // 8 the Go leaf in one piece, 16 the network also runs at terminal leaves (sim_kernel)
+                                      // 8 the Go leaf in one piece, 16 the network also runs at terminal leaves (sim_kernel), 32 no tail help (sim_help.h)
     int cand_coop;                    // the candidate rank sort is shared by the 8 waves (its scratch fits the tower tiles)
     // opt-in bf16x3 tower (net_bf16_body.h): fragments + layer table; used by the BF instantiations of sim_kernel
     const uint4* wfrag;
@@ -59,6 +59,10 @@ struct SimArgs {
     float *pre_value, *pre_reward;    // [games][slots], game scale
     unsigned* pre_stat;               // [0] simulations that found their leaf evaluated, [1] leaves evaluated ahead (tests / monitoring)
     int alt_base;                     // != 0: slots alt_base + s hold a SECOND expected leaf of simulation s (sim_pre_kernel_mz, hypothesis 1)
+    // tail help of sim_kernel (sim_help.h): a workgroup whose game is done computes half of the tower of a game of its XCD that still runs
+    int help_min_left;                // a game is only claimed while it has at least this many simulations of the launch left
+    unsigned* help;                   // per-game blocks of `help_words` words, cleared before every launch that helps; nullptr: never
+    int help_words;
 };
 
 // SimArgs never changes during a launch: the device functions read it through the CONSTANT address space, i.e. with scalar loads whose

@@ -67,6 +67,7 @@ __device__ unsigned long long g_bp[20];
 #include "go_body.h"
 #include "gumbel_body.h"
 #include "sim_args.h"
+#include "sim_help.h"
 #include <algorithm>
 #include <type_traits>
 #include <cstring>
@@ -417,6 +418,112 @@ __device__ __noinline__ const float* simTowerBf16(CSimArgs* __restrict__ a, int 
                                reinterpret_cast<char*>(tiles));
 }
 
+// Tail help (sim_help.h), owner side: the simulation's tower with the game's helper.  Wave 0 first sends the leaf's bit-packed planes — the command: 16-byte
+// stores of three words + the simulation's sequence number each — then the workgroup runs member 0 of the pair tower.  Its own function beside simTower, so
+// that the solo path keeps its register budget and code.  nullptr: the helper went missing (the error flag is raised, the workgroup leaves the kernel).
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __noinline__ const float* simTowerPair(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
+{
+    g = __builtin_amdgcn_readfirstlane(g);
+    seq = __builtin_amdgcn_readfirstlane(seq);
+    xseq = __builtin_amdgcn_readfirstlane(xseq);
+    const GoDevView gv = simLeafView(ldc(&a->gv), xchg, g);
+    const unsigned* bits = reinterpret_cast<const unsigned*>(gv.feat) + size_t(g) * gv.channels * gv.W32; // (the view's pointers are moved back by the game's offset)
+    unsigned* hb = a->help + size_t(g) * a->help_words;
+    const int fw = gv.channels * gv.W32;
+    if (tid < helpCmdUnits(fw)) {
+        hpu4 u;
+        u.x = bits[3 * tid];
+        u.y = 3 * tid + 1 < fw ? bits[3 * tid + 1] : 0u;
+        u.z = 3 * tid + 2 < fw ? bits[3 * tid + 2] : 0u;
+        u.w = unsigned(seq);
+        asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(hb + kHpCmd + 4 * tid), "v"(u) : "memory");
+    }
+    HelpCtx c{hb, 0, xseq, abort_lds, a->err};
+    return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c);
+}
+
+// Tail help, helper side: the workgroup of game g has finished its simulations of this launch and written its results.  It looks among the games of its XCD
+// (workgroups are dealt to the XCDs round-robin, so those are the games congruent to g mod 8; the XCC_ID every owner publishes is compared anyway) for the one
+// with the least progress that has no helper and at least help_min_left simulations left, claims it and computes member 1 of its pair towers until that game is
+// done; then it looks again, and leaves when there is nothing to claim.  `bits`: LDS for the planes of a command.  MZ_SIM_PROF: tail words [6] ticks spent as
+// a helper in this launch, [15] games helped.
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __noinline__ void simHelpTail(CSimArgs* __restrict__ a, int g, int tid, float* tiles, unsigned* bits, int nsims, int* s_help)
+{
+    g = __builtin_amdgcn_readfirstlane(g);
+    nsims = __builtin_amdgcn_readfirstlane(nsims);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int games = gridDim.x, words = a->help_words, min_left = a->help_min_left;
+    const int fw = a->gv.channels * a->gv.W32, units = helpCmdUnits(fw);
+    const unsigned myxcc = hpXccId();
+    unsigned long long* ptail = a->prof ? a->prof + size_t(games) * 8 : nullptr;
+    for (int round = 0; round < 64; ++round) { // (bounded: a round either claims a game, loses the claim to another helper, or ends the search)
+        if (wave == 0) {
+            unsigned key = ~0u; // (progress << 10) | game: the least progress wins
+            for (int o = (g & 7) + 8 * lane; o < games; o += 8 * 64) {
+                const unsigned* ob = a->help + size_t(o) * words;
+                const unsigned x = hpLoadU(ob + kHpXcc), p = hpLoadU(ob + kHpProgress), h = hpLoadU(ob + kHpHelper);
+                const unsigned k = (p << 10) | unsigned(o);
+                if (o != g && x == myxcc && h == 0u && int(p) + min_left <= nsims && k < key) { key = k; }
+            }
+            for (int o = 32; o > 0; o >>= 1) { const unsigned k2 = __shfl_xor(key, o); key = k2 < key ? k2 : key; }
+            if (lane == 0) {
+                int cl = 0;
+                if (key != ~0u) {
+                    unsigned expected = 0u;
+                    unsigned* hw = a->help + size_t(key & 1023u) * words + kHpHelper;
+                    cl = __hip_atomic_compare_exchange_strong(hw, &expected, unsigned(g) + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? int(key & 1023u) + 1 : -1;
+                }
+                s_help[1] = cl;
+                s_help[2] = int(key >> 10); // the owner's progress when it was chosen: every command for this helper has a higher sequence number
+            }
+        }
+        __syncthreads();
+        const int cl = __builtin_amdgcn_readfirstlane(s_help[1]);
+        unsigned last = unsigned(__builtin_amdgcn_readfirstlane(s_help[2]));
+        __syncthreads();
+        if (cl == 0) { return; }
+        if (cl < 0) { continue; }
+        const unsigned long long th0 = ptail ? wall_clock64() : 0;
+        unsigned* ob = a->help + size_t(cl - 1) * words;
+        HelpCtx c{ob, 1, 0u, s_help, a->err};
+        for (;;) {
+            if (wave == 0) { // the next command, or the end of the owner's launch
+                int st = 0;
+                hpu4 u;
+                for (int i = 0; i < kHpPollLimit && st == 0; ++i) {
+                    const unsigned* src = ob + kHpCmd + 4 * (lane < units ? lane : 0);
+                    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(u) : "v"(src) : "memory");
+                    const unsigned sq = __builtin_amdgcn_readfirstlane(u.w);
+                    if (__all(u.w == sq) && sq > last && sq <= unsigned(nsims)) { st = 1; last = sq; }
+                    else if (hpLoadU(ob + kHpProgress) >= unsigned(nsims)) { st = 2; }
+                    else { __builtin_amdgcn_s_sleep(4); }
+                }
+                if (st == 1 && lane < units) {
+                    bits[3 * lane] = u.x;
+                    if (3 * lane + 1 < fw) { bits[3 * lane + 1] = u.y; }
+                    if (3 * lane + 2 < fw) { bits[3 * lane + 2] = u.z; }
+                }
+                if (lane == 0) {
+                    if (st == 0) { atomicExch(a->err, 96); }
+                    s_help[1] = st;
+                }
+            }
+            __syncthreads();
+            const int st = __builtin_amdgcn_readfirstlane(s_help[1]);
+            if (st != 1) {
+                if (ptail && tid == 0) { atomicAdd(ptail + 6, wall_clock64() - th0); atomicAdd(ptail + 15, 1ull); }
+                if (st == 0) { return; }
+                break;
+            }
+            if (!towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c)) { return; }
+            __syncthreads();
+        }
+        __syncthreads();
+    }
+}
+
 template <int H, int W, int CIN0_PAD, int CPAD, int CPL, bool BF = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPerEu<H, W, CIN0_PAD, CPAD, BF>(), 4))) void sim_kernel(const SimArgs* __restrict__ a_, const uint8_t* __restrict__ rot_tab, int sim0, int nsims, int host_start)
 {
@@ -476,6 +583,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     int* const node_count = reinterpret_cast<int*>(xchg) - 1; // (the spare word of the path block: simPathView)
     if (tid == 0) { *node_count = a->pv.num_nodes[g]; }
     if (prof && tid == 0) { simProfEnter(a->prof + size_t(games) * 8); }
+    // Tail help (sim_help.h; bit 1 of host_start: this launch helps): the game publishes the XCD it runs on — from here on it can be claimed by a workgroup of
+    // that XCD whose own game is done.  s_help: [0] abort flag of the exchanges, [1] the game's helper (0: none) as of this simulation, [2] the helper's scratch.
+    constexpr bool kHelp = !BF && WPE == 2 && CPL > 0 && pairTowerShape<H, W, CPAD>();
+    __shared__ int s_help[4];
+    const bool help_on = kHelp && (host_start & 2) != 0;
+    unsigned* const help_blk = help_on ? a->help + size_t(g) * a->help_words : nullptr;
+    unsigned help_xseq = 0;                        // layer exchanges of this game's pair towers so far
+    unsigned long long pair_n = 0, pair_t = 0;     // (MZ_SIM_PROF) simulations that ran a pair tower, their tower ticks
+    if (help_on && tid == 0) { s_help[0] = 0; s_help[1] = 0; hpStoreU(help_blk + kHpXcc, hpXccId()); }
     __syncthreads();
     for (int s = 0; s < nsims; ++s) {
         const int slot = sim0 + s; // simulation index within the move = position slot of its leaf
@@ -484,12 +600,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         if (prof) { t0 = wall_clock64(); }
         if (wave == 0) {
             if (slot == 1 && a->root_noise) { simApplyRootNoise<WPE>(a, g, lane); }
-            if (a->use_gumbel) { simGumbelStart<WPE>(a, slot, s == 0 && host_start != 0, g, lane, tiles); }
+            if (a->use_gumbel) { simGumbelStart<WPE>(a, slot, s == 0 && (host_start & 1) != 0, g, lane, tiles); }
             simSelectLeaf<CPL, WPE>(a, rot, slot, g, lane, tiles, rcp_lds, spec, xchg, seen_lds, (a->no_spec & 2) ? 0 : s + 1, leaf_smem);
         } else if (WPE == 2 && wave <= kHelpSegs && spec.w && !(a->no_spec & 2)) { // (MZ_NO_SPEC=2: helper segments off)
             simSelectHelper(a, g, lane, wave, s + 1, rcp_lds, spec);
+        } else if (kHelp && help_on && tid == 7 * 64) {
+            // has a helper claimed this game?  Looked up past the vector cache by a wave that has no part in the walk, handed to all waves behind the walk's
+            // barrier: the branch "pair tower or solo tower" is uniform over the workgroup, and a game without a helper pays nothing for looking
+            s_help[1] = int(hpLoadU(help_blk + kHpHelper));
         }
         __syncthreads();
+        const bool pair = kHelp && help_on && __builtin_amdgcn_readfirstlane(s_help[1]) != 0;
         // A terminal leaf has no children and its value is the game result (zero_actor.cpp:85): nobody reads the network's outputs, so planes, tower and heads
         // are not run for it.  The flag is wave 0's (simLeafTerminal), read by every wave behind the barrier: the branches on it are uniform over the workgroup,
         // and every wave passes the same barriers on either side.  (Each phase is skipped on its own, the barriers behind tower and heads stay where they are:
@@ -511,6 +632,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                 // 2 pixel tiles per wave fit the kernel's own budget.
                 const GoDevView gvt = simLeafView(ldc(&a->gv), xchg, g);
                 xt = towerBody<H, W, CIN0_PAD, CPAD>(reinterpret_cast<const float*>(gvt.feat), a->params, *(const TowerArgs*)&a->ta, nullptr, g, tid, tiles);
+            }
+            else if constexpr (kHelp) {
+                if (pair) { // with the game's helper: half of the output channels each (sim_help.h)
+                    xt = simTowerPair<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg, s + 1, help_xseq, s_help);
+                    if (!xt) { return; } // the helper went missing: the error flag is raised
+                    help_xseq += unsigned(a->ta.nlayers);
+                }
+                else { xt = simTower<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg); }
             }
             else { xt = simTower<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg); } // its own function: its own register budget
         }
@@ -542,13 +671,27 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
             // (a terminal leaf's second half, alone where the heads would be, counts as leaf time: "tower" and "heads" only hold simulations that ran them)
             prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
             prof[4] += 1 + (static_cast<unsigned long long>(term) << 32); // simulations | those whose network evaluation was skipped
+            if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
         }
+        if (kHelp && help_on && tid == 0) { hpStoreU(help_blk + kHpProgress, unsigned(s) + 1u); } // (nsims: the game is done, its helper looks for another one)
     }
     if (tid == 0) { a->pv.num_nodes[g] = *node_count; }
-    if (prof && tid == 0) { simProfExit(a->prof + size_t(games) * 8); }
+    if (prof && tid == 0) {
+        simProfExit(a->prof + size_t(games) * 8);
+        if (pair_n) { atomicAdd(a->prof + size_t(games) * 8 + 13, pair_n); atomicAdd(a->prof + size_t(games) * 8 + 14, pair_t); }
+    }
     if (prof && tid == 0 && spec_w) {
         prof[7] += (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 1]) << 40) | (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 5]) << 20) | spec_w[kSpecWays * kSpecWay + 3];
         prof[6] += static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 7]) << 40; // levels taken over from the helper waves (the low bits hold the path lengths)
+    }
+    if constexpr (kHelp) {
+        // this game is done and its results are written: the CU helps the stragglers of its XCD with their towers instead of idling to the end of the launch
+        if (help_on) {
+            const int A = a->gv.A;
+            const SimXchg x{A + (A & 1)};
+            __syncthreads();
+            simHelpTail<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, reinterpret_cast<unsigned*>(xchg + x.feat()), nsims, s_help);
+        }
     }
 }
 

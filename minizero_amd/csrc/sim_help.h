@@ -1,0 +1,173 @@
+// Tail help of the one-game-per-CU simulation kernel (sim_az_body.h): a workgroup whose game has finished the launch's simulations becomes the HELPER of a game
+// of its XCD that is still running and computes half of the output channels of that game's tower.
+//
+// The games of a launch do not cost the same (terminal leaves skip the network, paths differ in depth), the launch lasts as long as its slowest game, and a CU
+// whose game is done has nothing else to run: every phase of a game is a dependent chain on one CU.  What an idle CU can take over is half of another game's
+// tower, with the building blocks of the MuZero cluster (sim_cluster.h):
+//  * pair tower: member m (0 = the game's own workgroup, the owner; 1 = the helper) computes oc-tiles 2 m and 2 m + 1 of every layer for all pixel tiles — 12
+//    (oc-tile, pixel-tile) units on 8 waves, three tiles per SIMD — with the layer function of the solo tower (tower_layer_geo, XOUT epilogue): every output is the
+//    same tap-major, k-ordered chain, so the activations are bit-identical to the solo tower's;
+//  * after each layer the members swap their 32 x P outputs through two alternating buffers in global memory, i.e. through the L2 of the XCD they share, with
+//    self-validating words (the phase of the exchange in the sign bit of the ReLU outputs) and loads past the vector cache; after the last layer only the owner reads;
+//  * the owner tells the helper what to compute with 16-byte stores that each carry the simulation's sequence number (three words of the leaf's bit-packed
+//    planes + the sequence number), so the helper needs no other input and never touches the tree.
+// Every wait is bounded; a time-out raises the pool's error flag and both sides leave the kernel.  No workgroup waits for one that is not running: a helper only
+// claims a game that has published its XCC_ID in this launch, an owner only waits for a helper that has claimed it.
+#pragma once
+#include "net_body.h"
+
+namespace mz {
+
+// per-game help block in global memory (32-bit words); the host clears it before every launch that may help
+constexpr int kHpXcc = 0;       // XCC_ID + 1 of the owner (0: the game's workgroup has not started yet)
+constexpr int kHpProgress = 1;  // simulations of this launch the owner has finished
+constexpr int kHpHelper = 32;   // 0 or (helper's game index + 1), claimed by compare-and-swap (a 128-byte line of its own: the owner reads it at every simulation)
+constexpr int kHpCmd = 64;      // up to 64 units of 16 bytes: {three words of the leaf's planes, sequence number of the simulation}
+constexpr int kHpXbuf = 320;    // 2 x [C][P] floats
+constexpr int kHpPollLimit = 1 << 21;
+constexpr int kHpMaxUnits = 64;
+typedef unsigned hpu4 __attribute__((ext_vector_type(4)));
+inline size_t helpWords(int C, int P) { return (size_t(kHpXbuf) + 2 * size_t(C) * P + 31) / 32 * 32; }
+__host__ __device__ constexpr int helpCmdUnits(int feat_words) { return (feat_words + 2) / 3; }
+
+// loads that are served by the L2 (relaxed agent-scope atomic load = global_load_dword sc1), stores that the compiler may not delay or merge
+__device__ __forceinline__ unsigned hpLoadU(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ float hpLoadF(const float* p) { return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
+__device__ __forceinline__ void hpStoreU(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned hpXccId()
+{
+    unsigned id;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(id));
+    return (id & 15u) + 1u;
+}
+
+struct HelpCtx {
+    unsigned* hb;   // the helped game's block
+    int member;     // 0 owner, 1 helper
+    unsigned xseq;  // layer exchanges of this game so far in this launch
+    int* abort_lds; // workgroup-wide abort flag
+    int* err;
+};
+
+// my 16 x P block of the exchange buffer for the NEXT exchange, and the tag its words carry (the two buffers alternate, the phase flips each time a buffer is
+// reused; the host clears them: phase 0 = "never written", the first use writes 1)
+template <int CPAD, int P>
+__device__ __forceinline__ float* hpPart(const HelpCtx& c, int ot) { return reinterpret_cast<float*>(c.hb + kHpXbuf) + size_t(c.xseq & 1) * CPAD * P + size_t(ot) * 16 * P; }
+__device__ __forceinline__ unsigned hpSign(const HelpCtx& c) { return (((c.xseq >> 1) & 1u) ^ 1u) << 31; }
+
+// All 512 threads of both members, after a layer: my 32 channels are in LDS (`tout`, padded planes) and on their way to the exchange buffer; on return the other
+// member's 32 channels are in `tout` too.  false: the other member went missing (the caller leaves the kernel).  read = false (the helper after the last layer):
+// nobody needs the owner's half any more.  A member overwrites a buffer only after it has read the exchange in between, i.e. after the other one has finished
+// reading this one; the helper's skipped read is made up for by its wait for the next simulation's command, which the owner sends after it has read everything.
+template <int H, int W, int CPAD>
+__device__ __forceinline__ bool hpExchange(HelpCtx& c, float* __restrict__ tout, int tid, bool read)
+{
+    constexpr int P = H * W, PW = W + 2, CS = planeStride(H, W), HALF = CPAD / 2 * P;
+    const unsigned sign = hpSign(c);
+    const int other = 1 - c.member;
+    const float* xb = reinterpret_cast<const float*>(c.hb + kHpXbuf) + size_t(c.xseq & 1) * CPAD * P + size_t(other) * HALF;
+    ++c.xseq;
+    __syncthreads(); // the member's own waves are done with the layer: all waves start polling together
+    if (!read) { return true; }
+    constexpr int K = (HALF + 511) / 512;
+    unsigned got[K];
+    bool ok = false;
+    for (int polls = 0; polls < kHpPollLimit; ++polls) {
+        ok = true;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const int i = tid + j * 512;
+            const bool want = i < HALF;
+            got[j] = __float_as_uint(hpLoadF(xb + (want ? i : 0)));
+            ok = ok && (!want || (got[j] & 0x80000000u) == sign);
+        }
+        ok = __all(ok);
+        if (ok) { break; }
+        __builtin_amdgcn_s_sleep(2);
+    }
+    if (!ok && (tid & 63) == 0) { *c.abort_lds = 1; atomicExch(c.err, 95); }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int i = tid + j * 512;
+        if (i < HALF) {
+            const int ch = other * (CPAD / 2) + i / P, p = i % P;
+            tout[ch * CS + (p / W + 1) * PW + (p % W) + 1] = __uint_as_float(got[j] & 0x7FFFFFFFu);
+        }
+    }
+    __syncthreads();
+    return *c.abort_lds == 0;
+}
+
+// the layer sequence of one wave of a member: oc-tile `ot` x the NT pixel tiles from `tile0` (CORNER: the last of them is the corner tile)
+template <int H, int W, int CIN0_PAD, int CPAD, int NT, bool CORNER>
+__device__ __forceinline__ bool pairRun(const float* __restrict__ params, const TowerArgs& ta, float* __restrict__ T0, float* __restrict__ T1, int lane, int tid, int ot,
+                                        int tile0, HelpCtx& c)
+{
+    constexpr int P = H * W;
+    const PixSet<NT> px = makePixSet<H, W, NT>(lane, tile0);
+    float aS[CIN0_PAD / 4], aA[CPAD / 4], aB[CPAD / 4];
+    bool have = false;
+    if (ta.has_stem) {
+        const float* nw = ta.nlayers > 1 ? params + ta.w_off[1] : nullptr;
+        tower_layer<H, W, CIN0_PAD / 4, NT, CPAD / 4, CORNER, false, true>(T0, nullptr, T1, nullptr, params + ta.w_off[0], params + ta.b_off[0], ta.C, ta.OT, lane, ot, px, false,
+                                                                           aS, nw, aA, hpPart<CPAD, P>(c, ot), hpSign(c));
+        have = nw != nullptr;
+        if (!hpExchange<H, W, CPAD>(c, T1, tid, c.member == 0 || ta.nlayers > 1)) { return false; }
+    }
+    float *x = T1, *tmp = T0;
+#pragma unroll 1
+    for (int l = ta.has_stem; l < ta.nlayers; ++l) {
+        const bool second = ((l - ta.has_stem) & 1) != 0, last = l + 1 == ta.nlayers;
+        tower_layer<H, W, CPAD / 4, NT, CPAD / 4, CORNER, false, true>(second ? tmp : x, second ? x : nullptr, second ? x : tmp, nullptr, params + ta.w_off[l], params + ta.b_off[l],
+                                                                       ta.C, ta.OT, lane, ot, px, have, aA, last ? nullptr : params + ta.w_off[l + 1], aB, hpPart<CPAD, P>(c, ot),
+                                                                       hpSign(c));
+#pragma unroll
+        for (int cg = 0; cg < CPAD / 4; ++cg) { aA[cg] = aB[cg]; }
+        have = !last;
+        if (!hpExchange<H, W, CPAD>(c, second ? x : tmp, tid, c.member == 0 || !last)) { return false; }
+    }
+    return true;
+}
+
+// shapes the pair tower covers: 4 oc-tiles (two per member), 6 pixel tiles the last of which is the corner tile (9x9)
+template <int H, int W, int CPAD>
+constexpr bool pairTowerShape() { return CPAD == 64 && TileMap<H, W>::PT == 6 && TileMap<H, W>::kCorner; }
+
+// The tower of one simulation on a pair of workgroups: each member unpacks the leaf's planes (`bits`: cin0 x ceil(P / 32) words) into its own LDS tile, computes
+// its two oc-tiles of every layer and swaps them with the other member; the owner ends with the complete output x in its tile T1 (returned), the helper with all
+// but the owner's half of the last layer.  nullptr: aborted.
+// Waves w and w + 4 share a SIMD.  SIMD s works on oc-tile 2 m + s / 2: the wave of the lower half takes two full pixel tiles (0, 1 or 3, 4), its partner one
+// (tile 2, or the corner tile 5) with the higher priority, like the wave with fewer accumulator chains of the solo tower (net_body.h towerBody): at most
+// 3 x 144 = 432 MFMAs per SIMD and layer instead of 784.
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __forceinline__ float* towerBodyPair(const unsigned* __restrict__ bits, const float* __restrict__ params, const TowerArgs& ta, int tid, float* __restrict__ tiles,
+                                                HelpCtx& c)
+{
+    static_assert(pairTowerShape<H, W, CPAD>(), "pair tower: two oc-tiles per member, pixel tiles {0, 1}, {2}, {3, 4}, {corner}");
+    constexpr int P = H * W, PW = W + 2, CS = planeStride(H, W), W32 = (P + 31) / 32;
+    constexpr int CMAX = CIN0_PAD > CPAD ? CIN0_PAD : CPAD;
+    const int lane = tid & 63, wave = tid >> 6;
+    float* T0 = tiles;
+    float* T1 = tiles + CMAX * CS;
+    for (int i = tid; i < kTowerTiles * CMAX * CS / 4; i += 512) { reinterpret_cast<float4*>(tiles)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    __syncthreads();
+    float* Tin = ta.has_stem ? T0 : T1;
+    for (int i = tid; i < ta.cin0 * P; i += 512) {
+        const int ch = i / P, p = i - ch * P;
+        Tin[ch * CS + (p / W + 1) * PW + (p % W) + 1] = ((bits[ch * W32 + (p >> 5)] >> (p & 31)) & 1u) ? 1.0f : 0.0f;
+    }
+    __syncthreads();
+    const int simd = wave & 3, ot = 2 * c.member + (simd >> 1), grp = simd & 1;
+    bool ok;
+    if (wave < 4) {
+        ok = pairRun<H, W, CIN0_PAD, CPAD, 2, false>(params, ta, T0, T1, lane, tid, ot, 3 * grp, c);
+    } else {
+        __builtin_amdgcn_s_setprio(2);
+        if (grp == 0) { ok = pairRun<H, W, CIN0_PAD, CPAD, 1, false>(params, ta, T0, T1, lane, tid, ot, 2, c); }
+        else { ok = pairRun<H, W, CIN0_PAD, CPAD, 1, true>(params, ta, T0, T1, lane, tid, ot, 5, c); }
+        __builtin_amdgcn_s_setprio(0);
+    }
+    return ok ? T1 : nullptr;
+}
+
+} // namespace mz

@@ -1624,6 +1624,7 @@ int Worker::runCyclesSim(int n)
                         if (pre) { ++stats_.sim_launches; ++stats_.pre_launches; }
                     }
                 }
+                L->net->allowTailHelp(cfg_.mz_sim_round_pairs && plan_.lanes == 1); // (sim_help.h: only with the GPU to itself, one launch at a time)
                 int rc = plan_.sim_mz ? L->net->simLaunchMz(L->pool, L->d_hidden.p, plan_.slab_slots, L->d_rootfeat.p, L->d_rootlegal.p, L->d_rootturn.p,
                                                       games_[0].env->numPlayers(), L->d_policy.p, L->d_logit.p, L->d_value.p, L->d_reward.p, sim0 + c0, c1 - c0,
                                                       &launched, noise_in_batch ? L->d_noise.p : nullptr, cfg_.actor_dirichlet_noise_epsilon, noise_kind,
