@@ -72,6 +72,9 @@ inline std::string mzgpuCollectConfiguration()
 #elif defined(GOMOKU) && GOMOKU
     // the two keys the reference registers for this game only (configuration.cpp:179-181)
     o << "env_gomoku_rule=" << env_gomoku_rule << ":env_gomoku_exactly_five_stones=" << env_gomoku_exactly_five_stones << ":env_game=gomoku";
+#elif defined(HEX) && HEX
+    // the key the reference registers for this game only (configuration.cpp:185)
+    o << "env_hex_use_swap_rule=" << env_hex_use_swap_rule << ":env_game=hex";
 #elif defined(ATARI) && ATARI
     o << "env_game=atari:atari_init_q=true"; // the #if ATARI init-Q rule of mcts.cpp:211-216
 #else

@@ -343,7 +343,7 @@ int mz_godev_playout(int device, int board_size, float komi, const int* actions,
 /* the same for any game with a device engine ("go", "othello", "tictactoe"): feat_out [steps][channels*ceil(P/32)], legal_out [steps][actions] */
 int mz_envdev_playout(int device, const char* game, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots,
                       uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
-/* ... with the game and its rules from a configuration string as mz_env_create takes it (env_game=gomoku:env_gomoku_rule=outer_open:...) */
+/* ... with the game and its rules from a configuration string as mz_env_create takes it (env_game=gomoku:env_gomoku_rule=outer_open:..., env_game=hex:env_hex_use_swap_rule=false) */
 int mz_envdev_playout_conf(int device, const char* conf, const int* actions, int count, int root_prefix, const int* rots,
                            uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
 int mz_sort_candidates(int device, const float* policy, int n, int* order_out);

@@ -54,6 +54,7 @@ struct WorkerConfig {
     std::string env_go_ko_rule = "positional";
     std::string env_gomoku_rule = "standard"; // env_game=gomoku only: "outer_open" restricts the first move, any other value is the standard rule
     bool env_gomoku_exactly_five_stones = true;
+    bool env_hex_use_swap_rule = true; // env_game=hex only (ref hex.cpp:28-47): the second action may take over the first stone
     // run-time replacements of the reference's compile-time switches (-D<GAME>, #if ATARI in mcts.cpp:211)
     std::string env_game = "tictactoe";
     bool atari_init_q = false;

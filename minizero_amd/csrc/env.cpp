@@ -6,6 +6,7 @@
 //   Othello : two 64-bit bitboards, shift-and-mask move generation (8x8 and smaller).
 //   TicTacToe: two 9-bit masks.
 //   Gomoku  : two bitboards of up to 6 words, the winner from the four lines through the last stone.
+//   Hex     : two bitboards of up to 6 words, the winner from an early-exit flood of the mover's group through the last stone.
 // All feature planes are written straight into caller memory (the worker's pinned staging buffer).
 #include "env.h"
 #include "go_dev.h"
@@ -53,15 +54,27 @@ void RotationTables::build(int n, int num_actions)
     }
 }
 
-static const RotationTables* rotationTables(int n, int num_actions)
+// a game without symmetries (Hex: ref hex.h:61-62,78-79 getRotatePosition / getRotateAction return their argument): all eight maps are the identity
+void RotationTables::buildIdentity(int n, int num_actions)
+{
+    board_size = n;
+    for (int r = 0; r < 8; ++r) {
+        fwd[r].resize(num_actions);
+        inv[r].resize(n * n);
+        for (int a = 0; a < num_actions; ++a) { fwd[r][a] = a; }
+        for (int p = 0; p < n * n; ++p) { inv[r][p] = p; }
+    }
+}
+
+static const RotationTables* rotationTables(int n, int num_actions, bool identity = false)
 {
     static std::mutex mu;
     static std::map<std::pair<int, int>, std::unique_ptr<RotationTables>> cache;
     std::lock_guard<std::mutex> lock(mu);
-    auto& slot = cache[{n, num_actions}];
+    auto& slot = cache[{identity ? -n : n, num_actions}];
     if (!slot) {
         slot = std::make_unique<RotationTables>();
-        slot->build(n, num_actions);
+        if (identity) { slot->buildIdentity(n, num_actions); } else { slot->build(n, num_actions); }
     }
     return slot.get();
 }
@@ -429,6 +442,148 @@ private:
     int n_, P_;
     bool outer_open_, exactly_five_;
     int winner_;
+    uint64_t s_[2][kW];
+};
+
+// ---------------------------------------------------------------------------------------------
+// Hex, board <= 19x19 (ref hex.cpp:13-141,307-362): two bitboards of up to 6 words.  Black (player 1) connects column 0 with column n - 1, White row 0
+// with row n - 1 (hex.cpp:51-61); the neighbours of (x, y) are (x-1,y-1) (x,y-1) (x-1,y) (x+1,y) (x,y+1) (x+1,y+1) (hex.cpp:319-336).  The reference
+// propagates two edge flags per cell; here the winner is the mover when the mover's group through the new stone touches both of the mover's edges (the same
+// answer), found by a flood from that stone that stops as soon as both edges are reached.  Terminal <=> a winner exists.  With the swap rule
+// (env_hex_use_swap_rule, hex.cpp:28-47,86-99) every cell is legal on the second action, and choosing the occupied one replaces Black's stone by a White
+// stone on its reflection; the record keeps the chosen action id.  No pass action, no symmetries: the rotation tables are the identity.
+// ---------------------------------------------------------------------------------------------
+class Hex final : public GameEnv {
+    static constexpr int kW = (19 * 19 + 63) / 64;
+public:
+    Hex(int n, bool swap) : n_(n), P_(n * n), swap_(swap)
+    {
+        rot_ = rotationTables(n, n * n, true);
+        reset();
+    }
+    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<Hex>(*this); }
+    void copyFrom(const GameEnv& o) override { *this = static_cast<const Hex&>(o); }
+    void reset() override
+    {
+        turn_ = 1;
+        action_ids_.clear();
+        action_players_.clear();
+        memset(s_, 0, sizeof(s_));
+        winner_ = 0;
+        nact_ = 0;
+        first_ = -1;
+    }
+    bool stone(int c, int p) const { return (s_[c][p >> 6] >> (p & 63)) & 1; }
+    bool isLegal(int a, int) const override // ref hex.cpp:86-99: an empty cell, or any cell on the second action under the swap rule
+    {
+        if (a < 0 || a >= P_) { return false; }
+        return (swap_ && nact_ == 1) || (!stone(0, a) && !stone(1, a));
+    }
+    bool act(int a, int player) override
+    {
+        if (!isLegal(a, player)) { return false; }
+        actUnchecked(a, player);
+        return true;
+    }
+    void actUnchecked(int a, int player) override
+    {
+        int p = a;
+        if (swap_ && nact_ == 1 && a == first_) { // ref hex.cpp:28-47: the first stone goes, the mover's stone lands on its reflection
+            s_[0][a >> 6] &= ~(1ull << (a & 63));
+            s_[1][a >> 6] &= ~(1ull << (a & 63));
+            p = (n_ - 1 - a % n_) * n_ + (n_ - 1 - a / n_);
+        }
+        s_[player - 1][p >> 6] |= 1ull << (p & 63);
+        if (nact_ == 0) { first_ = a; }
+        ++nact_;
+        action_ids_.push_back(static_cast<int16_t>(a)); // the chosen id, also for a swap (B[k];W[k])
+        action_players_.push_back(static_cast<uint8_t>(player));
+        turn_ = 3 - player;
+        if (winner_ == 0 && connects(p, player - 1)) { winner_ = player; } // a winner never goes away
+    }
+    // does the group of colour c through p touch both of c's edges?  (a stack flood over the six neighbours, ended by the second edge)
+    bool connects(int p, int c) const
+    {
+        uint64_t seen[kW] = {};
+        int16_t stack[19 * 19];
+        int top = 0;
+        bool lo = false, hi = false;
+        stack[top++] = static_cast<int16_t>(p);
+        seen[p >> 6] |= 1ull << (p & 63);
+        static const int dx[6] = {-1, 0, -1, 1, 0, 1}, dy[6] = {-1, -1, 0, 0, 1, 1};
+        while (top) {
+            const int q = stack[--top], x = q % n_, y = q / n_;
+            const int along = c == 0 ? x : y; // Black: columns, White: rows
+            lo |= along == 0;
+            hi |= along == n_ - 1;
+            if (lo && hi) { return true; }
+            for (int k = 0; k < 6; ++k) {
+                const int u = x + dx[k], v = y + dy[k];
+                if (u < 0 || u >= n_ || v < 0 || v >= n_) { continue; }
+                const int r = v * n_ + u;
+                if (!stone(c, r) || ((seen[r >> 6] >> (r & 63)) & 1)) { continue; }
+                seen[r >> 6] |= 1ull << (r & 63);
+                stack[top++] = static_cast<int16_t>(r);
+            }
+        }
+        return false;
+    }
+    void legalMask(uint8_t* out) const override { for (int a = 0; a < P_; ++a) { out[a] = isLegal(a, turn_); } }
+    bool isTerminal() const override { return winner_ != 0; } // ref hex.cpp:101-104
+    float evalScore(bool is_resign) const override { return scoreOf(is_resign ? 3 - turn_ : winner_); } // ref hex.cpp:106-116
+    void features(int, float* out) const override // ref hex.cpp:118-141: own, opponent, black to move, white to move; the rotation is ignored
+    {
+        for (int p = 0; p < P_; ++p) {
+            out[p] = stone(turn_ - 1, p) ? 1.0f : 0.0f;
+            out[P_ + p] = stone(2 - turn_, p) ? 1.0f : 0.0f;
+            out[2 * P_ + p] = turn_ == 1 ? 1.0f : 0.0f;
+            out[3 * P_ + p] = turn_ == 2 ? 1.0f : 0.0f;
+        }
+    }
+    void featureBits(int, uint32_t* out) const override
+    {
+        const int W32 = (P_ + 31) / 32;
+        for (int i = 0; i < 4 * W32; ++i) { out[i] = 0; }
+        for (int p = 0; p < P_; ++p) {
+            const uint32_t b = 1u << (p & 31);
+            if (stone(turn_ - 1, p)) { out[p >> 5] |= b; }
+            if (stone(2 - turn_, p)) { out[W32 + (p >> 5)] |= b; }
+            out[(turn_ == 1 ? 2 : 3) * W32 + (p >> 5)] |= b;
+        }
+    }
+    int actionFromString(const std::string& str) const override // board coordinates ("F6"); no pass action
+    {
+        std::string up = str;
+        for (char& c : up) { c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
+        if (up == "PASS") { return -1; }
+        const int a = GameEnv::actionFromString(str);
+        return a >= 0 && a < P_ ? a : -1;
+    }
+    bool hasDeviceTwin() const override { return true; }
+    int deviceKind() const override { return 4; }
+    void exportDeviceRoot(void* dst) const override // the fields of GoRootSnapshot the Hex device engine reads (go_body.h hexLeafBody)
+    {
+        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
+        for (int w = 0; w < kGoMaxW; ++w) {
+            s.stones[0][w] = w < kW ? s_[0][w] : 0;
+            s.stones[1][w] = w < kW ? s_[1][w] : 0;
+        }
+        s.hash = 0;
+        s.hist_len = swap_ ? kHexSwap : 0;
+        s.turn = turn_;
+        s.nmoves = nact_;
+        s.passes = winner_;
+    }
+    int numInputChannels() const override { return 4; }
+    int boardSize() const override { return n_; }
+    int policySize() const override { return P_; }
+    std::string name() const override { return "hex_" + std::to_string(n_) + "x" + std::to_string(n_); } // ref hex.h:56
+    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", std::to_string(n_)}}; }
+
+private:
+    int n_, P_;
+    bool swap_;
+    int winner_, nact_, first_; // actions played (a swap is one), the first action (what a swap must repeat)
     uint64_t s_[2][kW];
 };
 
@@ -993,7 +1148,8 @@ private:
 };
 
 std::unique_ptr<GameEnv> createGameEnv(const std::string& game, int board_size, float go_komi, const std::string& atari_name, int atari_episode_length,
-                                       const std::string& go_ko_rule, size_t atari_recent_observations, const std::string& gomoku_rule, bool gomoku_exactly_five)
+                                       const std::string& go_ko_rule, size_t atari_recent_observations, const std::string& gomoku_rule, bool gomoku_exactly_five,
+                                       bool hex_use_swap_rule)
 {
     if (game == "atari") { return std::make_unique<AtariSynth>(atari_name, atari_episode_length, std::max<size_t>(1, atari_recent_observations)); }
     if (game == "tictactoe") { return std::make_unique<TicTacToe>(); }
@@ -1013,7 +1169,12 @@ std::unique_ptr<GameEnv> createGameEnv(const std::string& game, int board_size, 
         if (n > kMaxN) { setError("gomoku board size %d not supported (up to 19)", n); return nullptr; }
         return std::make_unique<Gomoku>(n, gomoku_rule == "outer_open", gomoku_exactly_five);
     }
-    setError("unknown env_game '%s' (tictactoe | go | othello | gomoku | atari)", game.c_str());
+    if (game == "hex") { // ref hex.h:12,63
+        const int n = board_size > 0 ? board_size : 11;
+        if (n < 2 || n > kMaxN) { setError("hex board size %d not supported (2..19)", n); return nullptr; }
+        return std::make_unique<Hex>(n, hex_use_swap_rule);
+    }
+    setError("unknown env_game '%s' (tictactoe | go | othello | gomoku | hex | atari)", game.c_str());
     return nullptr;
 }
 

@@ -1,7 +1,7 @@
 // Host rules engines of libmzgpu (AlphaZero leaves need game rules: ref zero_actor.cpp:55,79 replays the
 // path on a copy of the root environment).  Own implementations, designed for cheap copy + replay:
 // flat PODs, bitboards, early-exit flood fills, precomputed rotation tables.  Behavioural contract:
-// ref environment/{tictactoe,othello,go,gomoku}/*.cpp and SURVEY.md Appendix F; checked against the oracle's
+// ref environment/{tictactoe,othello,go,gomoku,hex}/*.cpp and SURVEY.md Appendix F; checked against the oracle's
 // restatement by the differential playout tests.
 #pragma once
 #include <cstdint>
@@ -17,6 +17,7 @@ struct RotationTables {
     std::vector<int> fwd[8]; // fwd[r][a]  = getRotateAction(a, r)            (ref zero_actor.cpp:221, rotation.h:51-93)
     std::vector<int> inv[8]; // inv[r][p]  = rotate(p, reversed_rotation[r])  (ref go.cpp:289, tictactoe.cpp:77, othello.cpp:242)
     void build(int board_size, int num_actions);
+    void buildIdentity(int board_size, int num_actions); // Hex: no symmetries
 };
 
 class GameEnv {
@@ -64,7 +65,7 @@ public:
     virtual int rawFrameBytes() const { return 0; }
     virtual void rawNewest(uint8_t* /*frame*/, uint8_t* /*meta*/) const {}
     virtual bool hasDeviceTwin() const { return false; }
-    virtual int deviceKind() const { return 0; } // GoDevView::kind (0 Go, 1 Othello, 2 TicTacToe, 3 Gomoku)
+    virtual int deviceKind() const { return 0; } // GoDevView::kind (0 Go, 1 Othello, 2 TicTacToe, 3 Gomoku, 4 Hex)
     virtual void exportDeviceRoot(void* /*GoRootSnapshot*/) const {}
     virtual const uint64_t* zobristKeys() const { return nullptr; } // [2][points]
     virtual uint64_t turnKey() const { return 0; }                  // Go, situational superko: XORed into the hash on every move
@@ -85,15 +86,16 @@ protected:
     const RotationTables* rot_ = nullptr;
 };
 
-// game: "tictactoe" | "go" | "othello" | "gomoku"; board_size 0 = the game's default (3 / 9 / 8 / 15)
+// game: "tictactoe" | "go" | "othello" | "gomoku" | "hex"; board_size 0 = the game's default (3 / 9 / 8 / 15 / 11)
 // game "atari": the synthetic Atari-shaped environment (18 actions, 32 x 96 x 96 features, 1 player)
 // atari_recent_observations: observation strings kept for the OBS tag (ref atari.cpp:87: intermediate sequence length + 8 + n-step +
 // unrolling + 1, or everything when sequences are off)
 // gomoku_rule / gomoku_exactly_five: env_gomoku_rule ("outer_open" restricts the first move; any other value is the standard rule, as in
 // ref gomoku.cpp:52) and env_gomoku_exactly_five_stones (an overline does not win)
+// hex_use_swap_rule: env_hex_use_swap_rule (ref hex.cpp:28-47,86-99)
 std::unique_ptr<GameEnv> createGameEnv(const std::string& game, int board_size, float go_komi, const std::string& atari_name = "ms_pacman",
                                        int atari_episode_length = 1000, const std::string& go_ko_rule = "positional",
                                        size_t atari_recent_observations = 108001, const std::string& gomoku_rule = "standard",
-                                       bool gomoku_exactly_five = true);
+                                       bool gomoku_exactly_five = true, bool hex_use_swap_rule = true);
 
 } // namespace mz

@@ -786,6 +786,152 @@ __device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& 
     }
 }
 
+// ---- Hex (ref environment/hex/hex.cpp:22-141,307-362): the slot layout of Gomoku — two bitboards of up to kGoMaxW words, `meta` (actions played, the winner).
+// Black (1) connects column 0 with column n - 1, White (2) row 0 with row n - 1; a point's neighbours are at -n-1, -n, -1, +1, +n, +n+1 (hex.cpp:319-336).  The
+// position is wave-uniform, so the win test is a wave-uniform flood: the set reached from the new stone is dilated by the six shifts (multi-word shifts with
+// column masks, every word index static), masked with the mover's stones, until a round adds nothing; then it is tested against the mover's two edge masks.
+// NW = the words the board needs (2 up to 11x11, else kGoMaxW), so that the default board does not shift four empty words.
+__device__ __forceinline__ unsigned long long hexUniform(unsigned long long x) // a value every lane holds, moved to scalar registers
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
+    return (static_cast<unsigned long long>(hi) << 32) | lo;
+}
+
+// bit p of a board: the word is gathered with masked ORs (not gmkWord's select chain, which the compiler turns into an indexed load from a scratch copy)
+__device__ __forceinline__ bool hexStone(const unsigned long long (&b)[kGoMaxW], int p)
+{
+    unsigned long long x = 0;
+#pragma unroll
+    for (int i = 0; i < kGoMaxW; ++i) { x |= i == (p >> 6) ? b[i] : 0ull; }
+    return (x >> (p & 63)) & 1;
+}
+
+template <int NW>
+__device__ __forceinline__ bool hexConnects(const unsigned long long (&stones)[kGoMaxW], int p_in, int colour, int n, int P, int lane)
+{
+    const int p = __builtin_amdgcn_readfirstlane(p_in);
+    unsigned long long mine[NW], ncl[NW], ncr[NW], e0[NW], e1[NW]; // the mover's stones; not column 0; not column n - 1; the mover's two edges
+    bool on0 = false, on1 = false;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int q = 64 * i + lane, x = q % n;
+        const bool in = q < P;
+        mine[i] = hexUniform(stones[i]);
+        ncl[i] = __ballot(in && x != 0);
+        ncr[i] = __ballot(in && x != n - 1);
+        e0[i] = __ballot(in && (colour == 1 ? x == 0 : q < n));          // hex.cpp:51-61
+        e1[i] = __ballot(in && (colour == 1 ? x == n - 1 : q >= P - n));
+        on0 |= (mine[i] & e0[i]) != 0;
+        on1 |= (mine[i] & e1[i]) != 0;
+    }
+    if (!on0 || !on1) { return false; } // no stone of the mover on one of the edges: nothing to flood
+    unsigned long long r[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { r[i] = i == (p >> 6) ? 1ull << (p & 63) : 0ull; }
+    const int s1 = n, s2 = n + 1; // (both below 64: n <= 19)
+    for (int round = 0; round < P; ++round) {
+        unsigned long long grow[NW], any = 0;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const unsigned long long below = i > 0 ? r[i - 1] : 0ull, above = i + 1 < NW ? r[i + 1] : 0ull;
+            const unsigned long long up1 = (r[i] << 1) | (below >> 63), dn1 = (r[i] >> 1) | (above << 63);
+            const unsigned long long upn = (r[i] << s1) | (below >> (64 - s1)), dnn = (r[i] >> s1) | (above << (64 - s1));
+            const unsigned long long upd = (r[i] << s2) | (below >> (64 - s2)), dnd = (r[i] >> s2) | (above << (64 - s2));
+            grow[i] = (((up1 | upd) & ncl[i]) | ((dn1 | dnd) & ncr[i]) | upn | dnn) & mine[i] & ~r[i];
+            any |= grow[i];
+        }
+        if (any == 0) { break; }
+#pragma unroll
+        for (int i = 0; i < NW; ++i) { r[i] |= grow[i]; }
+    }
+    bool at0 = false, at1 = false;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { at0 |= (r[i] & e0[i]) != 0; at1 |= (r[i] & e1[i]) != 0; }
+    return at0 && at1;
+}
+
+__device__ __forceinline__ void hexLeafBody(const GoDevView& v, const PoolView& pv, int /*rot: Hex has no symmetries, hex.cpp:128*/, int slot, int g, int lane)
+{
+    const int P = v.P, n = v.n, W = v.W, MD = pv.max_depth;
+    const int len = pv.path_len[g];
+    const int* path = pv.path + size_t(g) * MD;
+    const int* pact = pv.path_action + size_t(g) * MD;
+    const int depth = len - 1;
+    const GoRootSnapshot& S = v.snap[g];
+    const int root_turn = S.turn, rule = S.hist_len;
+    const size_t sb = size_t(g) * v.slots;
+    const int* hs = pv.hslot + size_t(g) * pv.cap;
+    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    unsigned long long blk[kGoMaxW], wht[kGoMaxW];
+#pragma unroll
+    for (int i = 0; i < kGoMaxW; ++i) {
+        blk[i] = i < W ? v.stones[((sb + src) * 2 + 0) * W + i] : 0ull;
+        wht[i] = i < W ? v.stones[((sb + src) * 2 + 1) * W + i] : 0ull;
+    }
+    int nact = v.meta[(sb + src) * 2], winner = v.meta[(sb + src) * 2 + 1];
+    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
+    if (depth >= 1) {
+        const int a = pact[len - 1], m = 3 - t; // moved by the other player
+        // the swap (hex.cpp:28-47), recognised from the position alone: rule on, one action played, the chosen cell occupied — the stone there goes, the mover's
+        // lands on its reflection (row, col) -> (n - 1 - col, n - 1 - row)
+        const bool swap = (rule & kHexSwap) && nact == 1 && (hexStone(blk, a) || hexStone(wht, a));
+        const int p = swap ? (n - 1 - a % n) * n + (n - 1 - a / n) : a;
+        ++nact;
+        unsigned long long mine[kGoMaxW];
+#pragma unroll
+        for (int i = 0; i < kGoMaxW; ++i) {
+            const unsigned long long gone = (swap && i == (a >> 6)) ? 1ull << (a & 63) : 0ull;
+            const unsigned long long bit = i == (p >> 6) ? 1ull << (p & 63) : 0ull;
+            blk[i] &= ~gone;
+            wht[i] &= ~gone;
+            if (m == 1) { blk[i] |= bit; } else { wht[i] |= bit; }
+            mine[i] = m == 1 ? blk[i] : wht[i];
+        }
+        if (winner == 0) { // a winner never goes away (and the flood is skipped)
+            const bool won = W <= 2 ? hexConnects<2>(mine, p, m, n, P, lane) : hexConnects<kGoMaxW>(mine, p, m, n, P, lane);
+            if (won) { winner = m; }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < kGoMaxW; ++i) {
+                if (i < W) {
+                    v.stones[((sb + slot) * 2 + 0) * W + i] = blk[i];
+                    v.stones[((sb + slot) * 2 + 1) * W + i] = wht[i];
+                }
+            }
+            v.meta[(sb + slot) * 2] = nact;
+            v.meta[(sb + slot) * 2 + 1] = winner;
+        }
+    }
+    const bool terminal = winner != 0; // ref hex.cpp:101-104: there is no draw
+    const bool any_cell = (rule & kHexSwap) && nact == 1; // hex.cpp:97: every cell is legal on the second action
+    uint32_t* out = v.feat + size_t(g) * 4 * v.W32;
+#pragma unroll
+    for (int i = 0; i < kGoMaxW; ++i) {
+        if (i >= W) { continue; }
+        const int p = 64 * i + lane;
+        const bool b = (blk[i] >> lane) & 1, w = (wht[i] >> lane) & 1;
+        const unsigned long long lw = __ballot(p < P && (any_cell || !(b || w)));
+        if (lane == 0) { v.legal[size_t(g) * v.LW + i] = lw; }
+        // planes (ref hex.cpp:118-141): own, opponent, black to move, white to move
+        const unsigned long long own = __ballot(p < P && (t == 1 ? b : w)), opp = __ballot(p < P && (t == 1 ? w : b)), ones = __ballot(p < P);
+        unsigned long long word = 0;
+        if (lane == 0) { word = own; }
+        if (lane == 1) { word = opp; }
+        if (lane == 2) { word = t == 1 ? ones : 0; }
+        if (lane == 3) { word = t == 2 ? ones : 0; }
+        if (lane < 4) {
+            if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(word); }
+            if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(word >> 32); }
+        }
+    }
+    if (lane == 0) {
+        v.leaf_player[g] = t;
+        v.terminal[g] = terminal ? 1 : 0;
+        v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); // ref hex.cpp:106-116
+    }
+}
+
 // order `k` candidates in cs[] like the reference's std::sort(policy descending): result in out[]
 __device__ void orderCandidates(Cand* cs, Cand* out, int* stack, int k, int lane, int* err)
 {

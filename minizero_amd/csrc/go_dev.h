@@ -32,11 +32,14 @@ struct GoRootSnapshot {
 // env_gomoku_rule=outer_open, env_gomoku_exactly_five_stones
 constexpr int kGmkOuterOpen = 1, kGmkExactlyFive = 2;
 
+// Hex (kind 4) in a GoRootSnapshot: as Gomoku; nmoves = the actions played (a swap is one); hist_len = the rule bit env_hex_use_swap_rule
+constexpr int kHexSwap = 1;
+
 struct RotPack { uint32_t w[kRotPackGames / 10]; }; // per-game feature rotation of one cycle, passed as a kernel argument
 inline void rotPackSet(RotPack& r, int g, int rot) { r.w[g / 10] = (r.w[g / 10] & ~(7u << (3 * (g % 10)))) | (uint32_t(rot) << (3 * (g % 10))); }
 
 struct GoDevView {
-    int kind;                  // 0: Go, 1: Othello (two bitboards + pass count per slot, no hash / group ids; same outputs), 2: TicTacToe
+    int kind;                  // 0: Go, 1: Othello (two bitboards + pass count per slot, no hash / group ids; same outputs), 2: TicTacToe, 3: Gomoku, 4: Hex
     int channels;              // feature planes of the game (Go 18, Othello 4)
     int games, n, P, W, A, slots, Ppad, W32, LW;
     float komi;
@@ -59,7 +62,7 @@ struct GoDevView {
 class GoDevice {
 public:
     // kind 0: Go (keys = Zobrist table [2][P]); kind 1: Othello (board_n <= 8, keys unused); kind 2: TicTacToe (3x3, 9 actions);
-    // kind 3: Gomoku (board_n <= 19, P actions, keys unused)
+    // kind 3: Gomoku, kind 4: Hex (board_n <= 19, P actions, keys unused)
     int init(int device, int games, int board_n, float komi, int action_size, int slots, int max_depth, hipStream_t stream, const int* const inv[8],
              const int* const fwd[8], const uint64_t* keys, int kind = 0, uint64_t turn_key = 0);
     GoRootSnapshot* hostSnap(int g) { return h_snap_.p + g; }

@@ -47,6 +47,11 @@ __global__ __launch_bounds__(64) void gmk_leaf_kernel(GoDevView v, PoolView pv, 
     gmkLeafBody(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x);
 }
 
+__global__ __launch_bounds__(64) void hex_leaf_kernel(GoDevView v, PoolView pv, RotPack rp, int slot)
+{
+    hexLeafBody(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x);
+}
+
 __global__ __launch_bounds__(64) void az_cand_kernel(GoDevView v, const float* __restrict__ policy, const float* __restrict__ logit,
                                                      const float* __restrict__ value, RotPack rp, int* __restrict__ cand_count,
                                                      int* __restrict__ cand_action, float* __restrict__ cand_policy, float* __restrict__ cand_logit,
@@ -79,9 +84,9 @@ int GoDevice::init(int device, int games, int board_n, float komi, int action_si
 {
     if (kind == 1 && board_n > 8) { setError("GoDevice: Othello boards up to 8x8"); return MZ_ERR_ARG; }
     if (kind == 2 && (board_n != 3 || action_size != 9)) { setError("GoDevice: TicTacToe is 3x3 with 9 actions"); return MZ_ERR_ARG; }
-    if (kind < 0 || kind > 3) { setError("GoDevice: unknown kind %d", kind); return MZ_ERR_ARG; }
-    // (TicTacToe and Gomoku have no pass action)
-    if (board_n < 2 || board_n > kGoMaxN || games < 1 || games > kRotPackGames || action_size != board_n * board_n + ((kind == 2 || kind == 3) ? 0 : 1)) {
+    if (kind < 0 || kind > 4) { setError("GoDevice: unknown kind %d", kind); return MZ_ERR_ARG; }
+    // (TicTacToe, Gomoku and Hex have no pass action)
+    if (board_n < 2 || board_n > kGoMaxN || games < 1 || games > kRotPackGames || action_size != board_n * board_n + ((kind == 2 || kind == 3 || kind == 4) ? 0 : 1)) {
         setError("GoDevice: unsupported shape (board %d, %d games, %d actions)", board_n, games, action_size);
         return MZ_ERR_ARG;
     }
@@ -139,6 +144,11 @@ int GoDevice::leafAsync(const PoolView& pv, const RotPack& rot, int slot)
     }
     if (v_.kind == 3) {
         hipLaunchKernelGGL(gmk_leaf_kernel, dim3(v_.games), dim3(64), 0, stream_, v_, pv, rot, slot);
+        MZ_HIP(hipGetLastError());
+        return MZ_OK;
+    }
+    if (v_.kind == 4) {
+        hipLaunchKernelGGL(hex_leaf_kernel, dim3(v_.games), dim3(64), 0, stream_, v_, pv, rot, slot);
         MZ_HIP(hipGetLastError());
         return MZ_OK;
     }

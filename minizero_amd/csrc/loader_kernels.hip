@@ -165,6 +165,7 @@ __global__ __launch_bounds__(64) void replay_kernel(GoDevView v, PoolView pv, co
         if constexpr (KIND == 2) { tttLeafBody(v, pv, r, d, g, lane); }
         else if constexpr (KIND == 1) { othLeafBody(v, pv, r, d, g, lane); }
         else if constexpr (KIND == 3) { gmkLeafBody(v, pv, r, d, g, lane); }
+        else if constexpr (KIND == 4) { hexLeafBody(v, pv, r, d, g, lane); }
         else { goLeafBody<CPL>(v, pv, r, d, g, lane, smem); }
         waveSync();
     }
@@ -206,6 +207,7 @@ int loaderReplayFeatures(GoDevice& gd, const PoolView& pv, int B, const int* d_p
     if (v.kind == 2) { hipLaunchKernelGGL((replay_kernel<2, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
     else if (v.kind == 1) { hipLaunchKernelGGL((replay_kernel<1, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
     else if (v.kind == 3) { hipLaunchKernelGGL((replay_kernel<3, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
+    else if (v.kind == 4) { hipLaunchKernelGGL((replay_kernel<4, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
     else {
         const size_t smem = goLeafSmemBytes(v, pv.max_depth);
 #define MZ_REPLAY_CASE(K) \

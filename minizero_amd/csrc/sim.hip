@@ -657,7 +657,7 @@ bool Net::hasSimKernel(int board_n, int env_kind, int num_simulation) const
         if (sizeof(uint64_t) * (64 * Wq + size_t(num_simulation) + 3 + 4 + 18 * Wq) + 64 * Wq * 7 > tile_bytes) { return false; }
     }
 #define MZ_SIM_HAS(h, w, cin0, cpad, cpl) \
-    if (H == h && W == w && c0 == cin0 && C == cpad && board_n == h && (env_kind == 3 ? -2 : env_kind == 2 ? -1 : env_kind == 1 ? 0 : (h * w + 63) / 64) == cpl) { return true; }
+    if (H == h && W == w && c0 == cin0 && C == cpad && board_n == h && (env_kind == 4 ? -3 : env_kind == 3 ? -2 : env_kind == 2 ? -1 : env_kind == 1 ? 0 : (h * w + 63) / 64) == cpl) { return true; }
     MZ_SIM_CASES(MZ_SIM_HAS)
 #undef MZ_SIM_HAS
     return false;
@@ -763,7 +763,7 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
         return MZ_OK;
     }
 #define MZ_SIM_LAUNCH(h, w, cin0, cpad, cpl) \
-    if (H == h && W == w && c0 == cin0 && C == cpad && gv.n == h && (gv.kind == 3 ? -2 : gv.kind == 2 ? -1 : gv.kind == 1 ? 0 : gv.W) == cpl) { *launched = true; return launchSimT<h, w, cin0, cpad, cpl>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, start_bits, lds, stream_); }
+    if (H == h && W == w && c0 == cin0 && C == cpad && gv.n == h && (gv.kind == 4 ? -3 : gv.kind == 3 ? -2 : gv.kind == 2 ? -1 : gv.kind == 1 ? 0 : gv.W) == cpl) { *launched = true; return launchSimT<h, w, cin0, cpad, cpl>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, start_bits, lds, stream_); }
     MZ_SIM_CASES(MZ_SIM_LAUNCH)
 #undef MZ_SIM_LAUNCH
     return MZ_OK;

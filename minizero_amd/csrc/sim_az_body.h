@@ -143,6 +143,7 @@ __device__ __noinline__ void simSelectLeaf(CSimArgs* __restrict__ a, int rot, in
     const GoDevView gv = simLeafView(ldc(&a->gv), xchg, g);
     if constexpr (CPL == -1) { tttLeafBody(gv, pv, rot, slot, g, lane); } // CPL -1: TicTacToe, 0: Othello, -2: Gomoku (go_body.h)
     else if constexpr (CPL == -2) { gmkLeafBody(gv, pv, rot, slot, g, lane); }
+    else if constexpr (CPL == -3) { hexLeafBody(gv, pv, rot, slot, g, lane); } // -3: Hex
     else if constexpr (CPL == 0) { othLeafBody(gv, pv, rot, slot, g, lane); }
     else if (leaf_smem) { goLeafBody<CPL, true, 1>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds); } // what the network needs; the rest beside the heads (simLeafRest)
     else { goLeafBody<CPL, true>(gv, pv, rot, slot, g, lane, reinterpret_cast<uint64_t*>(tiles), seen_lds); } // planes: simLeafPlanes, all waves

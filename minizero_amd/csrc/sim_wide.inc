@@ -163,6 +163,9 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
 #elif MZ_SIM_WIDE_PART == 4 // Gomoku (words per plane -2: sim_az_body.h simSelectLeaf) on its default 15x15 board: 64 channels (measured), 32 (tests)
 #define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 16, 64, -2) X(15, 15, 16, 32, -2)
 #define MZ_SIM_WIDE_PART_FN simWideLaunchPart4
+#elif MZ_SIM_WIDE_PART == 5 // Hex (words per plane -3: sim_az_body.h simSelectLeaf) on its default 11x11 board: 64 channels (measured), 32 (tests), 128
+#define MZ_SIM_WIDE_PART_CASES(X) X(11, 11, 16, 64, -3) X(11, 11, 16, 32, -3) X(11, 11, 16, 128, -3)
+#define MZ_SIM_WIDE_PART_FN simWideLaunchPart5
 #else // (built with MZ_SPEC_WAYS = 4: the shapes whose tile leaves too little LDS for sixteen remembered paths)
 #define MZ_SIM_WIDE_PART_CASES(X) X(19, 19, 32, 64, 6) X(19, 19, 32, 32, 6) X(13, 13, 32, 128, 3) X(9, 9, 32, 256, 2)
 #define MZ_SIM_WIDE_PART_FN simWideLaunchPart2

@@ -14,7 +14,10 @@ bool simWideLaunchPart3(int H, int W, int c0q, int C, int cpl, const SimArgs* d_
 bool simWideLaunchPart4(int H, int W, int c0q, int C, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds,
                         hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words);
 
-static int simWideCpl(int env_kind, int board_n) { return env_kind == 3 ? -2 : env_kind == 2 ? -1 : env_kind == 1 ? 0 : (board_n * board_n + 63) / 64; }
+bool simWideLaunchPart5(int H, int W, int c0q, int C, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds,
+                        hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words);
+
+static int simWideCpl(int env_kind, int board_n) { return env_kind == 4 ? -3 : env_kind == 3 ? -2 : env_kind == 2 ? -1 : env_kind == 1 ? 0 : (board_n * board_n + 63) / 64; }
 
 static bool simWideAny(int H, int W, int c0q, int C, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds,
                        hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words = nullptr)
@@ -23,12 +26,13 @@ static bool simWideAny(int H, int W, int c0q, int C, int cpl, const SimArgs* d_a
            simWideLaunchPart1(H, W, c0q, C, cpl, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words) ||
            simWideLaunchPart2(H, W, c0q, C, cpl, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words) ||
            simWideLaunchPart3(H, W, c0q, C, cpl, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words) ||
-           simWideLaunchPart4(H, W, c0q, C, cpl, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words);
+           simWideLaunchPart4(H, W, c0q, C, cpl, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words) ||
+           simWideLaunchPart5(H, W, c0q, C, cpl, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words);
 }
 
 // The LDS plan of sim_kernel_wide for a search of n simulations on a board of board_n x board_n points: false = no instance, or the mandatory blocks do not fit.
 // *lf = the optional blocks that fit, in the order of what they buy (superko table, the leaf's block beside the heads, path speculation); *lds = the bytes to ask for
-// env_kind: 0 Go, 1 Othello, 2 TicTacToe, 3 Gomoku (the leaf bodies of go_body.h; the kernels' words-per-plane argument is 0 / -1 / -2 for the latter three)
+// env_kind: 0 Go, 1 Othello, 2 TicTacToe, 3 Gomoku, 4 Hex (the leaf bodies of go_body.h; the kernels' words-per-plane argument is 0 / -1 / -2 / -3 for the latter four)
 bool Net::simWidePlan(int board_n, int env_kind, int num_simulation, const HeadParams& hp, int channels, int W32, size_t leaf_bytes, size_t scratch_bytes, int* lf, size_t* lds,
                       size_t* tile_bytes_out) const
 {

@@ -625,7 +625,7 @@ int Worker::createActors()
                                                           ? 108000
                                                           : cfg_.zero_actor_intermediate_sequence_length + 8 + cfg_.learner_n_step_return + cfg_.learner_muzero_unrolling_step) + 1;
         g.env = createGameEnv(cfg_.env_game, cfg_.env_board_size, cfg_.env_go_komi, cfg_.env_atari_name, cfg_.env_atari_episode_length, cfg_.env_go_ko_rule,
-                              recent_obs, cfg_.env_gomoku_rule, cfg_.env_gomoku_exactly_five_stones);
+                              recent_obs, cfg_.env_gomoku_rule, cfg_.env_gomoku_exactly_five_stones, cfg_.env_hex_use_swap_rule);
         if (!g.env) { return MZ_ERR_ARG; }
         if (g.env->policySize() != A_ || g.env->featureSize() != net0().featSize()) {
             setError("network (A=%d, features=%d) does not fit env %s (A=%d, features=%d)", A_, net0().featSize(), g.env->name().c_str(),
@@ -1986,6 +1986,8 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         if (games_[0].env->hasObservations()) { MZ_FIXED(zero_actor_intermediate_sequence_length) MZ_FIXED(learner_n_step_return) MZ_FIXED(learner_muzero_unrolling_step) }
         // Gomoku's rules live in its engines (host and device) from creation; for every other game the two keys are inert
         if (games_[0].env->deviceKind() == 3) { MZ_FIXED(env_gomoku_rule) MZ_FIXED(env_gomoku_exactly_five_stones) }
+        // ... and so does Hex's swap rule
+        if (games_[0].env->deviceKind() == 4) { MZ_FIXED(env_hex_use_swap_rule) }
 #undef MZ_FIXED
         if (fixed) { setError("update_config: %s is fixed when the worker is created (restart the worker to change it)", fixed); return MZ_ERR_ARG; }
         cfg_ = nc;
@@ -2162,7 +2164,7 @@ mz_env* mz_env_create(const char* conf)
     if (!conf || !c.loadFromString(conf)) { return nullptr; }
     std::unique_ptr<mz_env> e(new mz_env());
     e->e = mz::createGameEnv(c.env_game, c.env_board_size, c.env_go_komi, c.env_atari_name, c.env_atari_episode_length, c.env_go_ko_rule, 108001,
-                             c.env_gomoku_rule, c.env_gomoku_exactly_five_stones);
+                             c.env_gomoku_rule, c.env_gomoku_exactly_five_stones, c.env_hex_use_swap_rule);
     if (!e->e) { return nullptr; }
     return e.release();
 }
@@ -2239,7 +2241,7 @@ int mz_envdev_playout_conf(int device, const char* conf, const int* actions, int
     if (mz_device_count() < 1) { setError("mz_envdev_playout_conf: no GPU (libmzgpu has no CPU path)"); return MZ_ERR_DEVICE; }
     if (!actions || !rots || count < 0 || root_prefix < 0 || root_prefix > count) { setError("mz_envdev_playout_conf: bad arguments"); return MZ_ERR_ARG; }
     std::unique_ptr<GameEnv> env = createGameEnv(c.env_game, c.env_board_size, c.env_go_komi, c.env_atari_name, c.env_atari_episode_length, c.env_go_ko_rule, 1,
-                                                 c.env_gomoku_rule, c.env_gomoku_exactly_five_stones);
+                                                 c.env_gomoku_rule, c.env_gomoku_exactly_five_stones, c.env_hex_use_swap_rule);
     return envdevPlayout(device, env.get(), c.env_go_komi, actions, count, root_prefix, rots, feat_out, legal_out, terminal_out, eval_out, player_out);
 }
 

@@ -641,7 +641,8 @@ def envdev_playout(game, board_size, komi, actions, root_prefix, rots, channels,
 
 
 def envdev_playout_conf(conf, board_size, actions, root_prefix, rots, channels, num_actions, device=0):
-    """envdev_playout with the game and its rules from a configuration string, as Env takes it (e.g. "env_game=gomoku:env_gomoku_rule=outer_open")."""
+    """envdev_playout with the game and its rules from a configuration string, as Env takes it (e.g. "env_game=gomoku:env_gomoku_rule=outer_open",
+    "env_game=hex:env_hex_use_swap_rule=false")."""
     L = load()
     P = board_size * board_size
     acts = np.ascontiguousarray(actions, np.int32)
