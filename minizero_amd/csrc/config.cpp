@@ -1,5 +1,6 @@
 // Table-driven parser for WorkerConfig (see config.h).
 #include "config.h"
+#include "env.h"
 #include "common.h"
 #include <algorithm>
 #include <cstddef>
@@ -100,6 +101,22 @@ bool WorkerConfig::loadFromString(const std::string& s)
         if (!ok) { setError("Unsatisfiable value \"%s\" for option \"%s\"", value.c_str(), key.c_str()); return false; }
     }
     return true;
+}
+
+EnvOptions envOptions(const WorkerConfig& c, size_t recent_observations)
+{
+    EnvOptions o;
+    o.game = c.env_game;
+    o.board_size = c.env_board_size;
+    o.go_komi = c.env_go_komi;
+    o.go_ko_rule = c.env_go_ko_rule;
+    o.gomoku_rule = c.env_gomoku_rule;
+    o.gomoku_exactly_five = c.env_gomoku_exactly_five_stones;
+    o.hex_use_swap_rule = c.env_hex_use_swap_rule;
+    o.atari_name = c.env_atari_name;
+    o.atari_episode_length = c.env_atari_episode_length;
+    o.atari_recent_observations = recent_observations;
+    return o;
 }
 
 } // namespace mz

@@ -2,6 +2,7 @@
 // (ref config/configuration.cpp:7-90; same key names, defaults and "k=v:k=v" syntax as
 // config/configure_loader.cpp:51-117), held in a struct so several workers can live in one process.
 #pragma once
+#include <cstddef>
 #include <string>
 
 namespace mz {
@@ -92,5 +93,9 @@ struct WorkerConfig {
     // like ConfigureLoader::loadFromString; keys are applied left to right, later ones win
     bool loadFromString(const std::string& s);
 };
+
+// the env_* keys as the options of createGameEnv (env.h); recent_observations: EnvOptions::atari_recent_observations
+struct EnvOptions;
+EnvOptions envOptions(const WorkerConfig& c, size_t recent_observations);
 
 } // namespace mz

@@ -108,27 +108,98 @@ int GameEnv::actionFromString(const std::string& str) const
     return y * n + x;
 }
 
-class TicTacToe final : public GameEnv {
+// What the four games with the planes (own, opponent, black to move, white to move) share: the action history, act() over isLegal() + actUnchecked(), the
+// planes and the legal mask, the head of the device snapshot, the facts of the game's row in game_kind.h.  A game supplies word(colour, w) — word w of its
+// bitboard of that colour — isLegal() and actUnchecked(), which ends with played().  (CRTP: word() is inlined into the plane loops.)
+template <class Game, GameKind K>
+class FourPlaneEnv : public GameEnv {
 public:
-    TicTacToe() { rot_ = rotationTables(3, 9); reset(); }
-    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<TicTacToe>(*this); }
-    void copyFrom(const GameEnv& o) override { *this = static_cast<const TicTacToe&>(o); }
-    void reset() override { turn_ = 1; action_ids_.clear(); action_players_.clear(); m_[0] = m_[1] = 0; }
-    bool isLegal(int a, int) const override { return a >= 0 && a < 9 && !((m_[0] | m_[1]) >> a & 1); }
+    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<Game>(self()); }
+    void copyFrom(const GameEnv& o) override { static_cast<Game&>(*this) = static_cast<const Game&>(o); }
+    bool stone(int c, int p) const { return (self().word(c, p >> 6) >> (p & 63)) & 1; }
     bool act(int a, int player) override
     {
-        if (!isLegal(a, player)) { return false; }
-        actUnchecked(a, player);
+        if (!self().isLegal(a, player)) { return false; }
+        self().actUnchecked(a, player);
         return true;
     }
-    void actUnchecked(int a, int player) override
+    void legalMask(uint8_t* out) const override { for (int a = 0; a < policySize(); ++a) { out[a] = self().isLegal(a, turn_); } }
+    void features(int r, float* out) const override
     {
-        m_[player - 1] |= 1u << a;
+        const int* map = rot_->inv[r].data();
+        for (int p = 0; p < P_; ++p) {
+            out[p] = stone(turn_ - 1, map[p]) ? 1.0f : 0.0f;
+            out[P_ + p] = stone(2 - turn_, map[p]) ? 1.0f : 0.0f;
+            out[2 * P_ + p] = turn_ == 1 ? 1.0f : 0.0f;
+            out[3 * P_ + p] = turn_ == 2 ? 1.0f : 0.0f;
+        }
+    }
+    void featureBits(int r, uint32_t* out) const override
+    {
+        const int W32 = (P_ + 31) / 32;
+        const int* map = rot_->inv[r].data();
+        for (int i = 0; i < 4 * W32; ++i) { out[i] = 0; }
+        for (int p = 0; p < P_; ++p) {
+            const uint32_t b = 1u << (p & 31);
+            if (stone(turn_ - 1, map[p])) { out[p >> 5] |= b; }
+            if (stone(2 - turn_, map[p])) { out[W32 + (p >> 5)] |= b; }
+            out[(turn_ == 1 ? 2 : 3) * W32 + (p >> 5)] |= b;
+        }
+    }
+    int actionFromString(const std::string& str) const override
+    {
+        if (gameHasPass(K)) { return GameEnv::actionFromString(str); }
+        std::string up = str;
+        for (char& c : up) { c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
+        return up == "PASS" ? -1 : GameEnv::actionFromString(str); // no pass action
+    }
+    GameKind deviceKind() const override { return n_ >= gameMinBoard(K) && n_ <= gameMaxBoard(K) ? K : kNoDeviceGame; }
+    int numInputChannels() const override { return gameChannels(K); }
+    int boardSize() const override { return n_; }
+    int policySize() const override { return P_ + (gameHasPass(K) ? 1 : 0); }
+    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", std::to_string(n_)}}; }
+
+protected:
+    explicit FourPlaneEnv(int n, bool no_symmetries = false) : n_(n), P_(n * n) { rot_ = rotationTables(n, policySize(), no_symmetries); }
+    const Game& self() const { return static_cast<const Game&>(*this); }
+    Game& self() { return static_cast<Game&>(*this); }
+    void resetHistory() { turn_ = 1; action_ids_.clear(); action_players_.clear(); }
+    void played(int a, int player)
+    {
         action_ids_.push_back(static_cast<int16_t>(a));
         action_players_.push_back(static_cast<uint8_t>(player));
         turn_ = 3 - player;
     }
-    void legalMask(uint8_t* out) const override { for (int a = 0; a < 9; ++a) { out[a] = isLegal(a, turn_); } }
+    // the fields of GoRootSnapshot every one of the four device engines reads (go_body.h): the two bitboards, the player to move, the actions played;
+    // the game fills in what else its engine reads
+    GoRootSnapshot& exportHead(void* dst) const
+    {
+        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
+        for (int w = 0; w < kGoMaxW; ++w) {
+            s.stones[0][w] = self().word(0, w);
+            s.stones[1][w] = self().word(1, w);
+        }
+        s.hash = 0;
+        s.hist_len = 0;
+        s.turn = turn_;
+        s.nmoves = static_cast<int32_t>(action_ids_.size());
+        s.passes = 0;
+        return s;
+    }
+    int n_, P_;
+};
+
+class TicTacToe final : public FourPlaneEnv<TicTacToe, kTicTacToe> {
+public:
+    TicTacToe() : FourPlaneEnv(3) { reset(); }
+    void reset() override { resetHistory(); m_[0] = m_[1] = 0; }
+    uint64_t word(int c, int w) const { return w == 0 ? m_[c] : 0; }
+    bool isLegal(int a, int) const override { return a >= 0 && a < 9 && !((m_[0] | m_[1]) >> a & 1); }
+    void actUnchecked(int a, int player) override
+    {
+        m_[player - 1] |= 1u << a;
+        played(a, player);
+    }
     int winner() const
     {
         static const unsigned lines[8] = {0007, 0070, 0700, 0111, 0222, 0444, 0421, 0124};
@@ -140,35 +211,9 @@ public:
     }
     bool isTerminal() const override { return winner() != 0 || (m_[0] | m_[1]) == 0777; }
     float evalScore(bool is_resign) const override { return scoreOf(is_resign ? 3 - turn_ : winner()); }
-    void features(int r, float* out) const override
-    {
-        const unsigned own = m_[turn_ - 1], opp = m_[2 - turn_];
-        const int* map = rot_->inv[r].data();
-        for (int p = 0; p < 9; ++p) {
-            out[p] = (own >> map[p]) & 1 ? 1.0f : 0.0f;
-            out[9 + p] = (opp >> map[p]) & 1 ? 1.0f : 0.0f;
-            out[18 + p] = turn_ == 1 ? 1.0f : 0.0f;
-            out[27 + p] = turn_ == 2 ? 1.0f : 0.0f;
-        }
-    }
-    bool hasDeviceTwin() const override { return true; }
-    int deviceKind() const override { return 2; }
-    void exportDeviceRoot(void* dst) const override // the fields of GoRootSnapshot the TicTacToe device engine reads (go_body.h tttLeafBody)
-    {
-        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
-        s.stones[0][0] = m_[0];
-        s.stones[1][0] = m_[1];
-        s.hash = 0;
-        s.hist_len = 0;
-        s.turn = turn_;
-        s.nmoves = static_cast<int32_t>(action_ids_.size());
-        s.passes = 0;
-    }
-    int numInputChannels() const override { return 4; }
-    int boardSize() const override { return 3; }
-    int policySize() const override { return 9; }
+    int actionFromString(const std::string& str) const override { return GameEnv::actionFromString(str); } // ("pass" is 9, one past the board, as in ref tictactoe.h)
+    void exportDeviceRoot(void* dst) const override { exportHead(dst); } // (go_body.h tttLeafBody)
     std::string name() const override { return "tictactoe"; }
-    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", "3"}}; }
 
 private:
     unsigned m_[2];
@@ -177,11 +222,10 @@ private:
 // ---------------------------------------------------------------------------------------------
 // Othello, board <= 8x8 (ref othello.cpp:14-262)
 // ---------------------------------------------------------------------------------------------
-class Othello final : public GameEnv {
+class Othello final : public FourPlaneEnv<Othello, kOthello> {
 public:
-    explicit Othello(int n) : n_(n)
+    explicit Othello(int n) : FourPlaneEnv(n)
     {
-        rot_ = rotationTables(n, n * n + 1);
         full_ = 0; not_left_ = 0; not_right_ = 0;
         for (int y = 0; y < n; ++y)
             for (int x = 0; x < n; ++x) {
@@ -192,13 +236,10 @@ public:
             }
         reset();
     }
-    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<Othello>(*this); }
-    void copyFrom(const GameEnv& o) override { *this = static_cast<const Othello&>(o); }
+    uint64_t word(int c, int w) const { return w == 0 ? s_[c] : 0; }
     void reset() override // ref othello.cpp:14-27 (black on init, init+n+1; white on init+1, init+n)
     {
-        turn_ = 1;
-        action_ids_.clear();
-        action_players_.clear();
+        resetHistory();
         const int init = n_ * (n_ / 2 - (1 - n_ % 2)) + (n_ / 2 - 1);
         s_[0] = (1ull << init) | (1ull << (init + n_ + 1));
         s_[1] = (1ull << (init + 1)) | (1ull << (init + n_));
@@ -234,17 +275,9 @@ public:
         if (a == n_ * n_) { return m == 0; } // pass only when the mover has no move (ref othello.cpp:195-201)
         return a >= 0 && a < n_ * n_ && ((m >> a) & 1);
     }
-    bool act(int a, int player) override
-    {
-        if (!isLegal(a, player)) { return false; }
-        actUnchecked(a, player);
-        return true;
-    }
     void actUnchecked(int a, int player) override
     {
-        action_ids_.push_back(static_cast<int16_t>(a));
-        action_players_.push_back(static_cast<uint8_t>(player));
-        turn_ = 3 - player;
+        played(a, player);
         if (a == n_ * n_) { return; }
         uint64_t& me = s_[player - 1];
         uint64_t& op = s_[2 - player];
@@ -258,7 +291,7 @@ public:
         me |= placed | flip;
         op &= ~flip;
     }
-    void legalMask(uint8_t* out) const override
+    void legalMask(uint8_t* out) const override // (one move generation for all actions, not one per isLegal())
     {
         const uint64_t m = moves(turn_);
         for (int a = 0; a < n_ * n_; ++a) { out[a] = (m >> a) & 1; }
@@ -276,41 +309,16 @@ public:
         const int b = __builtin_popcountll(s_[0]), w = __builtin_popcountll(s_[1]);
         return scoreOf(b > w ? 1 : (b < w ? 2 : 0));
     }
-    void features(int r, float* out) const override
+    void exportDeviceRoot(void* dst) const override // (go_body.h othLeafBody)
     {
-        const int P = n_ * n_;
-        const uint64_t own = s_[turn_ - 1], opp = s_[2 - turn_];
-        const int* map = rot_->inv[r].data();
-        for (int p = 0; p < P; ++p) {
-            out[p] = (own >> map[p]) & 1 ? 1.0f : 0.0f;
-            out[P + p] = (opp >> map[p]) & 1 ? 1.0f : 0.0f;
-            out[2 * P + p] = turn_ == 1 ? 1.0f : 0.0f;
-            out[3 * P + p] = turn_ == 2 ? 1.0f : 0.0f;
-        }
-    }
-    bool hasDeviceTwin() const override { return n_ <= 8; }
-    int deviceKind() const override { return 1; }
-    void exportDeviceRoot(void* dst) const override // the fields of GoRootSnapshot the Othello device engine reads (go_body.h othLeafBody)
-    {
-        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
-        s.stones[0][0] = s_[0];
-        s.stones[1][0] = s_[1];
-        s.hash = 0;
-        s.hist_len = 0;
-        s.turn = turn_;
-        s.nmoves = static_cast<int32_t>(action_ids_.size());
+        GoRootSnapshot& s = exportHead(dst);
         int passes = 0;
         for (size_t k = action_ids_.size(); k > 0 && passes < 2 && action_ids_[k - 1] == n_ * n_; --k) { ++passes; }
         s.passes = passes;
     }
-    int numInputChannels() const override { return 4; }
-    int boardSize() const override { return n_; }
-    int policySize() const override { return n_ * n_ + 1; }
     std::string name() const override { return "othello_" + std::to_string(n_) + "x" + std::to_string(n_); }
-    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", std::to_string(n_)}}; }
 
 private:
-    int n_;
     uint64_t full_, not_left_, not_right_, s_[2];
 };
 
@@ -319,25 +327,17 @@ private:
 // along each of the four lines through its stone (gomoku.cpp:140-162); a win on the move that fills the board is a win.  Outer-open
 // restricts the game's first move (no move played yet) to the outer two rings.  No pass action: policySize() == P.
 // ---------------------------------------------------------------------------------------------
-class Gomoku final : public GameEnv {
+class Gomoku final : public FourPlaneEnv<Gomoku, kGomoku> {
     static constexpr int kW = (19 * 19 + 63) / 64;
 public:
-    Gomoku(int n, bool outer_open, bool exactly_five) : n_(n), P_(n * n), outer_open_(outer_open), exactly_five_(exactly_five)
-    {
-        rot_ = rotationTables(n, n * n);
-        reset();
-    }
-    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<Gomoku>(*this); }
-    void copyFrom(const GameEnv& o) override { *this = static_cast<const Gomoku&>(o); }
+    Gomoku(int n, bool outer_open, bool exactly_five) : FourPlaneEnv(n), outer_open_(outer_open), exactly_five_(exactly_five) { reset(); }
     void reset() override
     {
-        turn_ = 1;
-        action_ids_.clear();
-        action_players_.clear();
+        resetHistory();
         memset(s_, 0, sizeof(s_));
         winner_ = 0;
     }
-    bool stone(int c, int p) const { return (s_[c][p >> 6] >> (p & 63)) & 1; }
+    uint64_t word(int c, int w) const { return w < kW ? s_[c][w] : 0; }
     bool isLegal(int a, int) const override // ref gomoku.cpp:48-58: the first move under outer-open is any point of the outer two rings
     {
         if (a < 0 || a >= P_) { return false; }
@@ -347,18 +347,10 @@ public:
         }
         return !stone(0, a) && !stone(1, a);
     }
-    bool act(int a, int player) override
-    {
-        if (!isLegal(a, player)) { return false; }
-        actUnchecked(a, player);
-        return true;
-    }
     void actUnchecked(int a, int player) override
     {
         s_[player - 1][a >> 6] |= 1ull << (a & 63);
-        action_ids_.push_back(static_cast<int16_t>(a));
-        action_players_.push_back(static_cast<uint8_t>(player));
-        turn_ = 3 - player;
+        played(a, player);
         winner_ = wins(a, player - 1) ? player : 0; // ref gomoku.cpp:29: replaced on every move
     }
     // the stones of colour c on the line through p in direction (dx, dy), p included (ref gomoku.cpp:140-162)
@@ -386,60 +378,17 @@ public:
         for (int w = 0; w < kW; ++w) { k += __builtin_popcountll(s_[0][w] | s_[1][w]); }
         return k;
     }
-    void legalMask(uint8_t* out) const override { for (int a = 0; a < P_; ++a) { out[a] = isLegal(a, turn_); } }
     bool isTerminal() const override { return winner_ != 0 || stonesPlayed() == P_; }
     float evalScore(bool is_resign) const override { return scoreOf(is_resign ? 3 - turn_ : winner_); } // ref gomoku.cpp:65-73
-    void features(int r, float* out) const override // ref gomoku.cpp:75-98: own, opponent, black to move, white to move
+    void exportDeviceRoot(void* dst) const override // (go_body.h gmkLeafBody)
     {
-        const int* map = rot_->inv[r].data();
-        for (int p = 0; p < P_; ++p) {
-            out[p] = stone(turn_ - 1, map[p]) ? 1.0f : 0.0f;
-            out[P_ + p] = stone(2 - turn_, map[p]) ? 1.0f : 0.0f;
-            out[2 * P_ + p] = turn_ == 1 ? 1.0f : 0.0f;
-            out[3 * P_ + p] = turn_ == 2 ? 1.0f : 0.0f;
-        }
+        GoRootSnapshot& s = exportHead(dst);
+        s.ruleBits() = (outer_open_ ? kGmkOuterOpen : 0) | (exactly_five_ ? kGmkExactlyFive : 0);
+        s.winner() = winner_;
     }
-    void featureBits(int r, uint32_t* out) const override
-    {
-        const int W32 = (P_ + 31) / 32;
-        const int* map = rot_->inv[r].data();
-        for (int i = 0; i < 4 * W32; ++i) { out[i] = 0; }
-        for (int p = 0; p < P_; ++p) {
-            const uint32_t b = 1u << (p & 31);
-            if (stone(turn_ - 1, map[p])) { out[p >> 5] |= b; }
-            if (stone(2 - turn_, map[p])) { out[W32 + (p >> 5)] |= b; }
-            out[(turn_ == 1 ? 2 : 3) * W32 + (p >> 5)] |= b;
-        }
-    }
-    int actionFromString(const std::string& str) const override
-    {
-        std::string up = str;
-        for (char& c : up) { c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
-        return up == "PASS" ? -1 : GameEnv::actionFromString(str); // no pass action
-    }
-    bool hasDeviceTwin() const override { return n_ >= 2; }
-    int deviceKind() const override { return 3; }
-    void exportDeviceRoot(void* dst) const override // the fields of GoRootSnapshot the Gomoku device engine reads (go_body.h gmkLeafBody)
-    {
-        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
-        for (int w = 0; w < kGoMaxW; ++w) {
-            s.stones[0][w] = w < kW ? s_[0][w] : 0;
-            s.stones[1][w] = w < kW ? s_[1][w] : 0;
-        }
-        s.hash = 0;
-        s.hist_len = (outer_open_ ? kGmkOuterOpen : 0) | (exactly_five_ ? kGmkExactlyFive : 0);
-        s.turn = turn_;
-        s.nmoves = static_cast<int32_t>(action_ids_.size());
-        s.passes = winner_;
-    }
-    int numInputChannels() const override { return 4; }
-    int boardSize() const override { return n_; }
-    int policySize() const override { return P_; }
     std::string name() const override { return "gomoku" + std::string(outer_open_ ? "_oo_" : "_") + std::to_string(n_) + "x" + std::to_string(n_); }
-    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", std::to_string(n_)}}; }
 
 private:
-    int n_, P_;
     bool outer_open_, exactly_five_;
     int winner_;
     uint64_t s_[2][kW];
@@ -453,37 +402,23 @@ private:
 // (env_hex_use_swap_rule, hex.cpp:28-47,86-99) every cell is legal on the second action, and choosing the occupied one replaces Black's stone by a White
 // stone on its reflection; the record keeps the chosen action id.  No pass action, no symmetries: the rotation tables are the identity.
 // ---------------------------------------------------------------------------------------------
-class Hex final : public GameEnv {
+class Hex final : public FourPlaneEnv<Hex, kHex> {
     static constexpr int kW = (19 * 19 + 63) / 64;
 public:
-    Hex(int n, bool swap) : n_(n), P_(n * n), swap_(swap)
-    {
-        rot_ = rotationTables(n, n * n, true);
-        reset();
-    }
-    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<Hex>(*this); }
-    void copyFrom(const GameEnv& o) override { *this = static_cast<const Hex&>(o); }
+    Hex(int n, bool swap) : FourPlaneEnv(n, true), swap_(swap) { reset(); }
     void reset() override
     {
-        turn_ = 1;
-        action_ids_.clear();
-        action_players_.clear();
+        resetHistory();
         memset(s_, 0, sizeof(s_));
         winner_ = 0;
         nact_ = 0;
         first_ = -1;
     }
-    bool stone(int c, int p) const { return (s_[c][p >> 6] >> (p & 63)) & 1; }
+    uint64_t word(int c, int w) const { return w < kW ? s_[c][w] : 0; }
     bool isLegal(int a, int) const override // ref hex.cpp:86-99: an empty cell, or any cell on the second action under the swap rule
     {
         if (a < 0 || a >= P_) { return false; }
         return (swap_ && nact_ == 1) || (!stone(0, a) && !stone(1, a));
-    }
-    bool act(int a, int player) override
-    {
-        if (!isLegal(a, player)) { return false; }
-        actUnchecked(a, player);
-        return true;
     }
     void actUnchecked(int a, int player) override
     {
@@ -496,9 +431,7 @@ public:
         s_[player - 1][p >> 6] |= 1ull << (p & 63);
         if (nact_ == 0) { first_ = a; }
         ++nact_;
-        action_ids_.push_back(static_cast<int16_t>(a)); // the chosen id, also for a swap (B[k];W[k])
-        action_players_.push_back(static_cast<uint8_t>(player));
-        turn_ = 3 - player;
+        played(a, player); // the chosen id, also for a swap (B[k];W[k])
         if (winner_ == 0 && connects(p, player - 1)) { winner_ = player; } // a winner never goes away
     }
     // does the group of colour c through p touch both of c's edges?  (a stack flood over the six neighbours, ended by the second edge)
@@ -528,60 +461,23 @@ public:
         }
         return false;
     }
-    void legalMask(uint8_t* out) const override { for (int a = 0; a < P_; ++a) { out[a] = isLegal(a, turn_); } }
     bool isTerminal() const override { return winner_ != 0; } // ref hex.cpp:101-104
     float evalScore(bool is_resign) const override { return scoreOf(is_resign ? 3 - turn_ : winner_); } // ref hex.cpp:106-116
-    void features(int, float* out) const override // ref hex.cpp:118-141: own, opponent, black to move, white to move; the rotation is ignored
+    // (the planes, ref hex.cpp:118-141, ignore the rotation: the tables are the identity)
+    int actionFromString(const std::string& str) const override // board coordinates ("F6") on the board only
     {
-        for (int p = 0; p < P_; ++p) {
-            out[p] = stone(turn_ - 1, p) ? 1.0f : 0.0f;
-            out[P_ + p] = stone(2 - turn_, p) ? 1.0f : 0.0f;
-            out[2 * P_ + p] = turn_ == 1 ? 1.0f : 0.0f;
-            out[3 * P_ + p] = turn_ == 2 ? 1.0f : 0.0f;
-        }
-    }
-    void featureBits(int, uint32_t* out) const override
-    {
-        const int W32 = (P_ + 31) / 32;
-        for (int i = 0; i < 4 * W32; ++i) { out[i] = 0; }
-        for (int p = 0; p < P_; ++p) {
-            const uint32_t b = 1u << (p & 31);
-            if (stone(turn_ - 1, p)) { out[p >> 5] |= b; }
-            if (stone(2 - turn_, p)) { out[W32 + (p >> 5)] |= b; }
-            out[(turn_ == 1 ? 2 : 3) * W32 + (p >> 5)] |= b;
-        }
-    }
-    int actionFromString(const std::string& str) const override // board coordinates ("F6"); no pass action
-    {
-        std::string up = str;
-        for (char& c : up) { c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
-        if (up == "PASS") { return -1; }
-        const int a = GameEnv::actionFromString(str);
+        const int a = FourPlaneEnv::actionFromString(str);
         return a >= 0 && a < P_ ? a : -1;
     }
-    bool hasDeviceTwin() const override { return true; }
-    int deviceKind() const override { return 4; }
-    void exportDeviceRoot(void* dst) const override // the fields of GoRootSnapshot the Hex device engine reads (go_body.h hexLeafBody)
+    void exportDeviceRoot(void* dst) const override // (go_body.h hexLeafBody); nmoves = the actions played, a swap is one
     {
-        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
-        for (int w = 0; w < kGoMaxW; ++w) {
-            s.stones[0][w] = w < kW ? s_[0][w] : 0;
-            s.stones[1][w] = w < kW ? s_[1][w] : 0;
-        }
-        s.hash = 0;
-        s.hist_len = swap_ ? kHexSwap : 0;
-        s.turn = turn_;
-        s.nmoves = nact_;
-        s.passes = winner_;
+        GoRootSnapshot& s = exportHead(dst);
+        s.ruleBits() = swap_ ? kHexSwap : 0;
+        s.winner() = winner_;
     }
-    int numInputChannels() const override { return 4; }
-    int boardSize() const override { return n_; }
-    int policySize() const override { return P_; }
     std::string name() const override { return "hex_" + std::to_string(n_) + "x" + std::to_string(n_); } // ref hex.h:56
-    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", std::to_string(n_)}}; }
 
 private:
-    int n_, P_;
     bool swap_;
     int winner_, nact_, first_; // actions played (a swap is one), the first action (what a swap must repeat)
     uint64_t s_[2][kW];
@@ -896,7 +792,7 @@ public:
         uint32_t* t = out + (turn_ == 1 ? 16 : 17) * W32;
         for (int p = 0; p < P_; ++p) { t[p >> 5] |= 1u << (p & 31); }
     }
-    bool hasDeviceTwin() const override { return true; }
+    GameKind deviceKind() const override { return kGo; }
     uint64_t turnKey() const override { return turn_key_; }
     const uint64_t* zobristKeys() const override
     {
@@ -1147,35 +1043,47 @@ private:
     float action_plane_[kHist] = {};
 };
 
+std::unique_ptr<GameEnv> createGameEnv(const EnvOptions& o)
+{
+    if (o.game == "atari") { return std::make_unique<AtariSynth>(o.atari_name, o.atari_episode_length, std::max<size_t>(1, o.atari_recent_observations)); }
+    const GameKind k = gameFromName(o.game.c_str());
+    if (k == kNoDeviceGame) { setError("unknown env_game '%s' (tictactoe | go | othello | gomoku | hex | atari)", o.game.c_str()); return nullptr; }
+    const int n = o.board_size > 0 ? o.board_size : gameDefaultBoard(k);
+    switch (k) {
+    case kTicTacToe: return std::make_unique<TicTacToe>();
+    case kOthello:
+        if (n < 4 || n > 8 || n % 2) { setError("othello board size %d not supported (even, 4..8)", n); return nullptr; }
+        return std::make_unique<Othello>(n);
+    case kGo:
+        if (n < 2 || n > kMaxN) { setError("go board size %d not supported (2..19)", n); return nullptr; }
+        if (o.go_ko_rule != "positional" && o.go_ko_rule != "situational") { setError("env_go_ko_rule '%s' not supported (positional | situational, ref go.cpp:47)", o.go_ko_rule.c_str()); return nullptr; }
+        return std::make_unique<Go>(n, o.go_komi, o.go_ko_rule == "situational");
+    case kGomoku: // ref gomoku.h:13,21,44
+        if (n > kMaxN) { setError("gomoku board size %d not supported (up to 19)", n); return nullptr; }
+        return std::make_unique<Gomoku>(n, o.gomoku_rule == "outer_open", o.gomoku_exactly_five);
+    case kHex: // ref hex.h:12,63
+        if (n < 2 || n > kMaxN) { setError("hex board size %d not supported (2..19)", n); return nullptr; }
+        return std::make_unique<Hex>(n, o.hex_use_swap_rule);
+    default: return nullptr;
+    }
+}
+
 std::unique_ptr<GameEnv> createGameEnv(const std::string& game, int board_size, float go_komi, const std::string& atari_name, int atari_episode_length,
                                        const std::string& go_ko_rule, size_t atari_recent_observations, const std::string& gomoku_rule, bool gomoku_exactly_five,
                                        bool hex_use_swap_rule)
 {
-    if (game == "atari") { return std::make_unique<AtariSynth>(atari_name, atari_episode_length, std::max<size_t>(1, atari_recent_observations)); }
-    if (game == "tictactoe") { return std::make_unique<TicTacToe>(); }
-    if (game == "othello") {
-        const int n = board_size > 0 ? board_size : 8;
-        if (n < 4 || n > 8 || n % 2) { setError("othello board size %d not supported (even, 4..8)", n); return nullptr; }
-        return std::make_unique<Othello>(n);
-    }
-    if (game == "go") {
-        const int n = board_size > 0 ? board_size : 9;
-        if (n < 2 || n > kMaxN) { setError("go board size %d not supported (2..19)", n); return nullptr; }
-        if (go_ko_rule != "positional" && go_ko_rule != "situational") { setError("env_go_ko_rule '%s' not supported (positional | situational, ref go.cpp:47)", go_ko_rule.c_str()); return nullptr; }
-        return std::make_unique<Go>(n, go_komi, go_ko_rule == "situational");
-    }
-    if (game == "gomoku") { // ref gomoku.h:13,21,44
-        const int n = board_size > 0 ? board_size : 15;
-        if (n > kMaxN) { setError("gomoku board size %d not supported (up to 19)", n); return nullptr; }
-        return std::make_unique<Gomoku>(n, gomoku_rule == "outer_open", gomoku_exactly_five);
-    }
-    if (game == "hex") { // ref hex.h:12,63
-        const int n = board_size > 0 ? board_size : 11;
-        if (n < 2 || n > kMaxN) { setError("hex board size %d not supported (2..19)", n); return nullptr; }
-        return std::make_unique<Hex>(n, hex_use_swap_rule);
-    }
-    setError("unknown env_game '%s' (tictactoe | go | othello | gomoku | hex | atari)", game.c_str());
-    return nullptr;
+    EnvOptions o;
+    o.game = game;
+    o.board_size = board_size;
+    o.go_komi = go_komi;
+    o.go_ko_rule = go_ko_rule;
+    o.gomoku_rule = gomoku_rule;
+    o.gomoku_exactly_five = gomoku_exactly_five;
+    o.hex_use_swap_rule = hex_use_swap_rule;
+    o.atari_name = atari_name;
+    o.atari_episode_length = atari_episode_length;
+    o.atari_recent_observations = atari_recent_observations;
+    return createGameEnv(o);
 }
 
 } // namespace mz

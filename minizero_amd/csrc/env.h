@@ -4,6 +4,7 @@
 // ref environment/{tictactoe,othello,go,gomoku,hex}/*.cpp and SURVEY.md Appendix F; checked against the oracle's
 // restatement by the differential playout tests.
 #pragma once
+#include "game_kind.h"
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -64,8 +65,8 @@ public:
     virtual int rawValidCount() const { return 0; }
     virtual int rawFrameBytes() const { return 0; }
     virtual void rawNewest(uint8_t* /*frame*/, uint8_t* /*meta*/) const {}
-    virtual bool hasDeviceTwin() const { return false; }
-    virtual int deviceKind() const { return 0; } // GoDevView::kind (0 Go, 1 Othello, 2 TicTacToe, 3 Gomoku, 4 Hex)
+    virtual GameKind deviceKind() const { return kNoDeviceGame; } // the row of game_kind.h (GoDevView::kind) when this engine, at this board size, has a device twin
+    bool hasDeviceTwin() const { return deviceKind() != kNoDeviceGame; }
     virtual void exportDeviceRoot(void* /*GoRootSnapshot*/) const {}
     virtual const uint64_t* zobristKeys() const { return nullptr; } // [2][points]
     virtual uint64_t turnKey() const { return 0; }                  // Go, situational superko: XORed into the hash on every move
@@ -86,13 +87,23 @@ protected:
     const RotationTables* rot_ = nullptr;
 };
 
-// game: "tictactoe" | "go" | "othello" | "gomoku" | "hex"; board_size 0 = the game's default (3 / 9 / 8 / 15 / 11)
-// game "atari": the synthetic Atari-shaped environment (18 actions, 32 x 96 x 96 features, 1 player)
-// atari_recent_observations: observation strings kept for the OBS tag (ref atari.cpp:87: intermediate sequence length + 8 + n-step +
-// unrolling + 1, or everything when sequences are off)
-// gomoku_rule / gomoku_exactly_five: env_gomoku_rule ("outer_open" restricts the first move; any other value is the standard rule, as in
-// ref gomoku.cpp:52) and env_gomoku_exactly_five_stones (an overline does not win)
-// hex_use_swap_rule: env_hex_use_swap_rule (ref hex.cpp:28-47,86-99)
+// What createGameEnv needs to know, by configuration key (config.h envOptions fills it from a WorkerConfig).
+struct EnvOptions {
+    std::string game = "tictactoe";          // env_game: "tictactoe" | "go" | "othello" | "gomoku" | "hex" (game_kind.h), or "atari": the synthetic Atari-shaped
+                                             // environment (18 actions, 32 x 96 x 96 features, 1 player)
+    int board_size = 0;                      // env_board_size; 0 = the game's default (gameDefaultBoard)
+    float go_komi = 7.5f;
+    std::string go_ko_rule = "positional";
+    std::string gomoku_rule = "standard";    // "outer_open" restricts the first move; any other value is the standard rule, as in ref gomoku.cpp:52
+    bool gomoku_exactly_five = true;         // env_gomoku_exactly_five_stones (an overline does not win)
+    bool hex_use_swap_rule = true;           // env_hex_use_swap_rule (ref hex.cpp:28-47,86-99)
+    std::string atari_name = "ms_pacman";
+    int atari_episode_length = 1000;
+    // observation strings kept for the OBS tag (ref atari.cpp:87: intermediate sequence length + 8 + n-step + unrolling + 1, or everything when sequences are off)
+    size_t atari_recent_observations = 108001;
+};
+std::unique_ptr<GameEnv> createGameEnv(const EnvOptions& o);
+// the same by position (callers written before EnvOptions)
 std::unique_ptr<GameEnv> createGameEnv(const std::string& game, int board_size, float go_komi, const std::string& atari_name = "ms_pacman",
                                        int atari_episode_length = 1000, const std::string& go_ko_rule = "positional",
                                        size_t atari_recent_observations = 108001, const std::string& gomoku_rule = "standard",

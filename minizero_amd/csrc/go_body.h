@@ -45,19 +45,22 @@ __device__ inline uint64_t waveXor64(uint64_t v)
 __device__ inline uint64_t normH(uint64_t h) { return h ? h : 1; }
 __device__ inline int rotOf(const RotPack& r, int g) { return (r.w[g / 10] >> (3 * (g % 10))) & 7; }
 
-// position + legal mask + feature planes of the leaf selected for game `g` (one wave64; `smem` as sized by goLeafSmemBytes)
+// leafBody<CPL>: position + legal mask + feature planes of the leaf selected for game `g`, by the rules that CPL names (game_kind.h rulesArg) — every kernel that
+// evaluates a leaf calls this one name.  CPL > 0 is Go, whose body this is (`goLeafBody` in earlier notes and profiles); the overload for the other games
+// follows their bodies below.  (Two overloads and not one function that forwards to Go's body: forwarding puts a second inlining level, with its own no-alias
+// scopes, around the body and changes its register allocation.)  One wave64; `smem` as sized by goLeafSmemBytes.
 // PART 0: everything.  PART 1 / 2 (the one-game-per-CU simulation kernel, whose `smem` block then outlives the tower): 1 = what the network needs — the
 // leaf's position (parent + move, stored to its slot), the history block of the planes, the player to move and the terminal flag; 2 = what only the
 // phases AFTER the network need — the path's hashes, the groups' liberties and key sums, the legal mask, the score of a terminal leaf — run by another
 // wave beside the heads: with SYNC it passes a workgroup barrier after the liberties and after the legal mask (the two barriers inside headsBody), and
 // TWO waves share the work — ROLE 0: liberties + key sums | barrier | legal mask of the even 64-point chunks | barrier | score; ROLE 1: the path's hashes |
 // barrier | legal mask of the odd chunks | barrier — so that each piece fits the interval of the heads it runs beside
-template <int CPL, bool EXT_PLANES = false, int PART = 0, bool SYNC = false, int ROLE = 0>
+template <int CPL, bool EXT_PLANES = false, int PART = 0, bool SYNC = false, int ROLE = 0, std::enable_if_t<(CPL > 0), int> = 0>
 // EXT_PLANES: the caller builds the feature planes itself from the history block this body leaves in `smem` (goPlanesPart, all waves)
 // seen_lds: optional LDS copy of the root's positional-superko table (GoRootSnapshot::seen; constant during a move) — the simulation kernel
 // makes one per launch so that the probes of every candidate point are LDS reads instead of dependent trips to L2
-__device__ __forceinline__ void goLeafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane, uint64_t* __restrict__ smem,
-                                           const uint64_t* __restrict__ seen_lds = nullptr)
+__device__ __forceinline__ void leafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane, uint64_t* __restrict__ smem,
+                                         const uint64_t* __restrict__ seen_lds = nullptr)
 {
     const int P = v.P, n = v.n, W = v.W, Ppad = v.Ppad, MD = pv.max_depth;
     uint64_t* gh = smem;                                   // [Ppad] XOR of the keys of a group, by group id
@@ -477,7 +480,7 @@ __device__ __forceinline__ void goLeafBody(const GoDevView& v, const PoolView& p
     }
 }
 
-// The planes of goLeafBody<CPL, true>, shared by `nw` waves (the per-game simulation kernel: every wave takes the planes ch = w, w + nw, ...):
+// The planes of leafBody<CPL, true> (Go), shared by `nw` waves (the per-game simulation kernel: every wave takes the planes ch = w, w + nw, ...):
 // planes 2k / 2k+1 = own / opponent stones k moves ago under the rotation, 16 / 17 = black / white to move (ref go.cpp:280-308).
 // `smem` is the leaf's scratch block (its history words were filled by the leaf body), the player to move is read from v.leaf_player.
 template <int CPL>
@@ -700,7 +703,7 @@ __device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& 
     const int* pact = pv.path_action + size_t(g) * MD;
     const int depth = len - 1;
     const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn, rule = S.hist_len;
+    const int root_turn = S.turn, rule = S.ruleBits();
     const size_t sb = size_t(g) * v.slots;
     const int* hs = pv.hslot + size_t(g) * pv.cap;
     const int src = depth == 0 ? 0 : hs[path[len - 2]];
@@ -858,7 +861,7 @@ __device__ __forceinline__ void hexLeafBody(const GoDevView& v, const PoolView& 
     const int* pact = pv.path_action + size_t(g) * MD;
     const int depth = len - 1;
     const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn, rule = S.hist_len;
+    const int root_turn = S.turn, rule = S.ruleBits();
     const size_t sb = size_t(g) * v.slots;
     const int* hs = pv.hslot + size_t(g) * pv.cap;
     const int src = depth == 0 ? 0 : hs[path[len - 2]];
@@ -930,6 +933,17 @@ __device__ __forceinline__ void hexLeafBody(const GoDevView& v, const PoolView& 
         v.terminal[g] = terminal ? 1 : 0;
         v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); // ref hex.cpp:106-116
     }
+}
+
+// leafBody<CPL> of the two-bitboard games (the template arguments behind CPL, `smem` and `seen_lds` are Go's: unused here)
+template <int CPL, bool EXT_PLANES = false, int PART = 0, bool SYNC = false, int ROLE = 0, std::enable_if_t<(CPL <= 0), int> = 0>
+__device__ __forceinline__ void leafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane, uint64_t* = nullptr, const uint64_t* = nullptr)
+{
+    static_assert(CPL == kRulesTicTacToe || CPL == kRulesOthello || CPL == kRulesGomoku || CPL == kRulesHex, "no leaf body for this rules argument");
+    if constexpr (CPL == kRulesTicTacToe) { tttLeafBody(v, pv, rot, slot, g, lane); }
+    else if constexpr (CPL == kRulesOthello) { othLeafBody(v, pv, rot, slot, g, lane); }
+    else if constexpr (CPL == kRulesGomoku) { gmkLeafBody(v, pv, rot, slot, g, lane); }
+    else { hexLeafBody(v, pv, rot, slot, g, lane); }
 }
 
 // order `k` candidates in cs[] like the reference's std::sort(policy descending): result in out[]

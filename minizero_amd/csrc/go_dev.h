@@ -11,7 +11,10 @@
 // 8-ring), the positional-superko set is the root's hash table plus the hashes along the path.
 #pragma once
 #include "common.h"
+#include "game_kind.h"
 #include "pool.h"
+#include <cstddef>
+#include <type_traits>
 
 namespace mz {
 
@@ -24,23 +27,29 @@ struct GoRootSnapshot {
     uint64_t hist[8][2][kGoMaxW];   // ring of the last 8 positions: entry (hist_len - 1 - j) & 7 is j moves ago
     uint64_t seen[kGoSeenCap];      // positional-superko set: open addressing, linear probing, 0 = empty, hash 0 stored as 1
     uint64_t hash;
-    int32_t hist_len, turn, nmoves, passes; // passes = trailing consecutive passes (capped at 2)
+    int32_t hist_len, turn, nmoves, passes; // Go: positions in `hist` so far, ..., trailing consecutive passes (capped at 2; Othello too)
     uint16_t lab[kGoMaxP + 3];      // group id per point (valid where a stone is): any point of the group
+    // Gomoku and Hex keep other things in two of those words; there they go by these names.  (Accessors, not anonymous unions: a union member is a may-alias
+    // access to the compiler, and with one the kernels that read `hist_len` and `passes` — Go's — are scheduled differently.)  nmoves: Hex counts the actions, a swap is one
+    __host__ __device__ int32_t& ruleBits() { return hist_len; }             // kGmk* / kHex* below
+    __host__ __device__ const int32_t& ruleBits() const { return hist_len; }
+    __host__ __device__ int32_t& winner() { return passes; }                 // 0 none, 1 black, 2 white
+    __host__ __device__ const int32_t& winner() const { return passes; }
 };
+static_assert(sizeof(GoRootSnapshot) == 8 * (2 + 16) * kGoMaxW + 8 * kGoSeenCap + 8 + 16 + 2 * (kGoMaxP + 3), "GoRootSnapshot is copied to the device as it is");
+static_assert(offsetof(GoRootSnapshot, hist_len) == offsetof(GoRootSnapshot, hash) + 8 && offsetof(GoRootSnapshot, passes) == offsetof(GoRootSnapshot, hist_len) + 12,
+              "the words behind ruleBits() and winner()");
 
-// Gomoku (kind 3) in a GoRootSnapshot: stones = the two bitboards, nmoves, turn; passes = the winner (0 none); hist_len = the rule bits:
-// env_gomoku_rule=outer_open, env_gomoku_exactly_five_stones
+// GoRootSnapshot::ruleBits() of Gomoku (env_gomoku_rule=outer_open, env_gomoku_exactly_five_stones) and of Hex (env_hex_use_swap_rule)
 constexpr int kGmkOuterOpen = 1, kGmkExactlyFive = 2;
-
-// Hex (kind 4) in a GoRootSnapshot: as Gomoku; nmoves = the actions played (a swap is one); hist_len = the rule bit env_hex_use_swap_rule
 constexpr int kHexSwap = 1;
 
 struct RotPack { uint32_t w[kRotPackGames / 10]; }; // per-game feature rotation of one cycle, passed as a kernel argument
 inline void rotPackSet(RotPack& r, int g, int rot) { r.w[g / 10] = (r.w[g / 10] & ~(7u << (3 * (g % 10)))) | (uint32_t(rot) << (3 * (g % 10))); }
 
 struct GoDevView {
-    int kind;                  // 0: Go, 1: Othello (two bitboards + pass count per slot, no hash / group ids; same outputs), 2: TicTacToe, 3: Gomoku, 4: Hex
-    int channels;              // feature planes of the game (Go 18, Othello 4)
+    int kind;                  // GameKind (game_kind.h); all but Go: two bitboards + two `meta` words per slot, no hash / group ids; same outputs
+    int channels;              // feature planes of the game (gameChannels)
     int games, n, P, W, A, slots, Ppad, W32, LW;
     float komi;
     uint64_t* stones;          // [games][slots][2][W]
@@ -61,10 +70,9 @@ struct GoDevView {
 
 class GoDevice {
 public:
-    // kind 0: Go (keys = Zobrist table [2][P]); kind 1: Othello (board_n <= 8, keys unused); kind 2: TicTacToe (3x3, 9 actions);
-    // kind 3: Gomoku, kind 4: Hex (board_n <= 19, P actions, keys unused)
+    // keys: Go's Zobrist table [2][P] (unused by the other games); board sizes and the pass action: the game's row of game_kind.h
     int init(int device, int games, int board_n, float komi, int action_size, int slots, int max_depth, hipStream_t stream, const int* const inv[8],
-             const int* const fwd[8], const uint64_t* keys, int kind = 0, uint64_t turn_key = 0);
+             const int* const fwd[8], const uint64_t* keys, int kind = kGo, uint64_t turn_key = 0); // kind: a GameKind
     GoRootSnapshot* hostSnap(int g) { return h_snap_.p + g; }
     int uploadRoots();                                                   // snapshots H2D + slot 0 of every game
     int leafAsync(const PoolView& pv, const RotPack& rot, int slot);      // position + planes + legal mask of the selected leaves
@@ -86,6 +94,20 @@ private:
     DevBuf<uint32_t> feat_;
     DevBuf<float> eval_;
 };
+
+// f(std::integral_constant<int, CPL>) for the rules argument `cpl` (game_kind.h rulesArg): the instance list of the stand-alone leaf and replay kernels.
+// false: no instance (a Go board of more than kGoMaxW words per plane)
+template <class F>
+inline bool forRulesArg(int cpl, F&& f)
+{
+    switch (cpl) {
+#define MZ_RULES_CASE(K) case K: f(std::integral_constant<int, K>{}); return true;
+        MZ_RULES_CASE(1) MZ_RULES_CASE(2) MZ_RULES_CASE(3) MZ_RULES_CASE(4) MZ_RULES_CASE(5) MZ_RULES_CASE(6)
+        MZ_RULES_CASE(kRulesOthello) MZ_RULES_CASE(kRulesTicTacToe) MZ_RULES_CASE(kRulesGomoku) MZ_RULES_CASE(kRulesHex)
+#undef MZ_RULES_CASE
+    default: return false;
+    }
+}
 
 // stand-alone ordering of one candidate list by the device path (tests): out_order[i] = index of the i-th candidate
 int sortCandidatesOnDevice(int device, const float* policy, int n, int* out_order);

@@ -26,30 +26,10 @@ __global__ __launch_bounds__(64) void go_root_kernel(GoDevView v)
 }
 
 template <int CPL>
-__global__ __launch_bounds__(64) void go_leaf_kernel(GoDevView v, PoolView pv, RotPack rp, int slot)
+__global__ __launch_bounds__(64) void leaf_kernel(GoDevView v, PoolView pv, RotPack rp, int slot)
 {
     extern __shared__ uint64_t smem[];
-    goLeafBody<CPL>(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x, smem);
-}
-
-__global__ __launch_bounds__(64) void ttt_leaf_kernel(GoDevView v, PoolView pv, RotPack rp, int slot)
-{
-    tttLeafBody(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x);
-}
-
-__global__ __launch_bounds__(64) void oth_leaf_kernel(GoDevView v, PoolView pv, RotPack rp, int slot)
-{
-    othLeafBody(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x);
-}
-
-__global__ __launch_bounds__(64) void gmk_leaf_kernel(GoDevView v, PoolView pv, RotPack rp, int slot)
-{
-    gmkLeafBody(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x);
-}
-
-__global__ __launch_bounds__(64) void hex_leaf_kernel(GoDevView v, PoolView pv, RotPack rp, int slot)
-{
-    hexLeafBody(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x);
+    leafBody<CPL>(v, pv, rotOf(rp, blockIdx.x), slot, blockIdx.x, threadIdx.x, smem);
 }
 
 __global__ __launch_bounds__(64) void az_cand_kernel(GoDevView v, const float* __restrict__ policy, const float* __restrict__ logit,
@@ -80,13 +60,13 @@ __global__ __launch_bounds__(64) void sort_test_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 int GoDevice::init(int device, int games, int board_n, float komi, int action_size, int slots, int max_depth, hipStream_t stream, const int* const inv[8],
-                   const int* const fwd[8], const uint64_t* keys, int kind, uint64_t turn_key)
+                   const int* const fwd[8], const uint64_t* keys, int kind_arg, uint64_t turn_key)
 {
-    if (kind == 1 && board_n > 8) { setError("GoDevice: Othello boards up to 8x8"); return MZ_ERR_ARG; }
-    if (kind == 2 && (board_n != 3 || action_size != 9)) { setError("GoDevice: TicTacToe is 3x3 with 9 actions"); return MZ_ERR_ARG; }
-    if (kind < 0 || kind > 4) { setError("GoDevice: unknown kind %d", kind); return MZ_ERR_ARG; }
-    // (TicTacToe, Gomoku and Hex have no pass action)
-    if (board_n < 2 || board_n > kGoMaxN || games < 1 || games > kRotPackGames || action_size != board_n * board_n + ((kind == 2 || kind == 3 || kind == 4) ? 0 : 1)) {
+    if (!isDeviceGame(kind_arg)) { setError("GoDevice: unknown kind %d", kind_arg); return MZ_ERR_ARG; }
+    const GameKind kind = static_cast<GameKind>(kind_arg);
+    if (kind == kOthello && board_n > gameMaxBoard(kOthello)) { setError("GoDevice: Othello boards up to 8x8"); return MZ_ERR_ARG; }
+    if (kind == kTicTacToe && (board_n != 3 || action_size != 9)) { setError("GoDevice: TicTacToe is 3x3 with 9 actions"); return MZ_ERR_ARG; }
+    if (board_n < 2 || board_n > kGoMaxN || games < 1 || games > kRotPackGames || action_size != board_n * board_n + (gameHasPass(kind) ? 1 : 0)) {
         setError("GoDevice: unsupported shape (board %d, %d games, %d actions)", board_n, games, action_size);
         return MZ_ERR_ARG;
     }
@@ -95,7 +75,7 @@ int GoDevice::init(int device, int games, int board_n, float komi, int action_si
     max_depth_ = max_depth;
     MZ_HIP(hipSetDevice(device));
     GoDevView& v = v_;
-    v.kind = kind; v.channels = kind == 0 ? 18 : 4;
+    v.kind = kind; v.channels = gameChannels(kind);
     v.games = games; v.n = board_n; v.P = board_n * board_n; v.W = (v.P + 63) / 64; v.A = action_size; v.slots = slots;
     v.Ppad = 64 * v.W; v.W32 = (v.P + 31) / 32; v.LW = (v.A + 63) / 64; v.komi = komi;
     const size_t GS = size_t(games) * slots;
@@ -132,34 +112,11 @@ int GoDevice::uploadRoots()
 int GoDevice::leafAsync(const PoolView& pv, const RotPack& rot, int slot)
 {
     if (slot < 0 || slot >= v_.slots) { setError("GoDevice::leafAsync: slot %d out of range", slot); return MZ_ERR_ARG; }
-    if (v_.kind == 2) {
-        hipLaunchKernelGGL(ttt_leaf_kernel, dim3(v_.games), dim3(64), 0, stream_, v_, pv, rot, slot);
-        MZ_HIP(hipGetLastError());
-        return MZ_OK;
+    const size_t smem = v_.kind == kGo ? goLeafSmemBytes(v_, pv.max_depth) : 0;
+    if (!forRulesArg(rulesArg(v_.kind, v_.n), [&](auto cpl) { hipLaunchKernelGGL(leaf_kernel<cpl()>, dim3(v_.games), dim3(64), smem, stream_, v_, pv, rot, slot); })) {
+        setError("GoDevice: board too large");
+        return MZ_ERR_ARG;
     }
-    if (v_.kind == 1) {
-        hipLaunchKernelGGL(oth_leaf_kernel, dim3(v_.games), dim3(64), 0, stream_, v_, pv, rot, slot);
-        MZ_HIP(hipGetLastError());
-        return MZ_OK;
-    }
-    if (v_.kind == 3) {
-        hipLaunchKernelGGL(gmk_leaf_kernel, dim3(v_.games), dim3(64), 0, stream_, v_, pv, rot, slot);
-        MZ_HIP(hipGetLastError());
-        return MZ_OK;
-    }
-    if (v_.kind == 4) {
-        hipLaunchKernelGGL(hex_leaf_kernel, dim3(v_.games), dim3(64), 0, stream_, v_, pv, rot, slot);
-        MZ_HIP(hipGetLastError());
-        return MZ_OK;
-    }
-    const size_t smem = goLeafSmemBytes(v_, pv.max_depth);
-#define MZ_GO_CASE(K) \
-    case K: hipLaunchKernelGGL(go_leaf_kernel<K>, dim3(v_.games), dim3(64), smem, stream_, v_, pv, rot, slot); break;
-    switch (v_.W) {
-        MZ_GO_CASE(1) MZ_GO_CASE(2) MZ_GO_CASE(3) MZ_GO_CASE(4) MZ_GO_CASE(5) MZ_GO_CASE(6)
-    default: setError("GoDevice: board too large"); return MZ_ERR_ARG;
-    }
-#undef MZ_GO_CASE
     MZ_HIP(hipGetLastError());
     return MZ_OK;
 }

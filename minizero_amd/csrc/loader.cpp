@@ -215,8 +215,7 @@ int Loader::init(int device, const char* conf)
     if (cfg_.nn_type_name != "alphazero" && cfg_.nn_type_name != "muzero") { setError("nn_type_name must be alphazero or muzero (ref data_loader.cpp:135-141)"); return MZ_ERR_ARG; }
     muzero_ = cfg_.nn_type_name == "muzero";
     atari_ = cfg_.env_game == "atari";
-    proto_ = createGameEnv(cfg_.env_game, cfg_.env_board_size, cfg_.env_go_komi, cfg_.env_atari_name, cfg_.env_atari_episode_length, cfg_.env_go_ko_rule, 1,
-                           cfg_.env_gomoku_rule, cfg_.env_gomoku_exactly_five_stones, cfg_.env_hex_use_swap_rule);
+    proto_ = createGameEnv(envOptions(cfg_, 1));
     if (!proto_) { return MZ_ERR_ARG; }
     if (!atari_ && !proto_->hasDeviceTwin()) { setError("loader: no device engine for %s at this board size", proto_->name().c_str()); return MZ_ERR_ARG; }
     A_ = proto_->policySize();
@@ -426,7 +425,7 @@ void Loader::actionFeaturesOf(const LGame& g, int pos, int rot, float* out)
     if (atari_) { // atari.cpp:223-235
         const int a = pos < size ? g.action[pos] : randInt() % 18;
         std::fill(out + a * 36, out + (a + 1) * 36, 1.0f);
-    } else if (cfg_.env_game == "tictactoe" || cfg_.env_game == "gomoku" || cfg_.env_game == "hex") { // tictactoe.cpp:148-155, gomoku.cpp:177-185, hex.cpp:364-371 (no pass action; Hex's rotation is the identity)
+    } else if (!gameHasPass(proto_->deviceKind())) { // tictactoe.cpp:148-155, gomoku.cpp:177-185, hex.cpp:364-371 (no pass action; Hex's rotation is the identity)
         out[pos < size ? rotateAction(g.action[pos], rot) : randInt() % P_] = 1.0f;
     } else if (pos < size) { // go.cpp:725-737, othello.cpp:264-276
         if (g.action[pos] != P_) { out[rotateAction(g.action[pos], rot)] = 1.0f; }

@@ -12,10 +12,10 @@ namespace {
 
 
 // Go: the moves 1 .. upto of sample g applied ONE AFTER THE OTHER ON THE SAME WAVE STATE (stones and group ids in registers + LDS, the hash in a register)
-// instead of one goLeafBody per move through the position slots in global memory (load the parent, apply, store: 3 us per move, 0.5 ms for a
-// 160-move sample).  Same observable effects as the "leaf = parent + one move" part of goLeafBody (ref go.cpp:132-190); every position's hash and
+// instead of one leafBody per move through the position slots in global memory (load the parent, apply, store: 3 us per move, 0.5 ms for a
+// 160-move sample).  Same observable effects as the "leaf = parent + one move" part of Go's leafBody (ref go.cpp:132-190); every position's hash and
 // move counters are stored, stones and group ids only for the last `keep` positions — what the planes of the sampled position (8 positions of
-// history) and the final goLeafBody (its parent slot) read.
+// history) and the final leafBody (its parent slot) read.
 template <int CPL>
 __device__ __forceinline__ void goReplayMoves(const GoDevView& v, const PoolView& pv, int g, int lane, uint64_t* __restrict__ smem, int upto, int keep)
 {
@@ -25,7 +25,7 @@ __device__ __forceinline__ void goReplayMoves(const GoDevView& v, const PoolView
     uint64_t* hb = ph + MD + 4;
     uint64_t* cur = hb + 16 * W;
     int* libs = reinterpret_cast<int*>(cur + 2 * W);
-    uint16_t* lab = reinterpret_cast<uint16_t*>(libs + Ppad); // same LDS layout as goLeafBody
+    uint16_t* lab = reinterpret_cast<uint16_t*>(libs + Ppad); // same LDS layout as Go's leafBody
     uint8_t* col = reinterpret_cast<uint8_t*>(lab + Ppad);
     const int* pact = pv.path_action + size_t(g) * MD;
     const size_t sb = size_t(g) * v.slots;
@@ -131,7 +131,7 @@ __device__ __forceinline__ void goReplayMoves(const GoDevView& v, const PoolView
             v.meta[(sb + d) * 2] = nmoves;
             v.meta[(sb + d) * 2 + 1] = passes;
         }
-        if (d > upto - keep) { // one of the last positions: the planes of the sampled position and the final goLeafBody read its slot
+        if (d > upto - keep) { // one of the last positions: the planes of the sampled position and the final leafBody read its slot
 #pragma unroll
             for (int i = 0; i < CPL; ++i) {
                 const int p = i * 64 + lane;
@@ -148,25 +148,21 @@ __device__ __forceinline__ void goReplayMoves(const GoDevView& v, const PoolView
 }
 
 // sample g: moves pact[g][1 .. pos[g]] replayed from the root snapshot (slot 0); the planes of the last position under rot[g] end in v.feat
-template <int KIND, int CPL>
+template <int CPL>
 __global__ __launch_bounds__(64) void replay_kernel(GoDevView v, PoolView pv, const int* __restrict__ pos, const uint8_t* __restrict__ rot)
 {
     extern __shared__ uint64_t smem[];
     const int g = blockIdx.x, lane = threadIdx.x;
     const int n = pos[g], r = rot[g];
     int d0 = 0;
-    if constexpr (KIND == 0) { // Go: all moves but the last on one wave state; the last one (the sampled position) through goLeafBody
+    if constexpr (CPL > 0) { // Go: all moves but the last on one wave state; the last one (the sampled position) through its leaf body
         if (n > 1) { goReplayMoves<CPL>(v, pv, g, lane, smem, n - 1, 8); d0 = n; }
     }
     for (int d = d0; d <= n; ++d) {
         if (lane == 0) { pv.path_len[g] = d + 1; }
         waveSync();
         if (d == 0 && n > 0) { continue; } // slot 0 is the uploaded root: only evaluate it when it is the sampled position itself
-        if constexpr (KIND == 2) { tttLeafBody(v, pv, r, d, g, lane); }
-        else if constexpr (KIND == 1) { othLeafBody(v, pv, r, d, g, lane); }
-        else if constexpr (KIND == 3) { gmkLeafBody(v, pv, r, d, g, lane); }
-        else if constexpr (KIND == 4) { hexLeafBody(v, pv, r, d, g, lane); }
-        else { goLeafBody<CPL>(v, pv, r, d, g, lane, smem); }
+        leafBody<CPL>(v, pv, r, d, g, lane, smem);
         waveSync();
     }
 }
@@ -204,19 +200,10 @@ __global__ __launch_bounds__(256) void expand_atari_kernel(const uint8_t* __rest
 int loaderReplayFeatures(GoDevice& gd, const PoolView& pv, int B, const int* d_pos, const uint8_t* d_rot, float* d_out, hipStream_t stream)
 {
     const GoDevView& v = gd.v_;
-    if (v.kind == 2) { hipLaunchKernelGGL((replay_kernel<2, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
-    else if (v.kind == 1) { hipLaunchKernelGGL((replay_kernel<1, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
-    else if (v.kind == 3) { hipLaunchKernelGGL((replay_kernel<3, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
-    else if (v.kind == 4) { hipLaunchKernelGGL((replay_kernel<4, 1>), dim3(B), dim3(64), 0, stream, v, pv, d_pos, d_rot); }
-    else {
-        const size_t smem = goLeafSmemBytes(v, pv.max_depth);
-#define MZ_REPLAY_CASE(K) \
-    case K: hipLaunchKernelGGL((replay_kernel<0, K>), dim3(B), dim3(64), smem, stream, v, pv, d_pos, d_rot); break;
-        switch (v.W) {
-            MZ_REPLAY_CASE(1) MZ_REPLAY_CASE(2) MZ_REPLAY_CASE(3) MZ_REPLAY_CASE(4) MZ_REPLAY_CASE(5) MZ_REPLAY_CASE(6)
-        default: setError("loader: board too large for the device engine"); return MZ_ERR_ARG;
-        }
-#undef MZ_REPLAY_CASE
+    const size_t smem = v.kind == kGo ? goLeafSmemBytes(v, pv.max_depth) : 0;
+    if (!forRulesArg(rulesArg(v.kind, v.n), [&](auto cpl) { hipLaunchKernelGGL(replay_kernel<cpl()>, dim3(B), dim3(64), smem, stream, v, pv, d_pos, d_rot); })) {
+        setError("loader: board too large for the device engine");
+        return MZ_ERR_ARG;
     }
     MZ_HIP(hipGetLastError());
     hipLaunchKernelGGL(expand_bits_kernel, dim3(B), dim3(256), 0, stream, v.feat, v.channels, v.P, v.W32, d_out);

@@ -4,6 +4,7 @@
 // muzero_network.py:137-164.  Arithmetic order is specified in DESIGN.md §"Network numerics".
 #pragma once
 #include "common.h"
+#include "game_kind.h"
 #include <string>
 
 namespace mz {
@@ -65,6 +66,8 @@ struct SimMzMode {
     int alt_base = 0;     // != 0: the slab has 2 x alt_base slots per game, the upper half for the rounds' second expected leaves (sim.hip simPreProbe)
 };
 
+constexpr int kNoiseDirichlet = 1, kNoiseGumbel = 2; // the root noise of a simulation-kernel launch (ref zero_actor.cpp:194-213)
+
 class Net {
 public:
     Net() = default;
@@ -88,16 +91,16 @@ public:
     // the per-game simulation kernel (sim.hip): `nsims` whole simulations (select, leaf environment, tower, heads, candidates, expand +
     // backup) of every game in ONE launch, each game advancing on its own workgroup.  *launched = false when no instance fits.
     // d_root_noise ([games][A], nullable): Dirichlet noise applied to the root children before simulation 1
-    // noise_kind 1: Dirichlet on the priors, 2: Gumbel on the logits; gum != nullptr: Gumbel root logic on the device (d_start: [games] scratch;
+    // noise_kind: kNoiseDirichlet (on the priors) or kNoiseGumbel (on the logits); gum != nullptr: Gumbel root logic on the device (d_start: [games] scratch;
     // host_start: the first simulation starts from d_start as uploaded by the host)
     int simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_logit, float* d_value, const uint8_t* d_rot, int sim0, int nsims,
-                  bool* launched, const float* d_root_noise = nullptr, float noise_eps = 0.0f, int noise_kind = 1, const struct GumbelView* gum = nullptr,
+                  bool* launched, const float* d_root_noise = nullptr, float noise_eps = 0.0f, int noise_kind = kNoiseDirichlet, const struct GumbelView* gum = nullptr,
                   int* d_start = nullptr, bool host_start = false);
     // tail help (sim_help.h): the caller has the GPU to itself and runs one simLaunch at a time — workgroups whose game is done may help the stragglers of their
     // XCD with their towers (only the 9x9 x 64 f32 instance, launches of at least kSimHelpMinLaunch simulations, one workgroup per CU at most)
     void allowTailHelp(bool on) { tail_help_ = on; }
     // num_simulation: the kernels keep per-search tables / the path in LDS; searches too long for 160 KB use the lock-step kernels
-    bool hasSimKernel(int board_n, int env_kind = 0, int num_simulation = 0) const; // env_kind: GoDevView::kind
+    bool hasSimKernel(int board_n, int env_kind = kGo, int num_simulation = 0) const; // env_kind: GameKind, as stored in GoDevView::kind
     // ... on the one-tile tower (sim_wide.inc, sim_wide_a.hip): Go with 128 / 256 hidden channels or on 7x7 / 13x13 / 19x19 boards
     bool hasSimKernelWide(int board_n, int env_kind, int num_simulation) const;
     bool simWidePlan(int board_n, int env_kind, int num_simulation, const HeadParams& hp, int channels, int W32, size_t leaf_bytes, size_t scratch_bytes, int* lf, size_t* lds,

@@ -555,7 +555,7 @@ __device__ __forceinline__ float orderedSumWave(const float* x, int n, int lane)
 
 // the body of heads_kernel for sample `b`, run by NT threads (a multiple of 64, >= 128); `sm` = (C*P + PC*P + P + VH + A + 16) floats of LDS
 // With xlds and without scale_hidden it passes exactly TWO workgroup barriers (after the conv1x1, after the FCs): the simulation kernel runs the second half
-// of the Go leaf beside it on waves that have no share of the heads (sim.hip simLeafRest / go_body.h goLeafBody PART 2), and those waves pass the same two.
+// of the Go leaf beside it on waves that have no share of the heads (sim.hip simLeafRest / go_body.h leafBody PART 2), and those waves pass the same two.
 // BIGA (boards of more than 128 actions, 13x13 / 19x19 Go: the policy FC is a 722-step chain per logit at 19x19): the weights of the long chains 64 steps ahead, and the
 // value FC1 on the threads the policy FC leaves free (two hidden units per thread, interleaved) instead of behind it on the same threads.  Same chains, same bits.
 // FP ("fast pointers", simulation kernels only: activations and scratch are LDS, weights global memory): every chain reads its weights with GLOBAL loads and its x

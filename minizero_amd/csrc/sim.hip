@@ -463,9 +463,9 @@ constexpr int kSimHelpMinLaunch = 64, kSimHelpMinLeft = 2;
 #define MZ_SIM_CASES(X) \
     X(9, 9, 20, 64, 2)  /* 9x9 Go, 64 channels (BASELINE configs[1]) */ \
     X(9, 9, 20, 8, 2)   /* small 9x9 test nets */ \
-    X(8, 8, 4, 64, 0)   /* 8x8 Othello, 64 channels (BASELINE configs[2]); CPL 0 = the Othello rules */ \
-    X(8, 8, 4, 8, 0)    /* small 8x8 Othello test nets */ \
-    X(3, 3, 4, 16, -1)  /* TicTacToe, 16 channels (BASELINE configs[0]); CPL -1 = the TicTacToe rules */
+    X(8, 8, 4, 64, kRulesOthello)   /* 8x8 Othello, 64 channels (BASELINE configs[2]) */ \
+    X(8, 8, 4, 8, kRulesOthello)    /* small 8x8 Othello test nets */ \
+    X(3, 3, 4, 16, kRulesTicTacToe) /* TicTacToe, 16 channels (BASELINE configs[0]) */
 
 // MZ_SIM_PROF: between two launches (stream order), the running launch's words of the profile's tail (sim_az_body.h simProfEnter / simProfExit) are added to the
 // sums — [8] launches, [9] / [10] / [11] ticks from the earliest start of a game to the first exit, the last exit and the mean exit, [12] mean ticks per CU spent
@@ -657,7 +657,7 @@ bool Net::hasSimKernel(int board_n, int env_kind, int num_simulation) const
         if (sizeof(uint64_t) * (64 * Wq + size_t(num_simulation) + 3 + 4 + 18 * Wq) + 64 * Wq * 7 > tile_bytes) { return false; }
     }
 #define MZ_SIM_HAS(h, w, cin0, cpad, cpl) \
-    if (H == h && W == w && c0 == cin0 && C == cpad && board_n == h && (env_kind == 4 ? -3 : env_kind == 3 ? -2 : env_kind == 2 ? -1 : env_kind == 1 ? 0 : (h * w + 63) / 64) == cpl) { return true; }
+    if (H == h && W == w && c0 == cin0 && C == cpad && board_n == h && rulesArg(env_kind, h) == cpl) { return true; }
     MZ_SIM_CASES(MZ_SIM_HAS)
 #undef MZ_SIM_HAS
     return false;
@@ -720,7 +720,7 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     // within a few simulations of each other and there is no tail to fill.  MZ_SIM_HELP_MIN=k (tests, experiments): launches of >= k simulations help, and a
     // game is claimed while it has >= min(k, kSimHelpMinLeft) simulations left.
     bool help = false;
-    if (tail_help_ && !bf && !(a.no_spec & 32) && H == 9 && W == 9 && c0 == 20 && C == 64 && a.ta.OT == 4 && gv.n == 9 && gv.kind == 0 && gv.games >= 2 && gv.games <= cu_count_ &&
+    if (tail_help_ && !bf && !(a.no_spec & 32) && H == 9 && W == 9 && c0 == 20 && C == 64 && a.ta.OT == 4 && gv.n == 9 && gv.kind == kGo && gv.games >= 2 && gv.games <= cu_count_ &&
         gv.games <= 1024 && helpCmdUnits(gv.channels * gv.W32) <= kHpMaxUnits) {
         const int env_min = getenv("MZ_SIM_HELP_MIN") ? std::max(1, atoi(getenv("MZ_SIM_HELP_MIN"))) : 0;
         const size_t words = helpWords(C, H * W);
@@ -747,23 +747,17 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     const bool two_per_cu = !bf && H * W <= 64 && tile_bytes <= size_t(76) * 1024;
     const size_t lds = tile_bytes + size_t(a.rcp_n) * sizeof(double) +
                        (two_per_cu ? 0 : size_t(a.rcp_n) * (sizeof(double) + sizeof(float)) + kSpecWords * sizeof(int)) + (simXchgWords(gv.A, gv.channels, gv.W32) + 2 + 2 * size_t(pool.v_.max_depth) + 2) * sizeof(float) +
-                       ((gv.kind == 0 && !two_per_cu) ? size_t(kGoSeenCap) * sizeof(uint64_t) + ((goLeafSmemBytes(gv, pool.v_.max_depth) + 7) & ~size_t(7)) : 0);
-    // the argument block is constant between weight reloads / re-allocations: upload it only when it changed
-    static_assert(sizeof(SimArgs) % 4 == 0, "SimArgs is copied as words");
-    if (sim_args_host_.size() != sizeof(SimArgs) || memcmp(sim_args_host_.data(), &a, sizeof(SimArgs)) != 0) {
-        if (!sim_args_.ensure(sizeof(SimArgs))) { setError("hipMalloc of the simulation arguments failed"); return MZ_ERR_DEVICE; }
-        MZ_HIP(hipStreamSynchronize(stream_));
-        MZ_HIP(hipMemcpy(sim_args_.p, &a, sizeof(SimArgs), hipMemcpyHostToDevice));
-        sim_args_host_.assign(reinterpret_cast<const char*>(&a), reinterpret_cast<const char*>(&a) + sizeof(SimArgs));
-    }
+                       ((gv.kind == kGo && !two_per_cu) ? size_t(kGoSeenCap) * sizeof(uint64_t) + ((goLeafSmemBytes(gv, pool.v_.max_depth) + 7) & ~size_t(7)) : 0);
+    rc = uploadSimArgs(a);
+    if (rc) { return rc; }
     if (lds > size_t(160) * 1024) { setError("simLaunch: %zu bytes of LDS needed", lds); return MZ_OK; }
     if (bf) { // the two BASELINE shapes the bf16x3 tower is built for
-        if (H == 9 && W == 9 && c0 == 20 && C == 64 && gv.n == 9 && gv.kind == 0 && gv.W == 2) { *launched = true; return launchSimT<9, 9, 20, 64, 2, true>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, host_start ? 1 : 0, lds, stream_); }
-        if (H == 8 && W == 8 && c0 == 4 && C == 64 && gv.n == 8 && gv.kind == 1) { *launched = true; return launchSimT<8, 8, 4, 64, 0, true>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, host_start ? 1 : 0, lds, stream_); }
+        if (H == 9 && W == 9 && c0 == 20 && C == 64 && gv.n == 9 && gv.kind == kGo && gv.W == 2) { *launched = true; return launchSimT<9, 9, 20, 64, 2, true>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, host_start ? 1 : 0, lds, stream_); }
+        if (H == 8 && W == 8 && c0 == 4 && C == 64 && gv.n == 8 && gv.kind == kOthello) { *launched = true; return launchSimT<8, 8, 4, 64, kRulesOthello, true>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, host_start ? 1 : 0, lds, stream_); }
         return MZ_OK;
     }
 #define MZ_SIM_LAUNCH(h, w, cin0, cpad, cpl) \
-    if (H == h && W == w && c0 == cin0 && C == cpad && gv.n == h && (gv.kind == 4 ? -3 : gv.kind == 3 ? -2 : gv.kind == 2 ? -1 : gv.kind == 1 ? 0 : gv.W) == cpl) { *launched = true; return launchSimT<h, w, cin0, cpad, cpl>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, start_bits, lds, stream_); }
+    if (H == h && W == w && c0 == cin0 && C == cpad && gv.n == h && rulesArg(gv.kind, gv.n) == cpl) { *launched = true; return launchSimT<h, w, cin0, cpad, cpl>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, start_bits, lds, stream_); }
     MZ_SIM_CASES(MZ_SIM_LAUNCH)
 #undef MZ_SIM_LAUNCH
     return MZ_OK;

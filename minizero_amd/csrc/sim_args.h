@@ -34,7 +34,7 @@ struct SimArgs {
     int slots, A, LW, num_players;
     const float* root_noise;          // [games][A] noise of the root children (host RNG), applied before simulation 1; nullptr: none
     float noise_eps;
-    int noise_kind;                   // 1: Dirichlet on the priors, 2: Gumbel on the logits (ref zero_actor.cpp:194-213)
+    int noise_kind;                   // kNoiseDirichlet: on the priors, kNoiseGumbel: on the logits (net.h)
     int use_gumbel;                   // Gumbel root logic (sequential halving + start node) between simulations
     GumbelView gum;
     int* start;                       // [games] start node of the next selection (written by the Gumbel step or by the host)

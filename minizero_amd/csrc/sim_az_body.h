@@ -141,16 +141,13 @@ __device__ __noinline__ void simSelectLeaf(CSimArgs* __restrict__ a, int rot, in
     }
     MZ_LPROF(0);
     const GoDevView gv = simLeafView(ldc(&a->gv), xchg, g);
-    if constexpr (CPL == -1) { tttLeafBody(gv, pv, rot, slot, g, lane); } // CPL -1: TicTacToe, 0: Othello, -2: Gomoku (go_body.h)
-    else if constexpr (CPL == -2) { gmkLeafBody(gv, pv, rot, slot, g, lane); }
-    else if constexpr (CPL == -3) { hexLeafBody(gv, pv, rot, slot, g, lane); } // -3: Hex
-    else if constexpr (CPL == 0) { othLeafBody(gv, pv, rot, slot, g, lane); }
-    else if (leaf_smem) { goLeafBody<CPL, true, 1>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds); } // what the network needs; the rest beside the heads (simLeafRest)
-    else { goLeafBody<CPL, true>(gv, pv, rot, slot, g, lane, reinterpret_cast<uint64_t*>(tiles), seen_lds); } // planes: simLeafPlanes, all waves
+    if constexpr (CPL <= 0) { leafBody<CPL>(gv, pv, rot, slot, g, lane); } // the two-bitboard games (game_kind.h rulesArg)
+    else if (leaf_smem) { leafBody<CPL, true, 1>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds); } // what the network needs; the rest beside the heads (simLeafRest)
+    else { leafBody<CPL, true>(gv, pv, rot, slot, g, lane, reinterpret_cast<uint64_t*>(tiles), seen_lds); } // planes: simLeafPlanes, all waves
 }
 
 // Go, one game per CU: what only the phases after the network need of the leaf — path hashes, liberties, legal mask, a terminal leaf's score (go_body.h
-// goLeafBody PART 2) — on the workgroup's last two waves BESIDE the heads, in which those waves have no share.  They pass the two barriers headsBody passes.
+// leafBody PART 2) — on the workgroup's last two waves BESIDE the heads, in which those waves have no share.  They pass the two barriers headsBody passes.
 template <int CPL>
 __device__ __noinline__ void simLeafRest(CSimArgs* __restrict__ a, int rot, int slot, int g, int lane, float* xchg, const uint64_t* seen_lds, uint64_t* leaf_smem, int role)
 {
@@ -161,8 +158,8 @@ __device__ __noinline__ void simLeafRest(CSimArgs* __restrict__ a, int rot, int 
     if constexpr (CPL > 0) {
         const PoolView pv = simPathView(ldc(&a->pv), reinterpret_cast<int*>(xchg) - 2 * a->pv.max_depth - 2, g);
         const GoDevView gv = simLeafView(ldc(&a->gv), xchg, g);
-        if (role == 0) { goLeafBody<CPL, true, 2, true, 0>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds); }
-        else { goLeafBody<CPL, true, 2, true, 1>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds); }
+        if (role == 0) { leafBody<CPL, true, 2, true, 0>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds); }
+        else { leafBody<CPL, true, 2, true, 1>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds); }
     }
 }
 
@@ -309,7 +306,7 @@ __device__ __noinline__ void simApplyRootNoise(CSimArgs* __restrict__ a, int g, 
     const float eps = a->noise_eps;
     for (int i = lane; i < nc; i += 64) {
         const float nz = a->root_noise[size_t(g) * v.A + i];
-        if (a->noise_kind == 1) { v.rec[fc + i].policy = (1 - eps) * v.rec[fc + i].policy + eps * nz; }
+        if (a->noise_kind == kNoiseDirichlet) { v.rec[fc + i].policy = (1 - eps) * v.rec[fc + i].policy + eps * nz; }
         else { v.logit[fc + i] = v.logit[fc + i] + nz; }
         v.noise[fc + i] = nz;
     }

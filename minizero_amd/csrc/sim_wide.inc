@@ -150,31 +150,34 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
     return MZ_OK;
 }
 
-// instances by part: (H, W, input channels of the stem padded to 16, hidden channels, 64-bit words per plane of the Go engine)
+// The parts, listed once: part n is simWideLaunchPart<n>, defined by the translation unit built with MZ_SIM_WIDE_PART == n and tried in this order (sim_wide_a.hip)
+#define MZ_SIM_WIDE_PARTS(X) X(0) X(1) X(2) X(3) X(4) X(5)
+#define MZ_SIM_WIDE_FN(n) simWideLaunchPart##n
+#define MZ_SIM_WIDE_SIG(n)                                                                                                                                                    \
+    bool MZ_SIM_WIDE_FN(n)(int H, int W, int c0q, int C, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds, \
+                           hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words)
+#define MZ_SIM_WIDE_SIG_OF(n) MZ_SIM_WIDE_SIG(n) // (expands MZ_SIM_WIDE_PART before it is pasted)
+
+// instances by part: (H, W, input channels of the stem padded to 16, hidden channels, the rules argument: game_kind.h rulesArg)
 #if MZ_SIM_WIDE_PART == 0
 #define MZ_SIM_WIDE_PART_CASES(X) X(9, 9, 32, 128, 2) X(9, 9, 32, 32, 2) X(7, 7, 32, 128, 1) X(13, 13, 32, 64, 3)
-#define MZ_SIM_WIDE_PART_FN simWideLaunchPart0
 #elif MZ_SIM_WIDE_PART == 1
 #define MZ_SIM_WIDE_PART_CASES(X) X(7, 7, 32, 32, 1) X(7, 7, 32, 64, 1) X(7, 7, 32, 256, 1)
-#define MZ_SIM_WIDE_PART_FN simWideLaunchPart1
-#elif MZ_SIM_WIDE_PART == 3 // Othello (words per plane 0) and TicTacToe (-1: sim_az_body.h simSelectLeaf) at the reference's default width: the same phase functions as sim_kernel's
-#define MZ_SIM_WIDE_PART_CASES(X) X(8, 8, 16, 128, 0) X(8, 8, 16, 256, 0) X(3, 3, 16, 128, -1) X(3, 3, 16, 256, -1)
-#define MZ_SIM_WIDE_PART_FN simWideLaunchPart3
-#elif MZ_SIM_WIDE_PART == 4 // Gomoku (words per plane -2: sim_az_body.h simSelectLeaf) on its default 15x15 board: 64 channels (measured), 32 (tests)
-#define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 16, 64, -2) X(15, 15, 16, 32, -2)
-#define MZ_SIM_WIDE_PART_FN simWideLaunchPart4
-#elif MZ_SIM_WIDE_PART == 5 // Hex (words per plane -3: sim_az_body.h simSelectLeaf) on its default 11x11 board: 64 channels (measured), 32 (tests), 128
-#define MZ_SIM_WIDE_PART_CASES(X) X(11, 11, 16, 64, -3) X(11, 11, 16, 32, -3) X(11, 11, 16, 128, -3)
-#define MZ_SIM_WIDE_PART_FN simWideLaunchPart5
-#else // (built with MZ_SPEC_WAYS = 4: the shapes whose tile leaves too little LDS for sixteen remembered paths)
+#elif MZ_SIM_WIDE_PART == 2 // (built with MZ_SPEC_WAYS = 4: the shapes whose tile leaves too little LDS for sixteen remembered paths)
 #define MZ_SIM_WIDE_PART_CASES(X) X(19, 19, 32, 64, 6) X(19, 19, 32, 32, 6) X(13, 13, 32, 128, 3) X(9, 9, 32, 256, 2)
-#define MZ_SIM_WIDE_PART_FN simWideLaunchPart2
+#elif MZ_SIM_WIDE_PART == 3 // Othello and TicTacToe at the reference's default width: the same phase functions as sim_kernel's
+#define MZ_SIM_WIDE_PART_CASES(X) X(8, 8, 16, 128, kRulesOthello) X(8, 8, 16, 256, kRulesOthello) X(3, 3, 16, 128, kRulesTicTacToe) X(3, 3, 16, 256, kRulesTicTacToe)
+#elif MZ_SIM_WIDE_PART == 4 // Gomoku on its default 15x15 board: 64 channels (measured), 32 (tests)
+#define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 16, 64, kRulesGomoku) X(15, 15, 16, 32, kRulesGomoku)
+#elif MZ_SIM_WIDE_PART == 5 // Hex on its default 11x11 board: 64 channels (measured), 32 (tests), 128
+#define MZ_SIM_WIDE_PART_CASES(X) X(11, 11, 16, 64, kRulesHex) X(11, 11, 16, 32, kRulesHex) X(11, 11, 16, 128, kRulesHex)
+#else
+#error "MZ_SIM_WIDE_PART: not one of MZ_SIM_WIDE_PARTS"
 #endif
 
 // true: this part holds the instance (launched when d_args != nullptr; d_args == nullptr: a query, *tile_bytes = the LDS bytes of the tower's tile, *spec_words = the
 // words of the walk's speculation memory as this translation unit was built)
-bool MZ_SIM_WIDE_PART_FN(int H, int W, int c0q, int C, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds,
-                         hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words)
+MZ_SIM_WIDE_SIG_OF(MZ_SIM_WIDE_PART)
 {
 #define MZ_SIM_WIDE_ONE(h, w, cin0q, c, cp)                                                                                                        \
     if (H == h && W == w && c0q == cin0q && C == c && cpl == cp) {                                                                                 \

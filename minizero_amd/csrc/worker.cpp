@@ -624,8 +624,7 @@ int Worker::createActors()
         const size_t recent_obs = static_cast<size_t>(cfg_.zero_actor_intermediate_sequence_length == 0
                                                           ? 108000
                                                           : cfg_.zero_actor_intermediate_sequence_length + 8 + cfg_.learner_n_step_return + cfg_.learner_muzero_unrolling_step) + 1;
-        g.env = createGameEnv(cfg_.env_game, cfg_.env_board_size, cfg_.env_go_komi, cfg_.env_atari_name, cfg_.env_atari_episode_length, cfg_.env_go_ko_rule,
-                              recent_obs, cfg_.env_gomoku_rule, cfg_.env_gomoku_exactly_five_stones, cfg_.env_hex_use_swap_rule);
+        g.env = createGameEnv(envOptions(cfg_, recent_obs));
         if (!g.env) { return MZ_ERR_ARG; }
         if (g.env->policySize() != A_ || g.env->featureSize() != net0().featSize()) {
             setError("network (A=%d, features=%d) does not fit env %s (A=%d, features=%d)", A_, net0().featSize(), g.env->name().c_str(),
@@ -1607,7 +1606,7 @@ int Worker::runCyclesSim(int n)
                 if (!use_rounds || part == 0) { MZ_HIP(hipEventRecord(L->ev0[use_rounds ? 0 : part], L->stream)); }
                 GumbelView gv = gum_;
                 gv.state = L->d_gum.p;
-                const int noise_kind = cfg_.actor_use_dirichlet_noise ? 1 : 2;
+                const int noise_kind = cfg_.actor_use_dirichlet_noise ? kNoiseDirichlet : kNoiseGumbel;
                 const bool hg = host_gumbel && part == 0 && !root_on_device;
                 if (use_rounds) {
                     // the first round needs the noisy logits before simulation 1 runs: the noise goes out as a launch of its own
@@ -1985,9 +1984,9 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         // would miss frames, so they are fixed where observations are kept (board games: free to change, like the reference)
         if (games_[0].env->hasObservations()) { MZ_FIXED(zero_actor_intermediate_sequence_length) MZ_FIXED(learner_n_step_return) MZ_FIXED(learner_muzero_unrolling_step) }
         // Gomoku's rules live in its engines (host and device) from creation; for every other game the two keys are inert
-        if (games_[0].env->deviceKind() == 3) { MZ_FIXED(env_gomoku_rule) MZ_FIXED(env_gomoku_exactly_five_stones) }
+        if (gameFromName(cfg_.env_game.c_str()) == kGomoku) { MZ_FIXED(env_gomoku_rule) MZ_FIXED(env_gomoku_exactly_five_stones) }
         // ... and so does Hex's swap rule
-        if (games_[0].env->deviceKind() == 4) { MZ_FIXED(env_hex_use_swap_rule) }
+        if (gameFromName(cfg_.env_game.c_str()) == kHex) { MZ_FIXED(env_hex_use_swap_rule) }
 #undef MZ_FIXED
         if (fixed) { setError("update_config: %s is fixed when the worker is created (restart the worker to change it)", fixed); return MZ_ERR_ARG; }
         cfg_ = nc;
@@ -2163,8 +2162,7 @@ mz_env* mz_env_create(const char* conf)
     mz::WorkerConfig c;
     if (!conf || !c.loadFromString(conf)) { return nullptr; }
     std::unique_ptr<mz_env> e(new mz_env());
-    e->e = mz::createGameEnv(c.env_game, c.env_board_size, c.env_go_komi, c.env_atari_name, c.env_atari_episode_length, c.env_go_ko_rule, 108001,
-                             c.env_gomoku_rule, c.env_gomoku_exactly_five_stones, c.env_hex_use_swap_rule);
+    e->e = mz::createGameEnv(mz::envOptions(c, 108001));
     if (!e->e) { return nullptr; }
     return e.release();
 }
@@ -2228,7 +2226,12 @@ int mz_envdev_playout(int device, const char* game, int board_size, float komi, 
     if (mz_device_count() < 1) { setError("mz_envdev_playout: no GPU (libmzgpu has no CPU path)"); return MZ_ERR_DEVICE; }
     if (!actions || !rots || count < 0 || root_prefix < 0 || root_prefix > count) { setError("mz_envdev_playout: bad arguments"); return MZ_ERR_ARG; }
     const bool situational = std::string(game) == "go_situational"; // test access to env_go_ko_rule=situational
-    std::unique_ptr<GameEnv> env = createGameEnv(situational ? "go" : game, board_size, komi, "ms_pacman", 1000, situational ? "situational" : "positional");
+    EnvOptions o;
+    o.game = situational ? "go" : game;
+    o.board_size = board_size;
+    o.go_komi = komi;
+    o.go_ko_rule = situational ? "situational" : "positional";
+    std::unique_ptr<GameEnv> env = createGameEnv(o);
     return envdevPlayout(device, env.get(), komi, actions, count, root_prefix, rots, feat_out, legal_out, terminal_out, eval_out, player_out);
 }
 
@@ -2240,8 +2243,7 @@ int mz_envdev_playout_conf(int device, const char* conf, const int* actions, int
     if (!conf || !c.loadFromString(conf)) { return MZ_ERR_ARG; }
     if (mz_device_count() < 1) { setError("mz_envdev_playout_conf: no GPU (libmzgpu has no CPU path)"); return MZ_ERR_DEVICE; }
     if (!actions || !rots || count < 0 || root_prefix < 0 || root_prefix > count) { setError("mz_envdev_playout_conf: bad arguments"); return MZ_ERR_ARG; }
-    std::unique_ptr<GameEnv> env = createGameEnv(c.env_game, c.env_board_size, c.env_go_komi, c.env_atari_name, c.env_atari_episode_length, c.env_go_ko_rule, 1,
-                                                 c.env_gomoku_rule, c.env_gomoku_exactly_five_stones, c.env_hex_use_swap_rule);
+    std::unique_ptr<GameEnv> env = createGameEnv(envOptions(c, 1));
     return envdevPlayout(device, env.get(), c.env_go_komi, actions, count, root_prefix, rots, feat_out, legal_out, terminal_out, eval_out, player_out);
 }
 

@@ -12,6 +12,7 @@
 //   host_check fuzz-config <iters> <seed>    byte mutations of configuration strings through WorkerConfig::loadFromString
 //   host_check fuzz-gz <iters> <seed>        compressToHex of random buffers (sizes 0 .. 200 KB)
 //   host_check fuzz-env <game> <size> <iters> <seed>   random legal / illegal actions, string actions and resets through the host rules engines
+//   host_check games                         every row of the game table (game_kind.h) against the host engine it describes, at the smallest, default and largest board
 #include "../../include/mzgpu.h"
 #include "../../minizero_amd/csrc/config.h"
 #include "../../minizero_amd/csrc/env.h"
@@ -255,7 +256,13 @@ static int fuzzGz(int iters, unsigned seed)
 
 static int fuzzEnv(const char* game, int size, int iters, unsigned seed)
 {
-    std::unique_ptr<mz::GameEnv> e = mz::createGameEnv(game, size, 7.0f, "ms_pacman", 30, "positional", 1);
+    mz::EnvOptions o;
+    o.game = game;
+    o.board_size = size;
+    o.go_komi = 7.0f;
+    o.atari_episode_length = 30;
+    o.atari_recent_observations = 1;
+    std::unique_ptr<mz::GameEnv> e = mz::createGameEnv(o);
     if (!e) { fprintf(stderr, "fuzz-env: %s\n", mz_last_error()); return 1; }
     std::mt19937 rng(seed);
     std::vector<uint8_t> legal(static_cast<size_t>(e->policySize()));
@@ -279,6 +286,64 @@ static int fuzzEnv(const char* game, int size, int iters, unsigned seed)
     return 0;
 }
 
+// ---- the game table: what game_kind.h says about a game is what its host engine says, and the kernels' rules arguments keep their values ----
+static int gamesMain()
+{
+#define GAMES_CHECK(cond) \
+    if (!(cond)) { fprintf(stderr, "games: %s %dx%d: %s\n", mz::gameName(k), n, n, #cond); return 1; }
+    int engines = 0;
+    for (int row = 0; row < mz::kNumGameKinds; ++row) {
+        const mz::GameKind k = static_cast<mz::GameKind>(row);
+        if (mz::gameFromName(mz::gameName(k)) != k) { fprintf(stderr, "games: row %d is not found by its name\n", row); return 1; }
+        const int sizes[3] = {mz::gameMinBoard(k), mz::gameDefaultBoard(k), mz::gameMaxBoard(k)};
+        for (int n : sizes) {
+            mz::EnvOptions o;
+            o.game = mz::gameName(k);
+            o.board_size = n;
+            std::unique_ptr<mz::GameEnv> e = mz::createGameEnv(o);
+            if (!e) { fprintf(stderr, "games: %s %dx%d: %s\n", mz::gameName(k), n, n, mz_last_error()); return 1; }
+            const int P = n * n;
+            GAMES_CHECK(e->boardSize() == n)
+            GAMES_CHECK(e->policySize() == P + (mz::gameHasPass(k) ? 1 : 0))
+            GAMES_CHECK(e->numInputChannels() == mz::gameChannels(k))
+            GAMES_CHECK(e->deviceKind() == k && e->hasDeviceTwin())
+            int want = 0; // the literal values: they are part of the kernels' names
+            switch (row) {
+            case 0: want = (P + 63) / 64; break; // Go: words per plane
+            case 1: want = 0; break;             // Othello
+            case 2: want = -1; break;            // TicTacToe
+            case 3: want = -2; break;            // Gomoku
+            default: want = -3; break;           // Hex
+            }
+            GAMES_CHECK(mz::rulesArg(k, n) == want)
+            ++engines;
+        }
+        { // board 0 = the default
+            const int n = 0;
+            mz::EnvOptions o;
+            o.game = mz::gameName(k);
+            std::unique_ptr<mz::GameEnv> e = mz::createGameEnv(o);
+            GAMES_CHECK(e && e->boardSize() == mz::gameDefaultBoard(k))
+        }
+    }
+#undef GAMES_CHECK
+    if (mz::gameHasPass(mz::kGo) != true || mz::gameHasPass(mz::kOthello) != true || mz::gameHasPass(mz::kTicTacToe) || mz::gameHasPass(mz::kGomoku) || mz::gameHasPass(mz::kHex) ||
+        mz::gameChannels(mz::kGo) != 18 || mz::gameChannels(mz::kOthello) != 4 || mz::gameMaxBoard(mz::kOthello) != 8 || mz::gameMaxBoard(mz::kTicTacToe) != 3 ||
+        mz::gameMaxBoard(mz::kGo) != 19 || mz::gameMaxBoard(mz::kGomoku) != 19 || mz::gameMaxBoard(mz::kHex) != 19) {
+        fprintf(stderr, "games: a fact of the table changed\n");
+        return 1;
+    }
+    mz::EnvOptions o;
+    o.game = "atari";
+    std::unique_ptr<mz::GameEnv> atari = mz::createGameEnv(o);
+    if (!atari || atari->deviceKind() != mz::kNoDeviceGame || atari->hasDeviceTwin() || mz::gameFromName("atari") != mz::kNoDeviceGame) {
+        fprintf(stderr, "games: the Atari-shaped engine reports a device game\n");
+        return 1;
+    }
+    printf("games ok: %d engines of %d games\n", engines, mz::kNumGameKinds);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     const std::string cmd = argc > 1 ? argv[1] : "";
@@ -289,6 +354,7 @@ int main(int argc, char** argv)
     if (cmd == "fuzz-loader" && argc == 6) { return fuzzLoader(argv[2], argv[3], atoi(argv[4]), static_cast<unsigned>(atoi(argv[5]))); }
     if (cmd == "fuzz-config" && argc == 4) { return fuzzConfig(atoi(argv[2]), static_cast<unsigned>(atoi(argv[3]))); }
     if (cmd == "fuzz-gz" && argc == 4) { return fuzzGz(atoi(argv[2]), static_cast<unsigned>(atoi(argv[3]))); }
+    if (cmd == "games" && argc == 2) { return gamesMain(); }
     if (cmd == "fuzz-env" && argc == 6) { return fuzzEnv(argv[2], atoi(argv[3]), atoi(argv[4]), static_cast<unsigned>(atoi(argv[5]))); }
     fprintf(stderr, "usage: see the header comment of tests/csrc/host_check.cpp\n");
     return 2;

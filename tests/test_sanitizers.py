@@ -149,6 +149,12 @@ def test_parsers_under_asan_ubsan(mz, oracle, binaries, tmp_path):
         assert "fuzz-env ok" in run(b, "fuzz-env", game, size, 20000 if game != "atari" else 300, 6)
 
 
+def test_game_table_matches_the_host_engines(binaries):
+    """every row of minizero_amd/csrc/game_kind.h against the engine it describes (smallest, default, largest board): policy size, planes, device kind, the
+    literal rules arguments of the kernels; the Atari-shaped engine reports no device game"""
+    assert "games ok: 15 engines of 5 games" in run(binaries["asan"], "games")
+
+
 @pytest.mark.parametrize("seed", range(10))
 def test_random_iteration_schedules_on_the_host_half(oracle, binaries, seed):
     """tests/test_gpu_iteration.py::test_random_iteration_schedules without a GPU: random protocol lines (stop / start, live update_config keys, load_model of

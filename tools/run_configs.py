@@ -87,8 +87,8 @@ WARM.update({"w9x128": 1, "w9x256": 1, "w19x64": 1, "c5x512": 14, "l19x128": 1, 
 KERNEL.update({"w9x128mz": "sim_kernel_mz_wide<9,9,32,144,128>", "w9x128": "sim_kernel_wide<9,9,32,128,2>", "w9x256": "sim_kernel_wide<9,9,32,256,2>", "w19x64": "sim_kernel_wide<19,19,32,64,6>",
                "w8x256oth": "sim_kernel_wide<8,8,16,256,0>", "w3x256ttt": "sim_kernel_wide<3,3,16,256,-1>",
                "l19x128": "conv3x3_band (lock-step worker: per-layer kernels)", "l13x96": "conv3x3_band (lock-step worker: per-layer kernels)",
-               "g15x64": "sim_kernel_wide<15,15,16,64,-2>", "g15x256": "conv3x3_band (lock-step worker: per-layer kernels, device rules gmk_leaf_kernel)",
-               "h11x64": "sim_kernel_wide<11,11,16,64,-3>", "h11x256": "conv3x3_band (lock-step worker: per-layer kernels, device rules hex_leaf_kernel)"})
+               "g15x64": "sim_kernel_wide<15,15,16,64,-2>", "g15x256": "conv3x3_band (lock-step worker: per-layer kernels, device rules leaf_kernel<-2>)",
+               "h11x64": "sim_kernel_wide<11,11,16,64,-3>", "h11x256": "conv3x3_band (lock-step worker: per-layer kernels, device rules leaf_kernel<-3>)"})
 
 
 def _by_kernel(s0, s1, launches):

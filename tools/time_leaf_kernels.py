@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Stand-alone cost of a device rules body per leaf: plays `moves` moves of 256 games in the lock-step mode (mz_sim_kernel=false), where every cycle is one launch of
-the game's leaf kernel (one wave per leaf: hex_leaf_kernel, gmk_leaf_kernel), so that a kernel trace of the run holds one duration per cycle, in playing order.
+the game's leaf kernel (one wave per leaf: leaf_kernel<-3> for Hex, leaf_kernel<-2> for Gomoku — go_dev.hip leaf_kernel<rules argument>), so that a kernel trace of the run holds one duration per cycle, in playing order.
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/time_leaf_kernels.py run hex 100
-    python tools/time_leaf_kernels.py report DIR hex_leaf_kernel
+    python tools/time_leaf_kernels.py report DIR 'leaf_kernel<-3>'
 `report` splits the launches of the named kernel into the first, middle and last third of the run (early, middle and late positions) and prints the median and the
 mean duration of each."""
 import csv
