@@ -168,9 +168,21 @@ constexpr int kSpecWords = kSpecHelp + kHelpSegs * kHelpSeg;    // the paths + [
 constexpr int kSpecNode = 4, kSpecFc = 4 + kSpecCap, kSpecNc = 4 + 2 * kSpecCap;
 struct SpecMem { LdsI32* w; LdsCFloat* bias; LdsCDbl* sqrt; }; // w == nullptr: no speculation
 
+// The walk beside the previous simulation's expand (JOIN, the value-first order of sim_az_body.h): the backup is done, the expand may still run.  Of what the walk
+// reads, the expand only writes the second half of the record of ITS leaf (first_child, num_children, players) and the children behind it, so the walk waits where it
+// arrives at that node — whatever header it has seen of it — until `word` holds `want` (the expand's serial number), and reads the record again.  stats: [0] walks
+// that arrived there, [1] those that had to wait, [2] their 100-MHz ticks.  The wait is bounded; `code` goes to the pool's error flag.
+struct SelectJoin {
+    LdsI32* word;
+    LdsI32* stats;
+    int want, leaf, poll_limit, code;
+    int* err;
+};
+
 // serial > 0: helper waves run selectSpecHelper(serial) beside this walk (the per-game simulation kernels): their blocks are taken over where they fit
-template <bool SPEC = false, class RcpPtr>
-__device__ __forceinline__ void selectBody(const PoolView& v, const int* __restrict__ start, int g, int lane, RcpPtr rcp, SpecMem sm = SpecMem{nullptr, nullptr, nullptr}, int serial = 0)
+template <bool SPEC = false, bool JOIN = false, class RcpPtr>
+__device__ __forceinline__ void selectBody(const PoolView& v, const int* __restrict__ start, int g, int lane, RcpPtr rcp, SpecMem sm = SpecMem{nullptr, nullptr, nullptr}, int serial = 0,
+                                           SelectJoin join = SelectJoin{nullptr, nullptr, 0, -1, 0, 0, nullptr})
 {
     GNodeRec* recs = (GNodeRec*)(v.rec + size_t(g) * v.cap);
     // (generic pointers: the simulation kernel keeps the path of its game in LDS and points the view there)
@@ -241,6 +253,31 @@ __device__ __forceinline__ void selectBody(const PoolView& v, const int* __restr
         cur.players = __builtin_amdgcn_readfirstlane(cur.players);
         depth = __builtin_amdgcn_readfirstlane(depth);
         node = __builtin_amdgcn_readfirstlane(node);
+        if constexpr (JOIN) {
+            if (node == join.leaf) { // the previous simulation's leaf: its children exist once the expand has published its serial number
+                join.leaf = -1;
+                int seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(join.word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                if (seen < join.want) {
+                    const unsigned long long tw = wall_clock64();
+                    for (int i = 0; i < join.poll_limit && seen < join.want; ++i) {
+                        __builtin_amdgcn_s_sleep(1);
+                        seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(join.word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+                    }
+                    if (lane == 0) {
+                        if (seen < join.want) { atomicExch(join.err, join.code); }
+                        join.stats[1] += 1;
+                        join.stats[2] += static_cast<int>(wall_clock64() - tw);
+                    }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+                if (lane == 0) { join.stats[0] += 1; }
+                cur = uniformRec(loadRec(recs + node));
+                if (SPEC && spec && lane == 0 && depth - 1 < kSpecCap) { // (the level was remembered with the header of an unexpanded node)
+                    spec[kSpecFc + depth - 1] = cur.first_child;
+                    spec[kSpecNc + depth - 1] = cur.num_children;
+                }
+            }
+        }
         if (!(cur.num_children != 0 && depth < max_depth)) { break; }
         const int nc = cur.num_children, fc = cur.first_child, cplayer = (cur.players >> 8) & 0xFF;
         const int N = static_cast<int>(cur.count - 1);

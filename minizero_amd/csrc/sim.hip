@@ -589,6 +589,10 @@ void Net::dumpSimProf()
         fprintf(stderr, "[mz sim prof] terminal leaves: network skipped in %.0f of %.0f simulations (%.2f %%; the game with the most: %.2f %%) -> per simulation that ran them: tower %.2f us, heads %.2f us\n",
                 skipped, sims_all, 100.0 * skipped / std::max(1.0, sims_all), 100.0 * skipped_max, tw / ran * 0.01, hd / ran * 0.01);
     }
+    // the value-first order of sim_kernel (sim_az_body.h): what the walk beside the previous simulation's expand met
+    fprintf(stderr, "[mz sim prof] value first: %llu of %.0f simulations in the new order; %llu walks arrived at the previous simulation's leaf, %llu waited there (avg %.2f us); "
+                    "%llu waits at the join in front of the leaf\n",
+            tail[16], sims_all, tail[17], tail[18], double(tail[19]) / std::max(1.0, double(tail[18])) * 0.01, tail[20]);
     if (tail[8] > 0) {
         const double L = double(tail[8]), first = double(tail[9]) / L * 0.01, last = double(tail[10]) / L * 0.01, mean = double(tail[11]) / L * 0.01;
         const double helping = double(tail[12]) / L * 0.01; // a CU that helps another game's tower is busy

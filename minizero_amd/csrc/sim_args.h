@@ -43,7 +43,8 @@ struct SimArgs {
     AtariHeadParams ahp;
     float* reward;                    // [games] reward head output (game scale)
     int no_spec;                      // MZ_NO_SPEC bits (experiments, tests): 1 path speculation of the walk off, 2 helper waves off, 4 fault injection (sim_cluster.h),
-                                      // 8 the Go leaf in one piece, 16 the network also runs at terminal leaves (sim_kernel), 32 no tail help (sim_help.h)
+                                      // 8 the Go leaf in one piece, 16 the network also runs at terminal leaves (sim_kernel), 32 no tail help (sim_help.h),
+                                      // 64 no value-first order: candidates + expand + backup of a simulation in front of the next walk (sim_az_body.h simWalkVf)
     int cand_coop;                    // the candidate rank sort is shared by the 8 waves (its scratch fits the tower tiles)
     // opt-in bf16x3 tower (net_bf16_body.h): fragments + layer table; used by the BF instantiations of sim_kernel
     const uint4* wfrag;

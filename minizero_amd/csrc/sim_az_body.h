@@ -250,6 +250,8 @@ __device__ __noinline__ void simBackupOnly(CSimArgs* __restrict__ a, int slot, i
     expandBackupBody(pv, nullptr, nullptr, nullptr, nullptr, nullptr, sc + 8 - g, sc + 9 - g, slot, a->err, g, lane, tiles, 2);
 }
 
+// (simCandPipeVf below repeats these steps — scatter, azCandStore, expand — with its own path view: a change here belongs there too.  It does not call this
+//  function because a second set of constant arguments would change how the shared bodies are compiled for every caller.)
 template <int WPE>
 __device__ __forceinline__ void simCandExpandImpl(CSimArgs* __restrict__ a, int rot, int slot, int g, int lane, float* tiles, float* xchg, int part)
 {
@@ -290,6 +292,129 @@ template <int WPE>
 __device__ __noinline__ void simCandExpand(CSimArgs* __restrict__ a, int rot, int slot, int g, int lane, float* tiles, float* xchg, int part)
 {
     simCandExpandImpl<WPE>(a, rot, slot, g, lane, tiles, xchg, part);
+}
+
+// ---- The value-first order (the instance with tail help and the split Go leaf; no Gumbel, no value rescaling; MZ_NO_SPEC=64: off) ----
+// Behind the heads the next walk only needs the backup, and the backup only needs the value: wave 0 backs up at once and walks simulation s + 1, waves 1 .. 3 run
+// their helper segments behind the backup, and waves 4 .. 7 — which have no part in the walk — run candidates + expand of simulation s beside it (wave 4 in wave
+// 0's role, the rank sort on the four of them).  The waves meet through LDS words that carry the simulation's serial number s + 1: monotonic, never reset inside a
+// launch, written behind a workgroup-scope release fence and read in front of an acquire fence (as waveSync() does), s_sleep between two polls, every poll loop
+// bounded (error flag 97).  All eight waves of the workgroup are resident, so no wave waits for one that is not running.
+constexpr int kVfBackup = 4;  // serial of the last backup that is done (wave 0 -> the helper segments of waves 1 .. 3)
+constexpr int kVfLeaf = 5;    // the leaf of the simulation the candidate pipeline works on, handed over before the next walk overwrites the path block; [6] = 1
+constexpr int kVfGather = 7;  // serial of the last gather that is done (wave 4 -> waves 5 .. 7)
+constexpr int kVfRank = 8;    // rank parts of waves 5 .. 7 done so far: 3 per simulation
+constexpr int kVfExpand = 9;  // serial of the last expand that is done (wave 4 -> wave 0: the joins)
+constexpr int kVfStats = 10;  // (MZ_SIM_PROF) walks that arrived at the previous leaf, those that waited there, their ticks, waits at the join in front of the leaf
+constexpr int kVfWords = 16;
+constexpr int kVfErr = 97;
+
+__device__ __forceinline__ bool vfWait(LdsI32* w, int want, int* err, int lane)
+{
+    int seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    const bool waited = seen < want;
+    for (int i = 0; i < kHpPollLimit && seen < want; ++i) {
+        __builtin_amdgcn_s_sleep(1);
+        seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    }
+    if (seen < want && lane == 0) { atomicExch(err, kVfErr); }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    return waited;
+}
+// (every store of the wave so far is visible to the workgroup before the word is)
+__device__ __forceinline__ void vfPublish(LdsI32* w, int serial, int lane)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) { __hip_atomic_store(w, serial, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+}
+
+// the walk alone (wave 0; the backup of the simulation before it is done): `join_leaf` >= 0 = the leaf of that simulation, whose expand may still be running
+template <class RcpPtr>
+__device__ __noinline__ void simWalkVf(CSimArgs* __restrict__ a, int g, int lane, RcpPtr rcp, SpecMem spec, float* xchg, int serial, int join_leaf, int join_want, int* vf_)
+{
+    serial = __builtin_amdgcn_readfirstlane(serial);
+    g = __builtin_amdgcn_readfirstlane(g);
+    join_leaf = __builtin_amdgcn_readfirstlane(join_leaf);
+    join_want = __builtin_amdgcn_readfirstlane(join_want);
+    LdsI32* vf = (LdsI32*)vf_;
+    unsigned long long t0 = 0;
+    if (a->prof) { t0 = wall_clock64(); }
+    const PoolView pv = simPathView(ldc(&a->pv), reinterpret_cast<int*>(xchg) - 2 * a->pv.max_depth - 2, g);
+    selectBody<true, true>(pv, nullptr, g, lane, rcp, spec, serial, SelectJoin{vf + kVfExpand, vf + kVfStats, join_want, join_leaf, kHpPollLimit, kVfErr, a->err});
+    waveSync();
+    if (a->prof && lane == 0) {
+        a->prof[size_t(g) * 8 + 5] += wall_clock64() - t0;
+        a->prof[size_t(g) * 8 + 6] += pv.path_len[g];
+    }
+}
+
+// the leaf's first half (wave 0, behind the join with the expand of the simulation before), and the hand-over of the leaf node to the candidate pipeline
+template <int CPL>
+__device__ __noinline__ void simLeafVf(CSimArgs* __restrict__ a, int rot, int slot, int g, int lane, float* xchg, const uint64_t* seen_lds, uint64_t* leaf_smem, int* vf)
+{
+    g = __builtin_amdgcn_readfirstlane(g);
+    slot = __builtin_amdgcn_readfirstlane(slot);
+    rot = __builtin_amdgcn_readfirstlane(rot);
+    if constexpr (CPL > 0) {
+        const PoolView pv = simPathView(ldc(&a->pv), reinterpret_cast<int*>(xchg) - 2 * a->pv.max_depth - 2, g);
+        const GoDevView gv = simLeafView(ldc(&a->gv), xchg, g);
+        if (lane == 0) {
+            const int len = pv.path_len[g];
+            vf[kVfLeaf] = len > 0 ? (pv.path + size_t(g) * pv.max_depth)[len - 1] : 0;
+            vf[kVfLeaf + 1] = len > 0 ? 1 : 0;
+        }
+        leafBody<CPL, true, 1>(gv, pv, rot, slot, g, lane, leaf_smem, seen_lds);
+    }
+}
+
+// candidates + expand of simulation `serial - 1` on waves 4 .. 7 (w = wave - 4), beside wave 0's backup and next walk
+template <int WPE>
+__device__ __noinline__ void simCandPipeVf(CSimArgs* __restrict__ a, int rot, int slot, int g, int lane, int w, int serial, float* tiles, float* xchg, int* vf_)
+{
+    g = __builtin_amdgcn_readfirstlane(g);
+    w = __builtin_amdgcn_readfirstlane(w);
+    serial = __builtin_amdgcn_readfirstlane(serial);
+    LdsI32* vf = (LdsI32*)vf_;
+    const int A = a->gv.A;
+    const SimXchg x{A + (A & 1)};
+    if (w == 0) {
+        simCandGatherImpl<WPE>(a, rot, g, lane, tiles, xchg);
+        vfPublish(vf + kVfGather, serial, lane);
+    } else {
+        vfWait(vf + kVfGather, serial, a->err, lane);
+    }
+    const int k = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int*>(xchg + x.scalars())[1]);
+    float* dense = simCandDense(tiles, A);
+    if (k > 0 && k <= kCandCoopMax && a->cand_coop) { // two of the eight shares per wave (otherwise wave 4 has sorted alone in the gather)
+        candRankPart(dense, k, w, 8, lane, reinterpret_cast<int*>(dense + kCandCoopMax));
+        candRankPart(dense, k, w + 4, 8, lane, reinterpret_cast<int*>(dense + kCandCoopMax));
+    }
+    if (w != 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) { __hip_atomic_fetch_add(vf + kVfRank, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+        return;
+    }
+    vfWait(vf + kVfRank, 3 * serial, a->err, lane);
+    // scatter, the sorted candidates where the expand reads them, the expand (simCandExpandImpl's steps; the path of the expand is the one node of kVfLeaf)
+    slot = __builtin_amdgcn_readfirstlane(slot);
+    const GoDevView gv = simLeafView(ldc(&a->gv), xchg, g);
+    PoolView pv = simPathView(ldc(&a->pv), reinterpret_cast<int*>(xchg) - 2 * a->pv.max_depth - 2, g);
+    pv.path = vf_ + kVfLeaf - size_t(g) * pv.max_depth;
+    pv.path_len = vf_ + kVfLeaf + 1 - g;
+    const size_t ga = size_t(g) * gv.A;
+    float* sc = xchg + x.scalars();
+    int* cand_count = reinterpret_cast<int*>(sc + 1) - g;
+    int* cand_player = reinterpret_cast<int*>(sc + 2) - g;
+    int* cand_action = reinterpret_cast<int*>(xchg + x.caction()) - ga;
+    Cand* cs = reinterpret_cast<Cand*>(tiles);
+    Cand* out = cs + gv.A;
+    if (k > 0 && k <= kCandCoopMax && a->cand_coop) { candScatter(cs, out, reinterpret_cast<int*>(out + gv.A), k, 8, lane, reinterpret_cast<const int*>(dense + kCandCoopMax), a->err); }
+    azCandStore(gv, sc - g, out, k, cand_count, cand_action, xchg + x.cpolicy() - ga, xchg + x.clogit() - ga, cand_player, sc + 3 - g, sc + 4 - g, g, lane);
+    waveSync();
+    expandBackupBody(pv, cand_count, cand_action, xchg + x.cpolicy() - ga, xchg + x.clogit() - ga, cand_player, sc + 3 - g, sc + 4 - g, slot, a->err, g, lane, tiles, 1);
+    vfPublish(vf + kVfExpand, serial, lane);
 }
 
 // Root exploration noise (ref zero_actor.cpp:194-213): policy = (1 - eps) * policy + eps * noise for the root's children, in storage
@@ -369,7 +494,7 @@ __device__ __forceinline__ bool simLeafTerminal(CSimArgs* __restrict__ a, const 
 
 // MZ_SIM_PROF: the words behind the per-game counters (kSimProfTail of them).  [0..3] belong to the launch that is running — earliest start, first and last exit
 // of a game (100-MHz ticks from [4], the stamp of the previous fold), sum of the exits; sim_prof_fold (sim.hip) adds them to [8..] between two launches.
-constexpr int kSimProfTail = 16;
+constexpr int kSimProfTail = 24; // ([16..20]: the value-first order: simulations, walks that arrived at the previous leaf, waits there, their ticks, waits in front of the leaf)
 __device__ __forceinline__ void simProfEnter(unsigned long long* tail)
 {
     atomicMin(tail + 0, wall_clock64() - tail[4]);
@@ -584,19 +709,51 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     // Tail help (sim_help.h; bit 1 of host_start: this launch helps): the game publishes the XCD it runs on — from here on it can be claimed by a workgroup of
     // that XCD whose own game is done.  s_help: [0] abort flag of the exchanges, [1] the game's helper (0: none) as of this simulation, [2] the helper's scratch.
     constexpr bool kHelp = !BF && WPE == 2 && CPL > 0 && pairTowerShape<H, W, CPAD>();
-    __shared__ int s_help[4];
+    __shared__ int s_help[kHelp ? kVfWords : 4]; // (+ the words of the value-first order: kVfBackup ..)
     const bool help_on = kHelp && (host_start & 2) != 0;
     unsigned* const help_blk = help_on ? a->help + size_t(g) * a->help_words : nullptr;
     unsigned help_xseq = 0;                        // layer exchanges of this game's pair towers so far
     unsigned long long pair_n = 0, pair_t = 0;     // (MZ_SIM_PROF) simulations that ran a pair tower, their tower ticks
     if (help_on && tid == 0) { s_help[0] = 0; s_help[1] = 0; hpStoreU(help_blk + kHpXcc, hpXccId()); }
+    // The value-first order (simWalkVf .. simCandPipeVf above): the same for every simulation of the launch and for every wave, so each wave passes the same barriers
+    bool vf = false;
+    if constexpr (kHelp) {
+        vf = leaf_smem != nullptr && !a->use_gumbel && !a->pv.value_rescale && a->cand_coop != 2 && !(a->no_spec & 64); // (MZ_NO_SPEC=64: the order of the other instances;
+                                                                                                                         //  cand_coop 2 is the wide boards' sort, which simCandPipeVf does not have: never set for this instance's 82 actions)
+        if (tid >= kVfBackup && tid < kVfWords) { s_help[tid] = 0; }
+    }
+    unsigned long long vf_t0 = 0, vf_n = 0; // (MZ_SIM_PROF) the start of the walk that ran in the iteration before, simulations in the new order
     __syncthreads();
     for (int s = 0; s < nsims; ++s) {
         const int slot = sim0 + s; // simulation index within the move = position slot of its leaf
         const int rot = rot_tab[size_t(s) * games + g];
         unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
-        if (prof) { t0 = wall_clock64(); }
-        if (wave == 0) {
+        if (prof) { t0 = (vf && s > 0) ? vf_t0 : wall_clock64(); }
+        if (kHelp && vf) {
+            if constexpr (kHelp) {
+                if (wave == 0) {
+                    if (s == 0) { // (the first walk of the launch; every later one ran behind the backup of the simulation before it)
+                        if (slot == 1 && a->root_noise) { simApplyRootNoise<WPE>(a, g, lane); }
+                        simWalkVf(a, g, lane, rcp_lds, spec, xchg, (a->no_spec & 2) ? 0 : 1, -1, 0, s_help);
+                    } else {
+                        // the join in front of the leaf: leafBody writes the hand-over block the candidate pipeline reads, and the node count is the expand's
+                        const bool waited = vfWait((LdsI32*)s_help + kVfExpand, s, a->err, lane);
+                        if (prof && waited && lane == 0) { s_help[kVfStats + 3] += 1; }
+                        // (behind the expand of simulation s - 1, i.e. up to one walk later than in the old order, which publishes at the end of iteration s - 1: a finished
+                        //  CU that looks for the game with the least progress sees this game one simulation behind for that long; the protocol only needs progress < the next
+                        //  command's sequence number s + 1)
+                        if (help_on && lane == 0) { hpStoreU(help_blk + kHpProgress, unsigned(s)); }
+                    }
+                    simLeafVf<CPL>(a, rot, slot, g, lane, xchg, seen_lds, leaf_smem, s_help);
+                } else if (s == 0 && wave <= kHelpSegs && spec.w && !(a->no_spec & 2)) {
+                    simSelectHelper(a, g, lane, wave, 1, rcp_lds, spec);
+                } else if (help_on && tid == 7 * 64) {
+                    // (wave 7 arrives here behind its rank shares of simulation s - 1, not beside the walk as in the old order: a claim made during the walk of s is
+                    //  picked up one simulation later)
+                    s_help[1] = int(hpLoadU(help_blk + kHpHelper));
+                }
+            }
+        } else if (wave == 0) {
             if (slot == 1 && a->root_noise) { simApplyRootNoise<WPE>(a, g, lane); }
             if (a->use_gumbel) { simGumbelStart<WPE>(a, slot, s == 0 && (host_start & 1) != 0, g, lane, tiles); }
             simSelectLeaf<CPL, WPE>(a, rot, slot, g, lane, tiles, rcp_lds, spec, xchg, seen_lds, (a->no_spec & 2) ? 0 : s + 1, leaf_smem);
@@ -650,6 +807,39 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         else if (leaf_smem) { __syncthreads(); __syncthreads(); }
         __syncthreads();
         if (prof) { t3 = wall_clock64(); }
+        if (kHelp && vf) {
+            if constexpr (kHelp) {
+                // no barrier from here to the one behind the next leaf: the waves meet through the words of s_help
+                const bool more = s + 1 < nsims;
+                if (wave == 0) {
+                    simBackupOnly<WPE>(a, slot, g, lane, tiles, xchg);
+                    vfPublish((LdsI32*)s_help + kVfBackup, s + 1, lane);
+                    if (prof && tid == 0) {
+                        t4 = wall_clock64(); // ("cand+expand": what is exposed between the heads and the next walk)
+                        prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
+                        prof[4] += 1 + (static_cast<unsigned long long>(term) << 32);
+                        if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
+                        vf_n += 1;
+                    }
+                    vf_t0 = t4;
+                    if (more) {
+                        if (slot + 1 == 1 && a->root_noise) { // the noise re-orders the root's priors, which the expand of simulation 0 writes
+                            vfWait((LdsI32*)s_help + kVfExpand, s + 1, a->err, lane);
+                            simApplyRootNoise<WPE>(a, g, lane);
+                        }
+                        simWalkVf(a, g, lane, rcp_lds, spec, xchg, (a->no_spec & 2) ? 0 : s + 2, __builtin_amdgcn_readfirstlane(s_help[kVfLeaf]), s + 1, s_help);
+                    }
+                } else if (wave <= kHelpSegs) {
+                    if (more && spec.w && !(a->no_spec & 2)) { // (their blocks claim "with the records as they are": behind the backup)
+                        vfWait((LdsI32*)s_help + kVfBackup, s + 1, a->err, lane);
+                        simSelectHelper(a, g, lane, wave, s + 2, rcp_lds, spec);
+                    }
+                } else {
+                    simCandPipeVf<WPE>(a, rot, slot, g, lane, wave - 4, s + 1, tiles, xchg, s_help);
+                }
+            }
+            continue;
+        }
         if (wave == 0) { simCandGather<WPE>(a, rot, g, lane, tiles, xchg); }
         __syncthreads();
         {
@@ -672,6 +862,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
             if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
         }
         if (kHelp && help_on && tid == 0) { hpStoreU(help_blk + kHpProgress, unsigned(s) + 1u); } // (nsims: the game is done, its helper looks for another one)
+    }
+    if constexpr (kHelp) {
+        if (vf) { // the candidate pipeline of the last simulation: the node count and the progress word of the tail help are written behind its expand
+            __syncthreads();
+            if (help_on && tid == 0) { hpStoreU(help_blk + kHpProgress, unsigned(nsims)); }
+            if (prof && tid == 0) {
+                unsigned long long* ptail = a->prof + size_t(games) * 8;
+                atomicAdd(ptail + 16, vf_n);
+                for (int i = 0; i < 4; ++i) { atomicAdd(ptail + 17 + i, static_cast<unsigned long long>(s_help[kVfStats + i])); }
+            }
+        }
     }
     if (tid == 0) { a->pv.num_nodes[g] = *node_count; }
     if (prof && tid == 0) {
