@@ -337,6 +337,8 @@ int mz_env_name(const mz_env* e, char* out, int cap);
  * ref zero_actor.cpp:225-227) on the device, ties included: order_out[i] = index of the i-th.
  * mz_invert_values_device applies the 601-bin decode (ref utils/utils.h:102-108 invertValue) to n values with the device
  * function the simulation kernel uses for muzero_atari (mz_invert_value is the host function of the lock-step path).
+ * mz_exp_tanh_device evaluates the deterministic exp and tanh every head and every softmax of the kernels calls (DESIGN.md
+ * "Network numerics") on n values on the device: exp_out[i], tanh_out[i] of x[i].
  * ------------------------------------------------------------------------------------------ */
 int mz_godev_playout(int device, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots,
                      uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
@@ -348,6 +350,7 @@ int mz_envdev_playout_conf(int device, const char* conf, const int* actions, int
                            uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
 int mz_sort_candidates(int device, const float* policy, int n, int* order_out);
 int mz_invert_values_device(int device, const float* values, int n, float* out);
+int mz_exp_tanh_device(int device, const float* x, int n, float* exp_out, float* tanh_out);
 
 #ifdef __cplusplus
 }

@@ -404,6 +404,26 @@ int invertValuesOnDevice(int device, const float* values, int n, float* out)
     return MZ_OK;
 }
 
+__global__ void exp_tanh_kernel(const float* __restrict__ in, int n, float* __restrict__ exp_out, float* __restrict__ tanh_out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { exp_out[i] = mz_expf(in[i]); tanh_out[i] = mz_tanhf(in[i]); }
+}
+
+int expTanhOnDevice(int device, const float* x, int n, float* exp_out, float* tanh_out)
+{
+    if (n <= 0) { return MZ_OK; }
+    MZ_HIP(hipSetDevice(device));
+    DevBuf<float> d_in, d_exp, d_tanh;
+    if (!d_in.alloc(n) || !d_exp.alloc(n) || !d_tanh.alloc(n)) { setError("expTanhOnDevice: allocation failed"); return MZ_ERR_DEVICE; }
+    MZ_HIP(hipMemcpy(d_in.p, x, size_t(n) * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(exp_tanh_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, d_in.p, n, d_exp.p, d_tanh.p);
+    MZ_HIP(hipGetLastError());
+    MZ_HIP(hipMemcpy(exp_out, d_exp.p, size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    MZ_HIP(hipMemcpy(tanh_out, d_tanh.p, size_t(n) * sizeof(float), hipMemcpyDeviceToHost));
+    return MZ_OK;
+}
+
 // raw observations -> the network's float planes (ref atari.cpp:199-216 getFeatures: per history step one action plane, then R, G, B / 255):
 // `raw` per sample = hist screens oldest first (3 * res * res bytes each), hist f32 action-plane values, hist valid bytes (env.cpp rawFeatures).
 // Same values as the host's features() (one IEEE division per element); the point is the 4x smaller host-to-device copy per move.
@@ -481,3 +501,12 @@ int Net::expandAtariFeatures(const uint8_t* d_raw, int raw_bytes, int B, float* 
 }
 
 } // namespace mz
+
+// test access to mz_expf / mz_tanhf (include/mzgpu.h); defined here, beside the kernel, so that the host-only builds of the worker need nothing of it
+extern "C" int mz_exp_tanh_device(int device, const float* x, int n, float* exp_out, float* tanh_out)
+{
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count < 1) { mz::setError("mz_exp_tanh_device: no GPU (libmzgpu has no CPU path)"); return MZ_ERR_DEVICE; }
+    if (!x || !exp_out || !tanh_out || n < 0 || device < 0 || device >= count) { mz::setError("mz_exp_tanh_device: bad arguments"); return MZ_ERR_ARG; }
+    return mz::expTanhOnDevice(device, x, n, exp_out, tanh_out);
+}

@@ -166,6 +166,7 @@ def load():
         L.mz_envdev_playout_conf.argtypes = [C.c_int, C.c_char_p, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
         L.mz_sort_candidates.argtypes = [C.c_int, fp, C.c_int, ip]
         L.mz_invert_values_device.argtypes = [C.c_int, fp, C.c_int, fp]
+        L.mz_exp_tanh_device.argtypes = [C.c_int, fp, C.c_int, fp, fp]
     L.mz_loader_create.restype = vp
     L.mz_loader_create.argtypes = [C.c_int, C.c_char_p]
     L.mz_loader_destroy.argtypes = [vp]
@@ -667,6 +668,15 @@ def invert_values_device(values, device=0):
     out = np.zeros(len(v), np.float32)
     _check(L, L.mz_invert_values_device(device, _f(v), len(v), _f(out)))
     return out
+
+
+def exp_tanh_device(x, device=0):
+    """(exp, tanh) of every element by the device's deterministic mz_expf / mz_tanhf (net_dev.h), the two functions of every head and softmax."""
+    L = load()
+    v = np.ascontiguousarray(x, np.float32)
+    e, t = np.zeros(len(v), np.float32), np.zeros(len(v), np.float32)
+    _check(L, L.mz_exp_tanh_device(device, _f(v), len(v), _f(e), _f(t)))
+    return e, t
 
 
 def sort_candidates(policy, device=0):

@@ -76,7 +76,7 @@ private:
 
 float mz_expf(float x)
 {
-    if (x < -87.0f) { return 0.0f; }
+    if (x < -87.3365402f) { return 0.0f; } // the first float whose exp is a normal number (ln FLT_MIN = -87.33654475): below it the scale 2^n has no normal encoding
     if (x > 88.0f) { x = 88.0f; }
     float n = rintf(x * 1.44269504088896341f);
     float r = fmaf(n, -0.693359375f, x);

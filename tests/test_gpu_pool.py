@@ -25,7 +25,9 @@ def make_candidates(rng, A, allow_terminal, tie_prob):
     return actions[order], p[order], logits[order]
 
 
-def drive(mz, oracle, G, A, n, conf, pool_kw, seed, gumbel=False, use_reward=False, oracle_games=None, noise=True):
+def drive(mz, oracle, G, A, n, conf, pool_kw, seed, gumbel=False, use_reward=False, oracle_games=None, noise=True, values=None, candidates=None):
+    """values(rng, G) -> the G leaf values of one simulation, candidates(rng, A, allow_terminal) -> (actions, priors, logits) sorted by prior descending:
+    the defaults draw values uniformly from [-1, 1) and softmax rows with occasional ties (make_candidates).  The longest path is left in pool.longest_path."""
     rng = np.random.default_rng(seed)
     cap = 1 + (n + 1) * A
     pool = mz.Pool(G, cap, A, n, **pool_kw)
@@ -44,6 +46,7 @@ def drive(mz, oracle, G, A, n, conf, pool_kw, seed, gumbel=False, use_reward=Fal
             rr = pool.root_read()
             start = np.array([1 + int(rng.integers(0, rr["num_children"][g])) for g in range(G)], np.int32)
         plen, paths, pacts = pool.select(start)
+        pool.longest_path = max(getattr(pool, "longest_path", 0), int(plen.max()))
         for g in og:
             op = trees[g].select(-1 if start is None else int(start[g]))
             assert plen[g] == len(op) and np.array_equal(paths[g, :plen[g]], op), f"sim {sim} game {g}: path {paths[g, :plen[g]]} != {op}"
@@ -52,11 +55,11 @@ def drive(mz, oracle, G, A, n, conf, pool_kw, seed, gumbel=False, use_reward=Fal
         cp = np.zeros((G, A), np.float32)
         cl = np.zeros((G, A), np.float32)
         pl = np.zeros(G, np.int32)
-        val = rng.uniform(-1, 1, G).astype(np.float32)
+        val = rng.uniform(-1, 1, G).astype(np.float32) if values is None else np.ascontiguousarray(values(rng, G), np.float32)
         rew = (rng.uniform(0, 1, G) < 0.3).astype(np.float32) * rng.uniform(0, 2, G).astype(np.float32) if use_reward else np.zeros(G, np.float32)
         for g in range(G):
             leaf = int(paths[g, plen[g] - 1])
-            a, p, l = make_candidates(rng, A, allow_terminal=(sim > 0), tie_prob=0.3)
+            a, p, l = make_candidates(rng, A, allow_terminal=(sim > 0), tie_prob=0.3) if candidates is None else candidates(rng, A, sim > 0)
             k = len(a)
             cc[g] = k
             ca[g, :k], cp[g, :k], cl[g, :k] = a, p, l
@@ -148,6 +151,95 @@ def test_baseline_size_c2_properties(mz, oracle):
         k = rr["num_children"][g]
         assert rr["count"][g, :k].sum() == n  # every simulation after the root expansion went through exactly one root child
         assert pool.num_nodes(g) == nn[g]
+
+
+TINY_VALUES = np.array([0.0, -0.0, 1.0, -1.0, 1e-35, -1e-35, 1e-40, -1e-40, 1 - 2.0 ** -24], np.float32)
+
+
+def tiny_values(rng, G):
+    return TINY_VALUES[rng.integers(0, len(TINY_VALUES), G)]
+
+
+def sharp_candidates(rng, A, allow_terminal):
+    """Candidate rows as a trained network's softmax hands them over (sorted by prior descending): a few live priors over a tail of exact zeros, subnormal
+    priors, a lone 1.0 over zeros, all priors tied."""
+    if allow_terminal and rng.random() < 0.05:
+        return np.zeros(0, np.int32), np.zeros(0, np.float32), np.zeros(0, np.float32)
+    k = int(rng.integers(1, A + 1))
+    actions = rng.permutation(A)[:k].astype(np.int32)
+    kind = int(rng.integers(0, 4))
+    p = np.zeros(k, np.float32)
+    if kind == 0:    # live priors (with a tie) over exact zeros
+        m = min(k, int(rng.integers(1, 5)))
+        p[:m] = np.sort(rng.dirichlet(np.ones(m)).astype(np.float32))[::-1]
+        if m > 2:
+            p[2] = p[1]
+    elif kind == 1:  # subnormals, tied and distinct, over zeros
+        p[0] = 1.0
+        m = min(k, int(rng.integers(2, 9)))
+        p[1:m] = np.sort(rng.choice(np.array([1e-39, 1e-39, 5e-42, 1.4e-45, 1.1754942e-38], np.float32), m - 1))[::-1]
+    elif kind == 2:  # a lone 1.0
+        p[0] = 1.0
+    else:            # all tied
+        p[:] = np.float32(1.0) / np.float32(k)
+    with np.errstate(divide="ignore"):
+        logit = np.maximum(np.log(p.astype(np.float64)), -3e38).astype(np.float32)
+    assert np.all(p[:-1] >= p[1:])
+    return actions, p, logit
+
+
+def _tiny_branch_taken(trees):
+    """some visited child with 0 < |mean * count| < 2^-100: the level that evaluates it takes selectBody's real division (pool_body.h evalChild `tiny`)"""
+    hits = 0
+    for t in trees.values():
+        d = t.dump()
+        a = np.abs(d["mean"] * d["count"])[1:]
+        hits += int(((d["count"][1:] > 0) & (a > 0) & (a < np.float32(2.0 ** -100))).sum())
+    return hits
+
+
+@pytest.mark.parametrize("A", [82, 20])
+@pytest.mark.parametrize("variant", ["puct", "gumbel_start", "rescale_discount_initq"])
+def test_tiny_values_and_sharp_priors(mz, oracle, A, variant):
+    """Values from {+-0, +-1, +-1e-35, +-1e-40 (subnormal), 1 - 2^-24} and candidate rows of exact zeros, subnormals, a lone 1.0 and all-tied priors: products
+    mean * count below 2^-100 (the walk's reciprocal shortcut gives way to the real division), q of +0 and -0, scores that tie at exactly 0.0 (the tie-break is
+    higher prior, then lower index), saturated values in the value bounds.  No root noise, so that the root's own zeros and ties stay."""
+    n, G = 60, 16
+    if variant == "rescale_discount_initq":
+        conf = (f"actor_num_simulation={n}:actor_mcts_value_rescale=true:actor_mcts_reward_discount=0.997:atari_init_q=true:actor_mcts_value_flipping_player=W")
+        kw = dict(value_rescale=True, reward_discount=0.997, atari_init_q=True, flipping_player=2)
+    else:
+        conf, kw = f"actor_num_simulation={n}", {}
+    pool, trees, nn = drive(mz, oracle, G=G, A=A, n=n, conf=conf, pool_kw=kw, seed=20 + A, gumbel=(variant == "gumbel_start"),
+                            use_reward=(variant == "rescale_discount_initq"), noise=False, values=tiny_values, candidates=sharp_candidates)
+    compare_trees(pool, trees, nn)
+    hits = _tiny_branch_taken(trees)
+    print(f"{variant} A={A}: {hits} visited children with 0 < |mean * count| < 2^-100, longest path {pool.longest_path}")
+    assert hits > 0, "no child ever had a product below 2^-100: the branch under test never ran"
+    if variant == "rescale_discount_initq":
+        import ctypes as C
+        rr = pool.root_read()
+        for g, t in trees.items():
+            lo, hi = C.c_float(), C.c_float()
+            assert rr["bound_size"][g] == t.L.mzo_tree_value_bound(t.h, C.byref(lo), C.byref(hi))
+            assert np.float32(lo.value) == rr["bound_lo"][g] and np.float32(hi.value) == rr["bound_hi"][g]
+
+
+def test_one_line_deeper_than_the_remembered_levels(mz, oracle):
+    """One dominant prior and value 0 at every leaf: every simulation walks the same line and adds a level, so the path grows to n + 1 = 201 nodes, past the
+    128 levels a remembered path holds (pool_body.h kSpecCap)."""
+    n, G, A = 200, 4, 20
+
+    def chain(rng, A, allow_terminal):
+        p = np.full(A, 1e-6, np.float32)
+        p[0] = np.float32(1.0) - np.float32(19e-6)
+        return rng.permutation(A).astype(np.int32), p, np.log(p.astype(np.float64)).astype(np.float32)
+
+    pool, trees, nn = drive(mz, oracle, G=G, A=A, n=n, conf=f"actor_num_simulation={n}", pool_kw={}, seed=30, noise=False,
+                            values=lambda rng, G: np.zeros(G, np.float32), candidates=chain)
+    compare_trees(pool, trees, nn)
+    assert pool.longest_path > 128, pool.longest_path
+    assert np.all(pool.root_read()["root_count"] == n + 1)
 
 
 def test_capacity_and_argument_errors(mz):

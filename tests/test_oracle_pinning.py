@@ -103,6 +103,8 @@ def test_weight_generator_twins(oracle, mz):
 
 
 def test_deterministic_exp_tanh_accuracy(oracle):
+    """The range a softmax of ordinary logits uses.  tests/test_sharp_regime.py test_primitives_against_float64 checks the wider input set (every float around
+    the cut to 0 and around tanh's cut and saturation, the clamp at 88, subnormals, infinities), tests/test_gpu_sharp.py the device copy on the same set."""
     x = np.concatenate([np.linspace(-87, 0, 20001), np.linspace(0, 5, 2001)]).astype(np.float32)
     y = np.empty_like(x)
     oracle.lib().mzo_expf(oracle.fptr(x), x.size, oracle.fptr(y))
