@@ -339,6 +339,11 @@ int mz_env_name(const mz_env* e, char* out, int cap);
  * function the simulation kernel uses for muzero_atari (mz_invert_value is the host function of the lock-step path).
  * mz_exp_tanh_device evaluates the deterministic exp and tanh every head and every softmax of the kernels calls (DESIGN.md
  * "Network numerics") on n values on the device: exp_out[i], tanh_out[i] of x[i].
+ * mz_tail_towers_device runs the representation tower of a 9x9 x 64 network (18 bit-packed input planes, bits [towers][18 * 3]) for `towers`
+ * positions the way the tail help of the simulation kernel does: on members = 1 (solo), 2 (pair) or 4 (quad) workgroups of one XCD each (all
+ * towers * members workgroups must fit the device at once; members of tower t are the workgroups t, t + towers, ..).  out [towers][64][81] the
+ * last layer's activations, xcc_out [towers * members] XCC_ID + 1 of every workgroup, *err_flag_out the error flag of the exchanges (0: none),
+ * *status_out 0, or 1: the members of a tower do not share an XCD — found out before any member waits for another; no exchange is run then.
  * ------------------------------------------------------------------------------------------ */
 int mz_godev_playout(int device, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots,
                      uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
@@ -351,6 +356,7 @@ int mz_envdev_playout_conf(int device, const char* conf, const int* actions, int
 int mz_sort_candidates(int device, const float* policy, int n, int* order_out);
 int mz_invert_values_device(int device, const float* values, int n, float* out);
 int mz_exp_tanh_device(int device, const float* x, int n, float* exp_out, float* tanh_out);
+int mz_tail_towers_device(mz_net* net, const uint32_t* bits, int towers, int members, float* out, uint32_t* xcc_out, int* err_flag_out, int* status_out);
 
 #ifdef __cplusplus
 }

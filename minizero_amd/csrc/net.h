@@ -99,6 +99,9 @@ public:
     // tail help (sim_help.h): the caller has the GPU to itself and runs one simLaunch at a time — workgroups whose game is done may help the stragglers of their
     // XCD with their towers (only the 9x9 x 64 f32 instance, launches of at least kSimHelpMinLaunch simulations, one workgroup per CU at most)
     void allowTailHelp(bool on) { tail_help_ = on; }
+    // test access to the towers of the tail help (mz_tail_towers_device): `towers` towers of bit-packed planes (host) on `members` = 1, 2 or 4 workgroups each;
+    // out [towers][C][P], xcc [towers * members] XCC_ID + 1 of every workgroup, *err_flag the exchanges' error flag, *status 1: members on different XCDs (nothing exchanged)
+    int tailTowers(const unsigned* bits, int towers, int members, float* out, unsigned* xcc, int* err_flag, int* status);
     // num_simulation: the kernels keep per-search tables / the path in LDS; searches too long for 160 KB use the lock-step kernels
     bool hasSimKernel(int board_n, int env_kind = kGo, int num_simulation = 0) const; // env_kind: GameKind, as stored in GoDevView::kind
     // ... on the one-tile tower (sim_wide.inc, sim_wide_a.hip): Go with 128 / 256 hidden channels or on 7x7 / 13x13 / 19x19 boards

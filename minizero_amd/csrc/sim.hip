@@ -469,7 +469,8 @@ constexpr int kSimHelpMinLaunch = 64, kSimHelpMinLeft = 2;
 
 // MZ_SIM_PROF: between two launches (stream order), the running launch's words of the profile's tail (sim_az_body.h simProfEnter / simProfExit) are added to the
 // sums — [8] launches, [9] / [10] / [11] ticks from the earliest start of a game to the first exit, the last exit and the mean exit, [12] mean ticks per CU spent
-// helping another game behind that exit — and cleared for the next one.  ([13] simulations that ran a pair tower, [14] their tower ticks, [15] games helped: running sums.)
+// helping another game behind that exit, [30..32] idle behind the search for a game to help, by its outcome — and cleared for the next one.  ([13] simulations that ran a
+// pair tower, [14] their tower ticks, [15] games helped, [21..23] the same for quad towers: running sums.)
 __global__ void sim_prof_fold(unsigned long long* tail)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) { return; }
@@ -481,8 +482,13 @@ __global__ void sim_prof_fold(unsigned long long* tail)
         tail[10] += tail[2] - start;
         tail[11] += tail[3] / n - start;
         tail[12] += tail[6] / n; // tail help (sim_help.h): ticks per CU spent as a helper behind the own game's exit
+        for (int c = 0; c < 3; ++c) { // ... and idle from where it stopped looking to the last game's exit, by the reason it stopped (kSimProfTail)
+            const unsigned long long end = tail[24 + c] * tail[2];
+            tail[30 + c] += (end > tail[27 + c] ? end - tail[27 + c] : 0) / n;
+        }
     }
     tail[0] = ~0ull; tail[1] = ~0ull; tail[2] = 0; tail[3] = 0; tail[5] = 0; tail[6] = 0;
+    for (int c = 24; c < 30; ++c) { tail[c] = 0; }
     tail[4] = wall_clock64();
 }
 
@@ -598,14 +604,22 @@ void Net::dumpSimProf()
         const double helping = double(tail[12]) / L * 0.01; // a CU that helps another game's tower is busy
         fprintf(stderr, "[mz sim prof] launches: %llu, avg per launch from the first game's start: first game done %.1f us, mean %.1f us, last %.1f us -> %.1f %% of the CU time idles at the end of a launch\n",
                 tail[8], first, mean, last, 100.0 * (last - mean - helping) / std::max(1e-9, last));
-        if (tail[13] > 0 || tail[15] > 0) {
+        if (tail[13] > 0 || tail[15] > 0 || tail[21] > 0) {
             double tw = 0;
             for (size_t g = 0; g < G; ++g) { tw += double(h[g * 8 + 1]); }
-            const double ran = sims_all - skipped, pn = double(tail[13]), pt = double(tail[14]);
+            // ("a pair tower" of the first line: a tower with at least one helper; the quad towers among them have the line after it)
+            const double ran = sims_all - skipped, qn = double(tail[21]), qt = double(tail[22]), pn = double(tail[13]) + qn, pt = double(tail[14]) + qt;
             fprintf(stderr, "[mz sim prof] tail help: %.0f of the %.0f simulations that ran the network had a pair tower (%.2f %%): tower %.2f us with a helper, %.2f us alone; %llu games helped, "
                             "a CU helps for %.1f us per launch after its own game (%.1f %% of the launch)\n",
                     pn, ran, 100.0 * pn / std::max(1.0, ran), pt / std::max(1.0, pn) * 0.01, (tw - pt) / std::max(1.0, ran - pn) * 0.01, tail[15], helping,
                     100.0 * helping / std::max(1e-9, last));
+            fprintf(stderr, "[mz sim prof] tail help, quad towers: %.0f of the %.0f simulations that ran the network had a quad tower (%.2f %%): tower %.2f us with three helpers, %.2f us with "
+                            "one; %llu games went from pair to quad towers\n",
+                    qn, ran, 100.0 * qn / std::max(1.0, ran), qt / std::max(1.0, qn) * 0.01, (pt - qt) / std::max(1.0, pn - qn) * 0.01, tail[23]);
+            const double ia = double(tail[30]) / L * 0.01, ib = double(tail[31]) / L * 0.01, ic = double(tail[32]) / L * 0.01;
+            fprintf(stderr, "[mz sim prof] tail help, idle CU time by the reason the CU stopped looking for a game to help (%% of the launch): (a) every running game of its XCD had its "
+                            "helpers %.2f %%, (b) no game of its XCD was running any more %.2f %%, (c) only games with fewer than help_min_left simulations were left %.2f %%\n",
+                    100.0 * ia / std::max(1e-9, last), 100.0 * ib / std::max(1e-9, last), 100.0 * ic / std::max(1e-9, last));
         }
     }
 }

@@ -494,7 +494,11 @@ __device__ __forceinline__ bool simLeafTerminal(CSimArgs* __restrict__ a, const 
 
 // MZ_SIM_PROF: the words behind the per-game counters (kSimProfTail of them).  [0..3] belong to the launch that is running — earliest start, first and last exit
 // of a game (100-MHz ticks from [4], the stamp of the previous fold), sum of the exits; sim_prof_fold (sim.hip) adds them to [8..] between two launches.
-constexpr int kSimProfTail = 24; // ([16..20]: the value-first order: simulations, walks that arrived at the previous leaf, waits there, their ticks, waits in front of the leaf)
+constexpr int kSimProfTail = 40; // ([16..20]: the value-first order: simulations, walks that arrived at the previous leaf, waits there, their ticks, waits in front of the leaf;
+                                 //  tail help: [21] simulations that ran a quad tower, [22] their tower ticks, [23] games whose pair became a quad; why a finished CU stopped looking
+                                 //  for a game to help — cause 0: every running game of its XCD with enough simulations left had its helpers, 1: no game of its XCD was running,
+                                 //  2: only games with fewer than help_min_left simulations were left — [24 + cause] CUs and [27 + cause] the sum of the ticks at which they
+                                 //  stopped, of the running launch; [30 + cause] ticks per CU from there to the last game's exit, summed over the launches by sim_prof_fold)
 __device__ __forceinline__ void simProfEnter(unsigned long long* tail)
 {
     atomicMin(tail + 0, wall_clock64() - tail[4]);
@@ -541,11 +545,12 @@ __device__ __noinline__ const float* simTowerBf16(CSimArgs* __restrict__ a, int 
                                reinterpret_cast<char*>(tiles));
 }
 
-// Tail help (sim_help.h), owner side: the simulation's tower with the game's helper.  Wave 0 first sends the leaf's bit-packed planes — the command: 16-byte
-// stores of three words + the simulation's sequence number each — then the workgroup runs member 0 of the pair tower.  Its own function beside simTower, so
-// that the solo path keeps its register budget and code.  nullptr: the helper went missing (the error flag is raised, the workgroup leaves the kernel).
-template <int H, int W, int CIN0_PAD, int CPAD>
-__device__ __noinline__ const float* simTowerPair(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
+// Tail help (sim_help.h), owner side: the simulation's tower with the game's helper(s).  Wave 0 first sends the leaf's bit-packed planes — the command: 16-byte
+// stores of three words + the command word (sequence number of the simulation, mode, start of the exchange count) each — then the workgroup runs member 0 of the pair
+// or quad tower.  Functions of their own beside simTower, so that the solo path keeps its register budget and code.  nullptr: a helper went missing (the error flag
+// is raised, the workgroup leaves the kernel).
+template <int H, int W, int CIN0_PAD, int CPAD, int MODE>
+__device__ __forceinline__ const float* simTowerHelped(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
 {
     g = __builtin_amdgcn_readfirstlane(g);
     seq = __builtin_amdgcn_readfirstlane(seq);
@@ -559,18 +564,52 @@ __device__ __noinline__ const float* simTowerPair(CSimArgs* __restrict__ a, int 
         u.x = bits[3 * tid];
         u.y = 3 * tid + 1 < fw ? bits[3 * tid + 1] : 0u;
         u.z = 3 * tid + 2 < fw ? bits[3 * tid + 2] : 0u;
-        u.w = unsigned(seq);
+        u.w = hpCmdWord(unsigned(seq), MODE, xseq);
         asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(hb + kHpCmd + 4 * tid), "v"(u) : "memory");
     }
     HelpCtx c{hb, 0, xseq, abort_lds, a->err};
-    return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c);
+    if constexpr (MODE == kHpModeQuad) { return towerBodyQuad<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c); }
+    else { return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c); }
+}
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __noinline__ const float* simTowerPair(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
+{
+    return simTowerHelped<H, W, CIN0_PAD, CPAD, kHpModePair>(a, g, tid, tiles, xchg, seq, xseq, abort_lds);
+}
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __noinline__ const float* simTowerQuad(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
+{
+    return simTowerHelped<H, W, CIN0_PAD, CPAD, kHpModeQuad>(a, g, tid, tiles, xchg, seq, xseq, abort_lds);
+}
+
+// Tail help, owner side: the tower of this simulation by the game's helper slots (one thread of a wave that has no part in the walk).  Slots 2 and 3 are only
+// claimed in a game whose slot 1 is, and only looked at then: a game without a helper pays one load, as before.
+__device__ __forceinline__ int simHelpMode(const unsigned* help_blk)
+{
+    if (hpLoadU(help_blk + kHpHelper) == 0u) { return 0; }
+    const unsigned h2 = hpLoadU(help_blk + kHpHelper2), h3 = hpLoadU(help_blk + kHpHelper3);
+    return (h2 != 0u && h3 != 0u) ? 2 : 1;
+}
+
+// Tail help, helper side: one tower of game `o` as its member `member`.  Pair and quad are functions of their own, each with its own register budget, like the
+// owner's (inlined side by side into simHelpTail they spilled into its layer loops).  false: a member went missing.
+template <int H, int W, int CIN0_PAD, int CPAD, int MODE>
+__device__ __noinline__ bool simHelpTower(CSimArgs* __restrict__ a, int o, int member, unsigned xseq, int tid, float* tiles, const unsigned* bits, int* abort_lds)
+{
+    o = __builtin_amdgcn_readfirstlane(o);
+    member = __builtin_amdgcn_readfirstlane(member);
+    xseq = __builtin_amdgcn_readfirstlane(xseq);
+    HelpCtx c{a->help + size_t(o) * a->help_words, member, xseq, abort_lds, a->err};
+    if constexpr (MODE == kHpModeQuad) { return towerBodyQuad<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c) != nullptr; }
+    else { return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c) != nullptr; }
 }
 
 // Tail help, helper side: the workgroup of game g has finished its simulations of this launch and written its results.  It looks among the games of its XCD
 // (workgroups are dealt to the XCDs round-robin, so those are the games congruent to g mod 8; the XCC_ID every owner publishes is compared anyway) for the one
-// with the least progress that has no helper and at least help_min_left simulations left, claims it and computes member 1 of its pair towers until that game is
-// done; then it looks again, and leaves when there is nothing to claim.  `bits`: LDS for the planes of a command.  MZ_SIM_PROF: tail words [6] ticks spent as
-// a helper in this launch, [15] games helped.
+// with the least progress that has no helper and at least help_min_left simulations left, and claims its slot 1; if there is none, for the helped game with the
+// least progress that has a free slot 2 or 3 (MZ_NO_SPEC=128: slot 1 only, one helper per game).  It computes its member's share of that game's pair or quad towers,
+// as the commands say, until that game is done; then it looks again, and leaves when there is nothing to claim.  `bits`: LDS for the planes of a command.
+// MZ_SIM_PROF: tail words [6] ticks spent as a helper in this launch, [15] games helped, [24 ..] why it left (kSimProfTail).
 template <int H, int W, int CIN0_PAD, int CPAD>
 __device__ __noinline__ void simHelpTail(CSimArgs* __restrict__ a, int g, int tid, float* tiles, unsigned* bits, int nsims, int* s_help)
 {
@@ -579,38 +618,62 @@ __device__ __noinline__ void simHelpTail(CSimArgs* __restrict__ a, int g, int ti
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int games = gridDim.x, words = a->help_words, min_left = a->help_min_left;
     const int fw = a->gv.channels * a->gv.W32, units = helpCmdUnits(fw);
+    const bool more_slots = !(a->no_spec & 128);
     const unsigned myxcc = hpXccId();
     unsigned long long* ptail = a->prof ? a->prof + size_t(games) * 8 : nullptr;
     for (int round = 0; round < 64; ++round) { // (bounded: a round either claims a game, loses the claim to another helper, or ends the search)
         if (wave == 0) {
-            unsigned key = ~0u; // (progress << 10) | game: the least progress wins
+            unsigned key = ~0u, key2 = ~0u; // (progress << 10) | game: the least progress wins; key2: among the helped games with a free slot
+            bool enough = false, running = false;
             for (int o = (g & 7) + 8 * lane; o < games; o += 8 * 64) {
                 const unsigned* ob = a->help + size_t(o) * words;
                 const unsigned x = hpLoadU(ob + kHpXcc), p = hpLoadU(ob + kHpProgress), h = hpLoadU(ob + kHpHelper);
+                const unsigned h2 = hpLoadU(ob + kHpHelper2), h3 = hpLoadU(ob + kHpHelper3);
                 const unsigned k = (p << 10) | unsigned(o);
-                if (o != g && x == myxcc && h == 0u && int(p) + min_left <= nsims && k < key) { key = k; }
+                const bool mine = o != g && x == myxcc, left = int(p) + min_left <= nsims;
+                running = running || (mine && int(p) < nsims);
+                enough = enough || (mine && left);
+                if (mine && left && h == 0u && k < key) { key = k; }
+                if (mine && left && more_slots && h != 0u && (h2 == 0u || h3 == 0u) && k < key2) { key2 = k; }
             }
             for (int o = 32; o > 0; o >>= 1) { const unsigned k2 = __shfl_xor(key, o); key = k2 < key ? k2 : key; }
+            for (int o = 32; o > 0; o >>= 1) { const unsigned k2 = __shfl_xor(key2, o); key2 = k2 < key2 ? k2 : key2; }
+            enough = __any(enough);
+            running = __any(running);
             if (lane == 0) {
-                int cl = 0;
+                int cl = 0, slot = 1;
                 if (key != ~0u) {
                     unsigned expected = 0u;
                     unsigned* hw = a->help + size_t(key & 1023u) * words + kHpHelper;
                     cl = __hip_atomic_compare_exchange_strong(hw, &expected, unsigned(g) + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? int(key & 1023u) + 1 : -1;
+                } else if (key2 != ~0u) {
+                    key = key2;
+                    unsigned* hw = a->help + size_t(key & 1023u) * words;
+                    cl = -1;
+                    for (slot = 2; slot <= 3 && cl < 0; ++slot) {
+                        unsigned expected = 0u;
+                        if (__hip_atomic_compare_exchange_strong(hw + (slot == 2 ? kHpHelper2 : kHpHelper3), &expected, unsigned(g) + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                                 __HIP_MEMORY_SCOPE_AGENT)) { cl = int(key & 1023u) + 1; break; }
+                    }
                 }
                 s_help[1] = cl;
-                s_help[2] = int(key >> 10); // the owner's progress when it was chosen: every command for this helper has a higher sequence number
+                // the owner's progress when it was chosen: every command for this helper has a higher sequence number.  Nothing to claim: why (kSimProfTail)
+                s_help[2] = cl != 0 ? int(key >> 10) : (enough ? 0 : running ? 2 : 1);
+                s_help[3] = slot;
             }
         }
         __syncthreads();
         const int cl = __builtin_amdgcn_readfirstlane(s_help[1]);
         unsigned last = unsigned(__builtin_amdgcn_readfirstlane(s_help[2]));
+        const int slot = __builtin_amdgcn_readfirstlane(s_help[3]);
         __syncthreads();
-        if (cl == 0) { return; }
+        if (cl == 0) {
+            if (ptail && tid == 0) { atomicAdd(ptail + 24 + last, 1ull); atomicAdd(ptail + 27 + last, wall_clock64() - ptail[4]); }
+            return;
+        }
         if (cl < 0) { continue; }
         const unsigned long long th0 = ptail ? wall_clock64() : 0;
         unsigned* ob = a->help + size_t(cl - 1) * words;
-        HelpCtx c{ob, 1, 0u, s_help, a->err};
         for (;;) {
             if (wave == 0) { // the next command, or the end of the owner's launch
                 int st = 0;
@@ -618,29 +681,35 @@ __device__ __noinline__ void simHelpTail(CSimArgs* __restrict__ a, int g, int ti
                 for (int i = 0; i < kHpPollLimit && st == 0; ++i) {
                     const unsigned* src = ob + kHpCmd + 4 * (lane < units ? lane : 0);
                     asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(u) : "v"(src) : "memory");
-                    const unsigned sq = __builtin_amdgcn_readfirstlane(u.w);
-                    if (__all(u.w == sq) && sq > last && sq <= unsigned(nsims)) { st = 1; last = sq; }
-                    else if (hpLoadU(ob + kHpProgress) >= unsigned(nsims)) { st = 2; }
+                    const unsigned cw = __builtin_amdgcn_readfirstlane(u.w), sq = hpCmdSeq(cw);
+                    if (__all(u.w == cw) && sq > last && sq <= unsigned(nsims)) {
+                        last = sq;
+                        // (the holder of slot 2 or 3 has no part in a pair tower: it waits for the command after it)
+                        if (slot == 1 || hpCmdMode(cw) == kHpModeQuad) { st = 1 + hpCmdMode(cw); s_help[2] = int(hpCmdXseq(cw)); }
+                    }
+                    else if (hpLoadU(ob + kHpProgress) >= unsigned(nsims)) { st = 3; }
                     else { __builtin_amdgcn_s_sleep(4); }
                 }
-                if (st == 1 && lane < units) {
+                if ((st == 1 || st == 2) && lane < units) {
                     bits[3 * lane] = u.x;
                     if (3 * lane + 1 < fw) { bits[3 * lane + 1] = u.y; }
                     if (3 * lane + 2 < fw) { bits[3 * lane + 2] = u.z; }
                 }
                 if (lane == 0) {
-                    if (st == 0) { atomicExch(a->err, 96); }
+                    if (st == 0) { atomicExch(a->err, slot == 1 ? 96 : kHpErrQuadCmd); }
                     s_help[1] = st;
                 }
             }
             __syncthreads();
             const int st = __builtin_amdgcn_readfirstlane(s_help[1]);
-            if (st != 1) {
+            if (st != 1 && st != 2) {
                 if (ptail && tid == 0) { atomicAdd(ptail + 6, wall_clock64() - th0); atomicAdd(ptail + 15, 1ull); }
                 if (st == 0) { return; }
                 break;
             }
-            if (!towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c)) { return; }
+            const unsigned xseq = unsigned(__builtin_amdgcn_readfirstlane(s_help[2]));
+            if (!(st == 2 ? simHelpTower<H, W, CIN0_PAD, CPAD, kHpModeQuad>(a, cl - 1, slot, xseq, tid, tiles, bits, s_help)
+                          : simHelpTower<H, W, CIN0_PAD, CPAD, kHpModePair>(a, cl - 1, 1, xseq, tid, tiles, bits, s_help))) { return; }
             __syncthreads();
         }
         __syncthreads();
@@ -707,13 +776,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     if (tid == 0) { *node_count = a->pv.num_nodes[g]; }
     if (prof && tid == 0) { simProfEnter(a->prof + size_t(games) * 8); }
     // Tail help (sim_help.h; bit 1 of host_start: this launch helps): the game publishes the XCD it runs on — from here on it can be claimed by a workgroup of
-    // that XCD whose own game is done.  s_help: [0] abort flag of the exchanges, [1] the game's helper (0: none) as of this simulation, [2] the helper's scratch.
+    // that XCD whose own game is done.  s_help: [0] abort flag of the exchanges, [1] the game's tower as of this simulation (0: solo, 1: pair, 2: quad), [2], [3] the
+    // helper's scratch.
     constexpr bool kHelp = !BF && WPE == 2 && CPL > 0 && pairTowerShape<H, W, CPAD>();
     __shared__ int s_help[kHelp ? kVfWords : 4]; // (+ the words of the value-first order: kVfBackup ..)
     const bool help_on = kHelp && (host_start & 2) != 0;
     unsigned* const help_blk = help_on ? a->help + size_t(g) * a->help_words : nullptr;
-    unsigned help_xseq = 0;                        // layer exchanges of this game's pair towers so far
+    unsigned help_xseq = 0;                        // layer exchanges of this game's pair and quad towers so far
     unsigned long long pair_n = 0, pair_t = 0;     // (MZ_SIM_PROF) simulations that ran a pair tower, their tower ticks
+    unsigned long long quad_n = 0, quad_t = 0;     // ... a quad tower
     if (help_on && tid == 0) { s_help[0] = 0; s_help[1] = 0; hpStoreU(help_blk + kHpXcc, hpXccId()); }
     // The value-first order (simWalkVf .. simCandPipeVf above): the same for every simulation of the launch and for every wave, so each wave passes the same barriers
     bool vf = false;
@@ -750,7 +821,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                 } else if (help_on && tid == 7 * 64) {
                     // (wave 7 arrives here behind its rank shares of simulation s - 1, not beside the walk as in the old order: a claim made during the walk of s is
                     //  picked up one simulation later)
-                    s_help[1] = int(hpLoadU(help_blk + kHpHelper));
+                    s_help[1] = simHelpMode(help_blk);
                 }
             }
         } else if (wave == 0) {
@@ -762,10 +833,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         } else if (kHelp && help_on && tid == 7 * 64) {
             // has a helper claimed this game?  Looked up past the vector cache by a wave that has no part in the walk, handed to all waves behind the walk's
             // barrier: the branch "pair tower or solo tower" is uniform over the workgroup, and a game without a helper pays nothing for looking
-            s_help[1] = int(hpLoadU(help_blk + kHpHelper));
+            s_help[1] = simHelpMode(help_blk);
         }
         __syncthreads();
-        const bool pair = kHelp && help_on && __builtin_amdgcn_readfirstlane(s_help[1]) != 0;
+        const int help_mode = (kHelp && help_on) ? __builtin_amdgcn_readfirstlane(s_help[1]) : 0;
+        const bool pair = help_mode == 1, quad = help_mode == 2;
         // A terminal leaf has no children and its value is the game result (zero_actor.cpp:85): nobody reads the network's outputs, so planes, tower and heads
         // are not run for it.  The flag is wave 0's (simLeafTerminal), read by every wave behind the barrier: the branches on it are uniform over the workgroup,
         // and every wave passes the same barriers on either side.  (Each phase is skipped on its own, the barriers behind tower and heads stay where they are:
@@ -794,6 +866,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                     if (!xt) { return; } // the helper went missing: the error flag is raised
                     help_xseq += unsigned(a->ta.nlayers);
                 }
+                else if (quad) { // with three helpers: one oc-tile each
+                    xt = simTowerQuad<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg, s + 1, help_xseq, s_help);
+                    if (!xt) { return; }
+                    help_xseq += unsigned(a->ta.nlayers);
+                }
                 else { xt = simTower<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg); }
             }
             else { xt = simTower<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg); } // its own function: its own register budget
@@ -819,6 +896,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                         prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
                         prof[4] += 1 + (static_cast<unsigned long long>(term) << 32);
                         if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
+                        if (quad && !term) { quad_n += 1; quad_t += t2 - t1; }
                         vf_n += 1;
                     }
                     vf_t0 = t4;
@@ -860,6 +938,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
             prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
             prof[4] += 1 + (static_cast<unsigned long long>(term) << 32); // simulations | those whose network evaluation was skipped
             if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
+            if (quad && !term) { quad_n += 1; quad_t += t2 - t1; }
         }
         if (kHelp && help_on && tid == 0) { hpStoreU(help_blk + kHpProgress, unsigned(s) + 1u); } // (nsims: the game is done, its helper looks for another one)
     }
@@ -878,6 +957,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     if (prof && tid == 0) {
         simProfExit(a->prof + size_t(games) * 8);
         if (pair_n) { atomicAdd(a->prof + size_t(games) * 8 + 13, pair_n); atomicAdd(a->prof + size_t(games) * 8 + 14, pair_t); }
+        if (quad_n) { atomicAdd(a->prof + size_t(games) * 8 + 21, quad_n); atomicAdd(a->prof + size_t(games) * 8 + 22, quad_t); atomicAdd(a->prof + size_t(games) * 8 + 23, pair_n ? 1ull : 0ull); }
     }
     if (prof && tid == 0 && spec_w) {
         prof[7] += (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 1]) << 40) | (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 5]) << 20) | spec_w[kSpecWays * kSpecWay + 3];

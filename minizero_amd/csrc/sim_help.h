@@ -13,6 +13,17 @@
 //    planes + the sequence number), so the helper needs no other input and never touches the tree.
 // Every wait is bounded; a time-out raises the pool's error flag and both sides leave the kernel.  No workgroup waits for one that is not running: a helper only
 // claims a game that has published its XCC_ID in this launch, an owner only waits for a helper that has claimed it.
+//
+// Up to three helpers per game (quad tower, below): a game has three helper slots.  A finished workgroup first looks for a running game without a helper (slot
+// 1), and only if its XCD has none for a helped game with a free slot 2 or 3, least progress first, so that two idle CUs converge on one game.  The owner reads
+// slot 1 at every simulation and, once it is claimed, slots 2 and 3: with all three claimed the simulation's tower is a quad tower (one oc-tile per member), with
+// slot 1 alone a pair tower (three members would split 2 / 1 / 1), otherwise the solo tower.  The sequence word of every command unit also carries the mode
+// and the low bits of the game's exchange count at which this tower starts (hpCmdWord): a helper that joins in mid-launch has not counted the exchanges before.
+// The holder of slot 2 or 3 skips the commands of pair towers and waits — bounded, error flag kHpErrQuadCmd — for the first quad command, or leaves when the
+// owner's progress word says the game is done (its third partner never came) and searches again.  A helper stays with its game until that game is done, so a
+// game's mode only ever goes solo -> pair -> quad within a launch.  The invariants above hold as they are: every wait is a bounded poll with s_sleep (error flags
+// 95 / 96 for the pair's exchange and command, kHpErrQuad / kHpErrQuadCmd for the quad's); a slot is only claimed in a game that published its XCC_ID in this
+// launch, by a workgroup that runs on the same XCD; the owner waits only for members whose slots it has seen claimed; no cooperative launch is needed.
 #pragma once
 #include "net_body.h"
 
@@ -22,10 +33,20 @@ namespace mz {
 constexpr int kHpXcc = 0;       // XCC_ID + 1 of the owner (0: the game's workgroup has not started yet)
 constexpr int kHpProgress = 1;  // simulations of this launch the owner has finished
 constexpr int kHpHelper = 32;   // 0 or (helper's game index + 1), claimed by compare-and-swap (a 128-byte line of its own: the owner reads it at every simulation)
-constexpr int kHpCmd = 64;      // up to 64 units of 16 bytes: {three words of the leaf's planes, sequence number of the simulation}
+constexpr int kHpCmd = 64;      // up to 32 units of 16 bytes: {three words of the leaf's planes, hpCmdWord of the simulation}
+constexpr int kHpHelper2 = 192; // helper slots 2 and 3, like kHpHelper, each on a line of its own behind the command
+constexpr int kHpHelper3 = 224;
 constexpr int kHpXbuf = 320;    // 2 x [C][P] floats
 constexpr int kHpPollLimit = 1 << 21;
-constexpr int kHpMaxUnits = 64;
+constexpr int kHpMaxUnits = 32;
+constexpr int kHpErrQuad = 98, kHpErrQuadCmd = 99; // error flags: a quad tower's exchange timed out (95: the pair's), the holder of slot 2 or 3 saw no command (96: slot 1)
+constexpr int kHpModePair = 0, kHpModeQuad = 1;
+// the last word of every command unit: the simulation's sequence number (1 ..), the tower's mode and the exchange count it starts at (its two low bits: hpPart and
+// hpSign use no others); a unit is valid when all units of the command carry the same word
+__host__ __device__ constexpr unsigned hpCmdWord(unsigned seq, int mode, unsigned xseq) { return (seq & 0x0FFFFFFFu) | (unsigned(mode) << 28) | ((xseq & 3u) << 29); }
+__host__ __device__ constexpr unsigned hpCmdSeq(unsigned w) { return w & 0x0FFFFFFFu; }
+__host__ __device__ constexpr int hpCmdMode(unsigned w) { return int((w >> 28) & 1u); }
+__host__ __device__ constexpr unsigned hpCmdXseq(unsigned w) { return w >> 29; }
 typedef unsigned hpu4 __attribute__((ext_vector_type(4)));
 inline size_t helpWords(int C, int P) { return (size_t(kHpXbuf) + 2 * size_t(C) * P + 31) / 32 * 32; }
 __host__ __device__ constexpr int helpCmdUnits(int feat_words) { return (feat_words + 2) / 3; }
@@ -43,7 +64,7 @@ __device__ __forceinline__ unsigned hpXccId()
 
 struct HelpCtx {
     unsigned* hb;   // the helped game's block
-    int member;     // 0 owner, 1 helper
+    int member;     // 0 owner, 1 helper (quad tower: 1-3, the helper's slot)
     unsigned xseq;  // layer exchanges of this game so far in this launch
     int* abort_lds; // workgroup-wide abort flag
     int* err;
@@ -167,6 +188,121 @@ __device__ __forceinline__ float* towerBodyPair(const unsigned* __restrict__ bit
         else { ok = pairRun<H, W, CIN0_PAD, CPAD, 1, true>(params, ta, T0, T1, lane, tid, ot, 5, c); }
         __builtin_amdgcn_s_setprio(0);
     }
+    return ok ? T1 : nullptr;
+}
+
+// ---- quad tower: four members (0 = the owner, 1-3 = the holders of the game's helper slots), member m computes oc-tile m of every layer for all pixel tiles
+// with the same layer function as the pair, so the activations are bit-identical to the pair's and the solo tower's.  The exchange buffers, hpPart and hpSign are
+// the pair's: part `ot` of buffer (xseq & 1) holds oc-tile ot whoever wrote it, and every exchange writes all four parts in either mode, so a game may change
+// between pair and quad towers from one simulation to the next while its exchange count runs on (a word of the exchange before last in the same buffer carries the
+// other phase).
+// Buffer reuse with four members: member A writes its part of buffer b for exchange x during layer x and overwrites it for exchange x + 2 during layer x + 2, which
+// it starts only after it has read exchange x + 1 completely.  Every other member B wrote its part of exchange x + 1 during its layer x + 1, which B started behind
+// the barrier that ends its read of exchange x: A's write for x + 2 comes after every B has finished reading x.  The read a helper skips after the last layer
+// (exchange x_l) is made up for by its wait for the next command: the owner sends it after it has read all of x_l, whose parts every helper wrote after it
+// had finished reading x_l - 1 — the buffer the next tower's first layer overwrites; nobody but the owner reads x_l, and the owner has.
+template <int H, int W, int CPAD>
+__device__ __forceinline__ bool hpExchangeQuad(HelpCtx& c, float* __restrict__ tout, int tid, bool read)
+{
+    constexpr int P = H * W, PW = W + 2, CS = planeStride(H, W), OWN = CPAD / 4 * P, OTHERS = 3 * OWN;
+    const unsigned sign = hpSign(c);
+    const float* xb = reinterpret_cast<const float*>(c.hb + kHpXbuf) + size_t(c.xseq & 1) * CPAD * P;
+    const int own0 = c.member * OWN; // the words [own0, own0 + OWN) of the buffer are this member's own
+    ++c.xseq;
+    __syncthreads(); // the member's own waves are done with the layer: all waves start polling together
+    if (!read) { return true; }
+    constexpr int K = (OTHERS + 511) / 512;
+    unsigned got[K];
+    bool ok = false;
+    for (int polls = 0; polls < kHpPollLimit; ++polls) {
+        ok = true;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            const int i = tid + j * 512;
+            const bool want = i < OTHERS;
+            const int src = want ? i + (i >= own0 ? OWN : 0) : (own0 == 0 ? OWN : 0);
+            got[j] = __float_as_uint(hpLoadF(xb + src));
+            ok = ok && (!want || (got[j] & 0x80000000u) == sign);
+        }
+        ok = __all(ok);
+        if (ok) { break; }
+        __builtin_amdgcn_s_sleep(2);
+    }
+    if (!ok && (tid & 63) == 0) { *c.abort_lds = 1; atomicExch(c.err, kHpErrQuad); }
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        const int i = tid + j * 512;
+        if (i < OTHERS) {
+            const int src = i + (i >= own0 ? OWN : 0), ch = src / P, p = src % P;
+            tout[ch * CS + (p / W + 1) * PW + (p % W) + 1] = __uint_as_float(got[j] & 0x7FFFFFFFu);
+        }
+    }
+    __syncthreads();
+    return *c.abort_lds == 0;
+}
+
+// the layer sequence of one wave of a quad member: oc-tile c.member x pixel tile `tile` (HAS_TILE = false: a wave without a tile, which only takes part in the exchanges)
+template <int H, int W, int CIN0_PAD, int CPAD, bool HAS_TILE, bool CORNER>
+__device__ __forceinline__ bool quadRun(const float* __restrict__ params, const TowerArgs& ta, float* __restrict__ T0, float* __restrict__ T1, int lane, int tid, int tile, HelpCtx& c)
+{
+    constexpr int P = H * W;
+    const int ot = c.member;
+    const PixSet<1> px = makePixSet<H, W, 1>(lane, HAS_TILE ? tile : 0);
+    float aS[CIN0_PAD / 4], aA[CPAD / 4], aB[CPAD / 4];
+    bool have = false;
+    if (ta.has_stem) {
+        const float* nw = ta.nlayers > 1 ? params + ta.w_off[1] : nullptr;
+        if constexpr (HAS_TILE) {
+            tower_layer<H, W, CIN0_PAD / 4, 1, CPAD / 4, CORNER, false, true>(T0, nullptr, T1, nullptr, params + ta.w_off[0], params + ta.b_off[0], ta.C, ta.OT, lane, ot, px, false,
+                                                                              aS, nw, aA, hpPart<CPAD, P>(c, ot), hpSign(c));
+        }
+        have = nw != nullptr;
+        if (!hpExchangeQuad<H, W, CPAD>(c, T1, tid, c.member == 0 || ta.nlayers > 1)) { return false; }
+    }
+    float *x = T1, *tmp = T0;
+#pragma unroll 1
+    for (int l = ta.has_stem; l < ta.nlayers; ++l) {
+        const bool second = ((l - ta.has_stem) & 1) != 0, last = l + 1 == ta.nlayers;
+        if constexpr (HAS_TILE) {
+            tower_layer<H, W, CPAD / 4, 1, CPAD / 4, CORNER, false, true>(second ? tmp : x, second ? x : nullptr, second ? x : tmp, nullptr, params + ta.w_off[l], params + ta.b_off[l],
+                                                                          ta.C, ta.OT, lane, ot, px, have, aA, last ? nullptr : params + ta.w_off[l + 1], aB, hpPart<CPAD, P>(c, ot),
+                                                                          hpSign(c));
+#pragma unroll
+            for (int cg = 0; cg < CPAD / 4; ++cg) { aA[cg] = aB[cg]; }
+        }
+        have = !last;
+        if (!hpExchangeQuad<H, W, CPAD>(c, second ? x : tmp, tid, c.member == 0 || !last)) { return false; }
+    }
+    return true;
+}
+
+// The tower of one simulation on four workgroups: like towerBodyPair, with one oc-tile per member.  Waves w and w + 4 share a SIMD; SIMD 0 works on pixel tiles
+// 0 and 1, SIMD 1 on 2 and 3, one wave each (two single chains fill a SIMD's pipe: a dependent MFMA issues every 57 cycles, the pipe takes one every 32), SIMD 2
+// on tile 4 and SIMD 3 on the corner tile: at most 2 x 144 = 288 MFMAs per SIMD and layer instead of the pair's 432.  The waves of a SIMD have the same number of
+// chains, so none gets a priority; waves 6 and 7 have no tile and take part in the exchanges only.
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __forceinline__ float* towerBodyQuad(const unsigned* __restrict__ bits, const float* __restrict__ params, const TowerArgs& ta, int tid, float* __restrict__ tiles,
+                                                HelpCtx& c)
+{
+    static_assert(pairTowerShape<H, W, CPAD>(), "quad tower: one oc-tile per member, pixel tiles {0, 1}, {2, 3}, {4}, {corner}");
+    constexpr int P = H * W, PW = W + 2, CS = planeStride(H, W), W32 = (P + 31) / 32;
+    constexpr int CMAX = CIN0_PAD > CPAD ? CIN0_PAD : CPAD;
+    const int lane = tid & 63, wave = tid >> 6;
+    float* T0 = tiles;
+    float* T1 = tiles + CMAX * CS;
+    for (int i = tid; i < kTowerTiles * CMAX * CS / 4; i += 512) { reinterpret_cast<float4*>(tiles)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    __syncthreads();
+    float* Tin = ta.has_stem ? T0 : T1;
+    for (int i = tid; i < ta.cin0 * P; i += 512) {
+        const int ch = i / P, p = i - ch * P;
+        Tin[ch * CS + (p / W + 1) * PW + (p % W) + 1] = ((bits[ch * W32 + (p >> 5)] >> (p & 31)) & 1u) ? 1.0f : 0.0f;
+    }
+    __syncthreads();
+    bool ok;
+    if (wave == 3) { ok = quadRun<H, W, CIN0_PAD, CPAD, true, true>(params, ta, T0, T1, lane, tid, 5, c); }
+    else if (wave < 3) { ok = quadRun<H, W, CIN0_PAD, CPAD, true, false>(params, ta, T0, T1, lane, tid, 2 * wave, c); }
+    else if (wave < 6) { ok = quadRun<H, W, CIN0_PAD, CPAD, true, false>(params, ta, T0, T1, lane, tid, 2 * (wave - 4) + 1, c); }
+    else { ok = quadRun<H, W, CIN0_PAD, CPAD, false, false>(params, ta, T0, T1, lane, tid, 0, c); }
     return ok ? T1 : nullptr;
 }
 

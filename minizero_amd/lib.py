@@ -679,6 +679,23 @@ def exp_tanh_device(x, device=0):
     return e, t
 
 
+def tail_towers(net, bits, members):
+    """The representation tower of a 9x9 x 64 network for every row of `bits` ([T][18 * 3] bit-packed planes) on `members` = 1 (solo), 2 (pair) or 4 (quad)
+    workgroups of one XCD each, as the tail help of the simulation kernel runs it (sim_help.h).  Returns (activations [T][64][81], XCC_ID + 1 of every workgroup
+    [members][T], error flag of the exchanges, status: 0, or 1 = the members of a tower do not share an XCD and nothing was exchanged)."""
+    L = load()
+    # (declared here and not in load(): a same-box A/B swaps in the parent commit's library, which does not have the symbol)
+    L.mz_tail_towers_device.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    b = np.ascontiguousarray(bits, np.uint32)
+    T = b.shape[0]
+    out = np.zeros((T, 64, 81), np.float32)
+    xcc = np.zeros((members, T), np.uint32)
+    err, status = C.c_int(0), C.c_int(0)
+    _check(L, L.mz_tail_towers_device(net.h, b.ctypes.data_as(C.POINTER(C.c_uint32)), T, members, _f(out), xcc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      C.byref(err), C.byref(status)))
+    return out, xcc, err.value, status.value
+
+
 def sort_candidates(policy, device=0):
     """Order of candidates under the reference's std::sort(policy descending), computed by the device path."""
     L = load()
