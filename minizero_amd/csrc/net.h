@@ -104,7 +104,8 @@ public:
     int tailTowers(const unsigned* bits, int towers, int members, float* out, unsigned* xcc, int* err_flag, int* status);
     // num_simulation: the kernels keep per-search tables / the path in LDS; searches too long for 160 KB use the lock-step kernels
     bool hasSimKernel(int board_n, int env_kind = kGo, int num_simulation = 0) const; // env_kind: GameKind, as stored in GoDevView::kind
-    // ... on the one-tile tower (sim_wide.inc, sim_wide_a.hip): Go with 128 / 256 hidden channels or on 7x7 / 13x13 / 19x19 boards
+    // ... on the one-tile tower (sim_wide.inc, sim_wide_a.hip): Go with 128 / 256 hidden channels or on 7x7 / 13x13 / 19x19 boards; at the network's precision
+    // (bf16x3: sim_kernel_wide_bf16, sim_wide_bf16.inc — 9x9 Go with 128 / 256 hidden channels)
     bool hasSimKernelWide(int board_n, int env_kind, int num_simulation) const;
     bool simWidePlan(int board_n, int env_kind, int num_simulation, const HeadParams& hp, int channels, int W32, size_t leaf_bytes, size_t scratch_bytes, int* lf, size_t* lds,
                      size_t* tile_bytes_out) const;
@@ -147,8 +148,9 @@ public:
     int expandAtariFeatures(const uint8_t* d_raw, int raw_bytes, int B, float* d_feat);
     int shiftExpandAtariFeatures(const uint8_t* d_prev, const uint8_t* d_newest, const uint8_t* d_meta, uint8_t* d_cur, int raw_bytes, int B, float* d_feat); // raw observations -> float planes (net_atari.hip)
     void makeAtariHeadParams(AtariHeadParams* out) const; // net_atari.hip
-    // opt-in 16-bit-input tower (net_bf16_body.h): 0 = f32 (default, bit-exact against the oracle), 1 = bf16x3 (split bf16 operands on
-    // v_mfma_f32_16x16x32_bf16, f32 accumulation; outputs within 1e-3 of the f32 path, records not bit-identical to the reference)
+    // opt-in 16-bit-input tower (net_bf16_body.h; net_bf16_wide_body.h): 0 = f32 (default, bit-exact against the oracle), 1 = bf16x3 (split bf16 operands on
+    // v_mfma_f32_16x16x32_bf16, f32 accumulation; outputs within 1e-3 of the f32 path, records not bit-identical to the reference).  Built for AlphaZero networks
+    // of 64 hidden channels on 9x9 / 8x8 boards and of 128 / 256 hidden channels on 9x9 boards (bf16Supported); every other shape is refused.
     int setPrecision(int mode);
     int precision() const { return precision_; }
     bool bf16Supported() const;
@@ -179,7 +181,8 @@ private:
     DevBuf<float> unpacked_;    // f32 planes of a bit-packed batch (run-time-shaped kernels only)
     bool makeTowerArgsBf16(TowerArgsBf16* out) const;
     int packBf16(const std::vector<float>& packed);
-    int launchTowerBf16(const float* d_feat, float* out, int B, bool in_bits);
+    int launchTowerBf16(const float* d_feat, float** out, int B, bool in_bits);
+    int launchTowerBf16Wide(const TowerArgsBf16& ta, const unsigned* bits, float* gx, float* gt, float* out, int B); // net_bf16_wide.hip: 128 / 256 channels
     int precision_ = 0;
     DevBuf<uint4> wfrag_;                 // bf16 hi / lo A-fragments of the representation trunk (built at load when the shape is supported)
     std::vector<unsigned> wfrag_off_;     // per layer, in 16-byte units

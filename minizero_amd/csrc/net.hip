@@ -16,6 +16,7 @@
 #include "net.h"
 #include "net_body.h"
 #include "net_bf16_body.h"
+#include "bf16_split.h"
 #include <cmath>
 #include <cstring>
 
@@ -207,48 +208,29 @@ int Net::reload(const float* raw, size_t n)
 // ---- opt-in bf16x3 tower: fragments, launch, switch ----
 bool Net::bf16Supported() const
 {
-    const int H = desc_.hidden_channel_height, W = desc_.hidden_channel_width;
-    return desc_.type == 0 && desc_.num_hidden_channels == 64 && !repr_.empty() && repr_.size() >= 3 && repr_.size() <= 48 && (repr_.size() % 2) == 1 &&
-           repr_[0].cin <= 32 && ((H == 9 && W == 9) || (H == 8 && W == 8));
-}
-
-static uint16_t bf16Rne(float v)
-{
-    uint32_t u;
-    memcpy(&u, &v, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u) { return static_cast<uint16_t>(u >> 16); } // inf / nan: truncate
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return static_cast<uint16_t>(u >> 16);
-}
-static float bf16ToFloat(uint16_t h)
-{
-    const uint32_t u = static_cast<uint32_t>(h) << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
+    const int H = desc_.hidden_channel_height, W = desc_.hidden_channel_width, C = desc_.num_hidden_channels;
+    if (desc_.type != 0 || repr_.size() < 3 || repr_.size() > 48 || (repr_.size() % 2) != 1 || repr_[0].cin > 32) { return false; }
+    if (C == 64) { return (H == 9 && W == 9) || (H == 8 && W == 8); } // the two-tile body (net_bf16_body.h)
+    return (C == 128 || C == 256) && H == 9 && W == 9;                // the one-tile body (net_bf16_wide_body.h)
 }
 
 int Net::packBf16(const std::vector<float>& packed)
 {
     wfrag_off_.clear();
     if (!bf16Supported()) { return MZ_OK; }
-    // per layer [tap][oc-tile][k-block][hi, lo][lane][8]: lane = 16 * kg + m holds W'[oc = 16 * ot + m][c = 32 * kb + 8 * kg + j][tap]
+    // per layer [tap][oc-tile][k-block][hi, lo][lane][8] (bf16_split.h bf16FragIndex); channels beyond the layer's own are zero
     std::vector<uint16_t> frag;
     for (const ConvLayer& L : repr_) {
         const int CG = L.cin_pad / 4, OT = L.cout_pad / 16, KB = (L.cin + 31) / 32;
-        wfrag_off_.push_back(static_cast<unsigned>(frag.size() / 8));
+        const size_t base = frag.size();
+        wfrag_off_.push_back(static_cast<unsigned>(base / 8));
+        frag.resize(base + bf16FragElems(OT, KB), 0);
         for (int t = 0; t < 9; ++t)
-            for (int ot = 0; ot < OT; ++ot)
-                for (int kb = 0; kb < KB; ++kb)
-                    for (int hl = 0; hl < 2; ++hl)
-                        for (int l = 0; l < 64; ++l)
-                            for (int j = 0; j < 8; ++j) {
-                                const int oc = 16 * ot + (l & 15), c = 32 * kb + 8 * (l >> 4) + j;
-                                float w = 0.0f;
-                                if (oc < L.cout && c < L.cin) { w = packed[L.w_off + ((size_t(t) * CG + c / 4) * OT + oc / 16) * 64 + 16 * (c % 4) + oc % 16]; }
-                                const uint16_t hi = bf16Rne(w);
-                                frag.push_back(hl == 0 ? hi : bf16Rne(w - bf16ToFloat(hi)));
-                            }
+            for (int oc = 0; oc < L.cout; ++oc)
+                for (int c = 0; c < L.cin; ++c) {
+                    const float w = packed[L.w_off + ((size_t(t) * CG + c / 4) * OT + oc / 16) * 64 + 16 * (c % 4) + oc % 16];
+                    bf16Split(w, &frag[base + bf16FragIndex(OT, KB, t, oc, c, 0)], &frag[base + bf16FragIndex(OT, KB, t, oc, c, 1)]);
+                }
     }
     if (!wfrag_.ensure(frag.size() / 8)) { setError("hipMalloc of the bf16 fragments failed"); return MZ_ERR_DEVICE; }
     MZ_HIP(hipMemcpy(wfrag_.p, frag.data(), frag.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -272,7 +254,9 @@ int Net::setPrecision(int mode)
 {
     if (mode != 0 && mode != 1) { setError("precision %d unknown (0 = f32, 1 = bf16x3)", mode); return MZ_ERR_ARG; }
     if (mode == 1 && !bf16Supported()) {
-        setError("mz_nn_precision=bf16x3 is built for AlphaZero networks with 64 hidden channels on 9x9 / 8x8 boards; this network keeps the f32 tower");
+        setError("mz_nn_precision=bf16x3 is built for AlphaZero networks with 64 hidden channels on 9x9 / 8x8 boards and with 128 / 256 hidden channels on 9x9 boards "
+                 "(at most 32 input planes); this network (%s, %dx%d x %d channels) keeps the f32 tower",
+                 desc_.type == 0 ? "alphazero" : "muzero", desc_.hidden_channel_height, desc_.hidden_channel_width, desc_.num_hidden_channels);
         return MZ_ERR_ARG;
     }
     precision_ = mode;
@@ -289,7 +273,8 @@ static int launchTowerBf16T(const TowerArgsBf16& ta, const uint4* wfrag, const f
     return MZ_OK;
 }
 
-int Net::launchTowerBf16(const float* d_feat, float* out, int B, bool in_bits)
+// *out: where the last activations ([B][C][P] f32) end up
+int Net::launchTowerBf16(const float* d_feat, float** out, int B, bool in_bits)
 {
     TowerArgsBf16 ta;
     if (!makeTowerArgsBf16(&ta)) { setError("bf16x3 tower: unsupported network"); return MZ_ERR_STATE; }
@@ -302,8 +287,10 @@ int Net::launchTowerBf16(const float* d_feat, float* out, int B, bool in_bits)
         MZ_HIP(hipGetLastError());
         bits = bits_in_.p;
     }
-    if (H == 9 && W == 9) { return launchTowerBf16T<9, 9>(ta, wfrag_.p, params_.p, bits, out, B, stream_); }
-    return launchTowerBf16T<8, 8>(ta, wfrag_.p, params_.p, bits, out, B, stream_);
+    if (ta.C != 64) { *out = act_[2].p; return launchTowerBf16Wide(ta, bits, act_[0].p, act_[1].p, act_[2].p, B); } // (x of the blocks in act_[0] / act_[1])
+    *out = act_[0].p;
+    if (H == 9 && W == 9) { return launchTowerBf16T<9, 9>(ta, wfrag_.p, params_.p, bits, act_[0].p, B, stream_); }
+    return launchTowerBf16T<8, 8>(ta, wfrag_.p, params_.p, bits, act_[0].p, B, stream_);
 }
 
 int Net::ensureBatch(int B)
@@ -424,10 +411,7 @@ int Net::launchTower(const std::vector<ConvLayer>& t, const float* in, float* ou
 int Net::runTrunk(const std::vector<ConvLayer>& t, const float* d_in, int B, float** d_out, bool in_bits)
 {
     if (precision_ == 1 && &t == &repr_) {
-        int rc = launchTowerBf16(d_in, act_[0].p, B, in_bits);
-        if (rc) { return rc; }
-        *d_out = act_[0].p;
-        return MZ_OK;
+        return launchTowerBf16(d_in, d_out, B, in_bits);
     }
     bool launched = false;
     int frc = launchTower(t, d_in, act_[0].p, B, &launched, in_bits);

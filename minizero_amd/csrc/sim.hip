@@ -647,9 +647,9 @@ int Net::uploadSimArgs(const SimArgs& a)
 
 bool Net::hasSimKernelWide(int board_n, int env_kind, int num_simulation) const
 {
-    // (precision_: simLaunch takes the wide path for the f32 tower only — one predicate for "is there a kernel" and "will it be launched", so that a shape
-    // that ever has both a bf16x3 tower and a wide instance falls back to the lock-step mode at init instead of failing at its first launch)
-    if (desc_.type != 0 || !use_fused_ || repr_.empty() || precision_ != 0) { return false; }
+    // (one predicate for "is there a kernel" and "will it be launched" — simLaunch asks it again — at the network's precision: a search whose blocks do not fit
+    // beside the bf16x3 tile falls back to the lock-step mode at init instead of failing at its first launch)
+    if (desc_.type != 0 || !use_fused_ || repr_.empty()) { return false; }
     HeadParams hp;
     makeHeadParams(&hp);
     GoDevView gv{};
@@ -689,7 +689,7 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     SimArgs a;
     memset(&a, 0, sizeof(a)); // compared bytewise below: no indeterminate padding
     int c0 = 0;
-    const bool wide = hasSimKernelWide(gv.n, gv.kind, pool.v_.max_depth - 3); // (false for the bf16x3 tower)
+    const bool wide = hasSimKernelWide(gv.n, gv.kind, pool.v_.max_depth - 3); // (the instance of the network's precision)
     if (wide) { if (!makeWideArgs(repr_, true, &a.ta, &c0)) { return MZ_OK; } }
     else if (!makeTowerArgs(repr_, true, true, &a.ta, &c0)) { return MZ_OK; }
     int rc = ensureBatch(gv.games);
@@ -716,7 +716,11 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
         rc = simProfBuffer(gv.games, &a.prof);
         if (rc) { return rc; }
     }
-    if (wide) { // sim_kernel_wide: its own LDS plan (sim_wide_a.hip)
+    if (wide) { // sim_kernel_wide / sim_kernel_wide_bf16: its own LDS plan (sim_wide_a.hip)
+        if (precision_ == 1) {
+            if (!makeTowerArgsBf16(&a.tb)) { setError("simLaunch: bf16x3 tower not available for this network"); return MZ_OK; }
+            a.wfrag = wfrag_.p;
+        }
         size_t scratch = std::max(std::max(goLeafSmemBytes(gv, pool.v_.max_depth), azCandSmemBytes(gv.A)), gumbelSmemBytes(gv.A));
         scratch = std::max(scratch, size_t(2) * pool.v_.bound_cap * sizeof(float));
         int lf = 0;

@@ -46,7 +46,7 @@ struct SimArgs {
                                       // 8 the Go leaf in one piece, 16 the network also runs at terminal leaves (sim_kernel), 32 no tail help (sim_help.h),
                                       // 64 no value-first order: candidates + expand + backup of a simulation in front of the next walk (sim_az_body.h simWalkVf)
     int cand_coop;                    // the candidate rank sort is shared by the 8 waves (its scratch fits the tower tiles)
-    // opt-in bf16x3 tower (net_bf16_body.h): fragments + layer table; used by the BF instantiations of sim_kernel
+    // opt-in bf16x3 tower (net_bf16_body.h): fragments + layer table; used by the BF instantiations of sim_kernel and by sim_kernel_wide_bf16
     const uint4* wfrag;
     TowerArgsBf16 tb;
     unsigned* cluster;                // cluster mode (sim_cluster.h): per-game exchange block of `cluster_words` words; nullptr: one workgroup per game

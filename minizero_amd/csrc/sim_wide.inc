@@ -151,14 +151,15 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
 }
 
 // The parts, listed once: part n is simWideLaunchPart<n>, defined by the translation unit built with MZ_SIM_WIDE_PART == n and tried in this order (sim_wide_a.hip)
-#define MZ_SIM_WIDE_PARTS(X) X(0) X(1) X(2) X(3) X(4) X(5)
+#define MZ_SIM_WIDE_PARTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7)
 #define MZ_SIM_WIDE_FN(n) simWideLaunchPart##n
 #define MZ_SIM_WIDE_SIG(n)                                                                                                                                                    \
-    bool MZ_SIM_WIDE_FN(n)(int H, int W, int c0q, int C, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds, \
+    bool MZ_SIM_WIDE_FN(n)(int H, int W, int c0q, int C, int cpl, int prec, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds, \
                            hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words)
 #define MZ_SIM_WIDE_SIG_OF(n) MZ_SIM_WIDE_SIG(n) // (expands MZ_SIM_WIDE_PART before it is pasted)
 
-// instances by part: (H, W, input channels of the stem padded to 16, hidden channels, the rules argument: game_kind.h rulesArg)
+// instances by part: (H, W, input channels of the stem padded to 16, hidden channels, the rules argument: game_kind.h rulesArg); prec: Net::precision() — the
+// parts of sim_kernel_wide hold the f32 tower's instances, parts 6 and 7 (sim_wide_bf16.inc) those of sim_kernel_wide_bf16
 #if MZ_SIM_WIDE_PART == 0
 #define MZ_SIM_WIDE_PART_CASES(X) X(9, 9, 32, 128, 2) X(9, 9, 32, 32, 2) X(7, 7, 32, 128, 1) X(13, 13, 32, 64, 3)
 #elif MZ_SIM_WIDE_PART == 1
@@ -171,16 +172,18 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
 #define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 16, 64, kRulesGomoku) X(15, 15, 16, 32, kRulesGomoku)
 #elif MZ_SIM_WIDE_PART == 5 // Hex on its default 11x11 board: 64 channels (measured), 32 (tests), 128
 #define MZ_SIM_WIDE_PART_CASES(X) X(11, 11, 16, 64, kRulesHex) X(11, 11, 16, 32, kRulesHex) X(11, 11, 16, 128, kRulesHex)
+#elif MZ_SIM_WIDE_PART == 6 || MZ_SIM_WIDE_PART == 7 // the bf16x3 tower: sim_wide_bf16.inc defines the kernel, its instances and the part's function
 #else
 #error "MZ_SIM_WIDE_PART: not one of MZ_SIM_WIDE_PARTS"
 #endif
 
 // true: this part holds the instance (launched when d_args != nullptr; d_args == nullptr: a query, *tile_bytes = the LDS bytes of the tower's tile, *spec_words = the
 // words of the walk's speculation memory as this translation unit was built)
+#ifdef MZ_SIM_WIDE_PART_CASES
 MZ_SIM_WIDE_SIG_OF(MZ_SIM_WIDE_PART)
 {
 #define MZ_SIM_WIDE_ONE(h, w, cin0q, c, cp)                                                                                                        \
-    if (H == h && W == w && c0q == cin0q && C == c && cpl == cp) {                                                                                 \
+    if (H == h && W == w && c0q == cin0q && C == c && cpl == cp && prec == 0) {                                                                    \
         if (tile_bytes) { *tile_bytes = wideTileFloats<h, w, c>(cin0q) * sizeof(float); }                                                          \
         if (spec_words) { *spec_words = kSpecWords; } /* of THIS translation unit (MZ_SPEC_WAYS) */                                                \
         if (d_args) { *rc = launchSimWideT<h, w, cin0q, c, cp>(d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s); }                       \
@@ -190,5 +193,6 @@ MZ_SIM_WIDE_SIG_OF(MZ_SIM_WIDE_PART)
 #undef MZ_SIM_WIDE_ONE
     return false;
 }
+#endif
 
 } // namespace mz

@@ -8,17 +8,18 @@ namespace mz {
 MZ_SIM_WIDE_PARTS(MZ_SIM_WIDE_DECL)
 #undef MZ_SIM_WIDE_DECL
 
-static bool simWideAny(int H, int W, int c0q, int C, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds,
+static bool simWideAny(int H, int W, int c0q, int C, int cpl, int prec, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds,
                        hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words = nullptr)
 {
-#define MZ_SIM_WIDE_TRY(n) || MZ_SIM_WIDE_FN(n)(H, W, c0q, C, cpl, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words)
+#define MZ_SIM_WIDE_TRY(n) || MZ_SIM_WIDE_FN(n)(H, W, c0q, C, cpl, prec, d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s, tile_bytes, rc, spec_words)
     return false MZ_SIM_WIDE_PARTS(MZ_SIM_WIDE_TRY);
 #undef MZ_SIM_WIDE_TRY
 }
 
 // The LDS plan of sim_kernel_wide for a search of n simulations on a board of board_n x board_n points: false = no instance, or the mandatory blocks do not fit.
 // *lf = the optional blocks that fit, in the order of what they buy (superko table, the leaf's block beside the heads, path speculation); *lds = the bytes to ask for
-// env_kind: GameKind (the kernels take its rules argument, game_kind.h rulesArg)
+// env_kind: GameKind (the kernels take its rules argument, game_kind.h rulesArg).  The instance is the one of the network's precision: the bf16x3 kernels' tile
+// is another size (9x9 x 256: 128 KB against the f32 tile's 124), so the same search may keep fewer optional blocks, or have no plan where the f32 tower has one.
 bool Net::simWidePlan(int board_n, int env_kind, int num_simulation, const HeadParams& hp, int channels, int W32, size_t leaf_bytes, size_t scratch_bytes, int* lf, size_t* lds,
                       size_t* tile_bytes_out) const
 {
@@ -30,7 +31,8 @@ bool Net::simWidePlan(int board_n, int env_kind, int num_simulation, const HeadP
     const int cpl = rulesArg(env_kind, board_n);
     size_t tile_bytes = 0;
     int rc = MZ_OK, spec_words = kSpecWords;
-    if (!simWideAny(H, W, c0q, C, cpl, nullptr, 0, nullptr, 0, 0, 0, 0, 0, nullptr, &tile_bytes, &rc, &spec_words)) { return false; }
+    if (precision_ == 1 && !bf16Supported()) { return false; }
+    if (!simWideAny(H, W, c0q, C, cpl, precision_, nullptr, 0, nullptr, 0, 0, 0, 0, 0, nullptr, &tile_bytes, &rc, &spec_words)) { return false; }
     const size_t rcp_n = size_t(num_simulation) + 5, max_depth = size_t(num_simulation) + 3, A = desc_.action_size;
     const size_t heads = (size_t(hp.PC) * hp.P + hp.P + hp.VH + hp.A + 16) * sizeof(float);
     size_t need = tile_bytes + rcp_n * sizeof(double) + (2 * max_depth + 2 + ((simXchgWords(int(A), channels, W32) + 1) & ~size_t(1))) * sizeof(float) + heads + 16;
@@ -59,7 +61,7 @@ int Net::simLaunchWide(const SimArgs& a, const GoDevView& gv, int max_depth, con
     if (rc) { return rc; }
     int c0q = 16 * repr_[0].cq;
     const int H = desc_.hidden_channel_height, W = desc_.hidden_channel_width, C = desc_.num_hidden_channels;
-    if (simWideAny(H, W, c0q, C, rulesArg(gv.kind, gv.n), reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, host_start ? 1 : 0, lf, lds, stream_, nullptr, &rc)) {
+    if (simWideAny(H, W, c0q, C, rulesArg(gv.kind, gv.n), precision_, reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, host_start ? 1 : 0, lf, lds, stream_, nullptr, &rc)) {
         *launched = rc == MZ_OK;
     }
     return rc;

@@ -161,6 +161,7 @@ def main():
     moves_override = None
     extra_conf = ""
     threads = None
+    precision = None
     keys = []
     i = 0
     while i < len(argv):
@@ -170,13 +171,23 @@ def main():
             extra_conf = ":" + argv[i + 1]; i += 2
         elif argv[i] == "--threads":  # zero_num_threads of every worker (1 = the host budget of one rank of eight on a 16-CPU quota)
             threads = int(argv[i + 1]); i += 2
+        elif argv[i] == "--precision":  # the tower's arithmetic for every worker: f32 (default) or bf16x3 (opt-in; refused by the shapes it is not built for)
+            if argv[i + 1] not in ("f32", "bf16x3"):
+                sys.exit("--precision f32|bf16x3")
+            precision = argv[i + 1]; i += 2
         elif argv[i] == "--out":
             out_path = argv[i + 1]; i += 2
         else:
             keys.append(argv[i]); i += 1
+    if precision:
+        extra_conf += ":mz_nn_precision=" + precision
     out = {}
     for key in keys or ["c1", "c2", "c3", "c4", "c5"]:
         out[key] = run_config(key, moves_override, threads, extra_conf)
+        if precision:
+            out[key]["precision"] = precision
+            if precision == "bf16x3" and out[key]["roofline"]["kernel"]:
+                out[key]["roofline"]["kernel"] = out[key]["roofline"]["kernel"].replace("sim_kernel_wide<", "sim_kernel_wide_bf16<")
         print(key, json.dumps(out[key]), flush=True)
     os.makedirs(os.path.dirname(out_path) or ".", exist_ok=True)
     json.dump(out, open(out_path, "w"), indent=1)
