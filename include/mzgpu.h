@@ -96,6 +96,9 @@ int mz_net_get_desc(const mz_net* net, mz_net_desc* out);
 /* AlphaZeroNetwork::forward() (ref network/alphazero_network.h:63-104): features [B][C_in][H][W] f32
  * -> policy[B][A] (softmax), policy_logit[B][A], value[B].  Blocking. */
 int mz_net_forward_az(mz_net* net, const float* features, int batch, float* policy, float* policy_logit, float* value, int where);
+/* test access to what the heads read: the representation tower alone (AlphaZero networks), at the network's current precision, on host features
+ * [B][C_in][H][W] f32 -> out [B][C][h*w] f32 (host), the activations after the last residual block.  Blocking. */
+int mz_net_tower_az(mz_net* net, const float* features, int batch, float* out);
 /* MuZeroNetwork::initialInference() (ref muzero_network.h:97-104, muzero_network.py:137-143):
  * hidden_state[B][C][h][w] is also returned */
 int mz_net_initial(mz_net* net, const float* features, int batch, float* policy, float* policy_logit, float* value, float* hidden_state,

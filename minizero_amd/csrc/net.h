@@ -85,6 +85,7 @@ public:
                   float* d_logit, float* d_value, float* d_reward, float* d_hidden_dst, const int* d_dst_idx);
     // host/device wrappers used by the C ABI
     int forwardAZ_any(const float* feat, int B, float* policy, float* logit, float* value, int where);
+    int towerAZ_host(const float* feat, int B, float* out); // test access (mz_net_tower_az): runTrunk on the representation tower alone, out [B][C][P] on the host
     int initial_any(const float* feat, int B, float* policy, float* logit, float* value, float* hidden, int where);
     int recurrent_any(const float* hidden_in, const float* action, int B, float* policy, float* logit, float* value, float* reward, float* hidden_out,
                       int where);

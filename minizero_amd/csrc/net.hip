@@ -551,6 +551,22 @@ int Net::forwardAZ_any(const float* feat, int B, float* policy, float* logit, fl
     return MZ_OK;
 }
 
+int Net::towerAZ_host(const float* feat, int B, float* out)
+{
+    if (B <= 0 || !feat || !out) { setError("tower: bad arguments"); return MZ_ERR_ARG; }
+    if (desc_.type != 0) { setError("tower() called on a %s network", desc_.type == 1 ? "muzero" : "muzero_atari"); return MZ_ERR_STATE; }
+    MZ_HIP(hipSetDevice(device_));
+    MZ_ENSURE(io_in_, size_t(B) * featSize());
+    MZ_HIP(hipMemcpyAsync(io_in_.p, feat, size_t(B) * featSize() * sizeof(float), hipMemcpyHostToDevice, stream_));
+    int rc = ensureBatch(B);
+    if (rc) { return rc; }
+    float* x = nullptr;
+    if ((rc = runTrunk(repr_, io_in_.p, B, &x))) { return rc; }
+    MZ_HIP(hipMemcpyAsync(out, x, size_t(B) * hiddenSize() * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    MZ_HIP(hipStreamSynchronize(stream_));
+    return MZ_OK;
+}
+
 int Net::initial_any(const float* feat, int B, float* policy, float* logit, float* value, float* hidden, int where)
 {
     if (B <= 0 || !feat || !policy || !logit || !value || !hidden) { setError("initialInference: bad arguments"); return MZ_ERR_ARG; }
@@ -690,3 +706,11 @@ int Net::timeTowerConv(int B, int iters, float* ms_per_launch, double* flops_per
 }
 
 } // namespace mz
+
+// defined here, beside the tower, so that the host-only builds of the C surface (capi.cpp over a stand-in device) need nothing of it
+struct mz_net { mz::Net net; };
+extern "C" int mz_net_tower_az(mz_net* net, const float* features, int batch, float* out)
+{
+    if (!net) { mz::setError("NULL network"); return MZ_ERR_ARG; }
+    return net->net.towerAZ_host(features, batch, out);
+}

@@ -100,6 +100,7 @@ def load():
     L.mz_net_get_desc.argtypes = [vp, C.POINTER(NetDesc)]
     L.mz_net_set_precision.argtypes = [vp, C.c_int]
     L.mz_net_forward_az.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int]
+    L.mz_net_tower_az.argtypes = [vp, vp, C.c_int, vp]
     L.mz_net_initial.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_int]
     L.mz_net_recurrent.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_int]
     L.mz_net_time_forward.argtypes = [vp, C.c_int, C.c_int, fp, fp, C.POINTER(C.c_double)]
@@ -302,6 +303,14 @@ class Net:
         p, l, v = np.empty((B, A), np.float32), np.empty((B, A), np.float32), np.empty(B, np.float32)
         _check(self.L, self.L.mz_net_forward_az(self.h, x.ctypes.data, B, p.ctypes.data, l.ctypes.data, v.ctypes.data, MZ_HOST))
         return p, l, v
+
+    def tower(self, features):
+        """the representation tower alone, at the current precision: the activations the heads read, [B][C][h * w]"""
+        x = np.ascontiguousarray(features, np.float32)
+        d = self.desc
+        out = np.empty((x.shape[0], d.num_hidden_channels, d.hidden_channel_height * d.hidden_channel_width), np.float32)
+        _check(self.L, self.L.mz_net_tower_az(self.h, x.ctypes.data, x.shape[0], out.ctypes.data))
+        return out
 
     def initial_inference(self, features):
         x = np.ascontiguousarray(features, np.float32)

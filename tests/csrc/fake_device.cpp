@@ -432,3 +432,6 @@ int GoDevice::candAsync(Pool&, const float*, const float*, const float*, const R
 int GoDevice::readLeaf(uint32_t*, uint8_t*, int*, float*, int*) { return refuse("the device rules"); }
 
 } // namespace mz
+
+// test access to the tower (net.hip on the real device): the stand-in has no tower to show
+extern "C" int mz_net_tower_az(mz_net*, const float*, int, float*) { mz::setError("fake device: mz_net_tower_az is not served"); return MZ_ERR_DEVICE; }

@@ -1,7 +1,8 @@
 """GPU tests of the opt-in `bf16x3` tower for 128 and 256 hidden channels (9x9 Go AlphaZero; net_bf16_wide_body.h: one LDS tile, layers in place) — the
 stand-alone forward against the f32 HIP path and the CPU oracle at the north star's 1e-3, and the worker: the per-game simulation kernel
 (sim_kernel_wide_bf16) must write byte for byte the records of the lock-step mode on the same tower.  Not bit-exact against the oracle by design (the
-summation order inside a K = 32 MFMA cannot be mirrored on the CPU); the default stays f32."""
+summation order inside a K = 32 MFMA cannot be mirrored on the CPU); the default stays f32.  (Where nothing rounds the order does not matter:
+tests/test_gpu_bf16_exact.py checks both bf16x3 bodies bit for bit on exactly representable networks.)"""
 import functools
 import re
 
