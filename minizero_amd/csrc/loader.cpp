@@ -296,6 +296,25 @@ bool Loader::parse(const std::string& content, LGame* g)
         for (int i = 0; i < n; ++i) {
             if (g->player[i] != 1 + (i & 1)) { setError("loader: move %d of a record is played by %s, the device replay needs alternating colours from B", i, g->player[i] == 1 ? "B" : g->player[i] == 2 ? "W" : "nobody"); return false; }
         }
+        // The device replay applies every move as it stands: the reference's replay calls act(), which refuses an illegal move and leaves the position
+        // alone (base_env.h:235-241, go.cpp:134), so a record with an illegal move (hand-edited or damaged files: self-play never writes one) would give
+        // other planes there.  The record is replayed once on the host engine and refused by name at the first move the rules reject.
+        if (proto_->deviceKind() == kGo && n > 2 * P_ + 1) { setError("loader: a record of %d moves, a game of Go on this board ends after %d", n, 2 * P_ + 1); return false; } // (also the bound of the host engine's table of seen positions)
+        std::unique_ptr<GameEnv> env = proto_->clone();
+        std::vector<float> planes;
+        for (int i = 0; i < n; ++i) {
+            const int a = g->action[i];
+            if (env->act(a, g->player[i])) { continue; }
+            const char* why = "not allowed by the rules";
+            planes.resize(feat_size_);
+            env->features(0, planes.data()); // planes 0 and 1: the stones of the player to move and of the other one, in all five games
+            if (a >= P_) { why = "pass while a move exists"; }
+            else if (planes[a] != 0.0f || planes[P_ + a] != 0.0f) { why = "occupied point"; }
+            else if (proto_->deviceKind() == kGo) { why = "suicide or repeated position"; }
+            else if (proto_->deviceKind() == kOthello) { why = "flips no stone"; }
+            setError("loader: move %d of a record is illegal (%s), the device replay needs legal moves", i, why);
+            return false;
+        }
     }
     // getReturn() = stof(RE) (base_env.h:300); only read for board games, but every record carries it
     if (const std::string* re = tag("RE")) { if (!parseFloat(*re, &g->ret)) { g->ret = 0.0f; } }

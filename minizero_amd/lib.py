@@ -189,6 +189,11 @@ def _err(L):
     return (L.mz_last_error() or b"").decode(errors="replace")
 
 
+def last_error():
+    """the text of the calling thread's last libmzgpu error (mz_last_error): why a call returned an error code, or why add_record skipped a record"""
+    return _err(load())
+
+
 def _check(L, rc):
     if rc < 0:
         raise MzError(f"libmzgpu error {rc}: {_err(L)}")

@@ -225,6 +225,8 @@ class OracleLoader:
             self.h = None
 
     def load_data_from_file(self, path): self.L.mzo_loader_load_file(self.h, path.encode())
+    def add_record(self, line): return self.L.mzo_loader_add(self.h, line.encode())  # one record; finish() after the last one, as load_data_from_file does
+    def finish(self): self.L.mzo_loader_finish(self.h)
     def num_data(self): return self.L.mzo_loader_num_data(self.h)
     def num_games(self): return self.L.mzo_loader_num_games(self.h)
 
