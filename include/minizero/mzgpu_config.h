@@ -67,6 +67,8 @@ inline std::string mzgpuCollectConfiguration()
 #undef MZGPU_KEY
 #if defined(GO) && GO
     o << "env_game=go";
+#elif defined(NOGO) && NOGO
+    o << "env_game=nogo"; // Go's keys (env_go_komi goes into the record's KM tag only, env_go_ko_rule is not read: ref nogo.h)
 #elif defined(OTHELLO) && OTHELLO
     o << "env_game=othello";
 #elif defined(GOMOKU) && GOMOKU

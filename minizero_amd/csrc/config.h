@@ -57,7 +57,7 @@ struct WorkerConfig {
     bool env_gomoku_exactly_five_stones = true;
     bool env_hex_use_swap_rule = true; // env_game=hex only (ref hex.cpp:28-47): the second action may take over the first stone
     // run-time replacements of the reference's compile-time switches (-D<GAME>, #if ATARI in mcts.cpp:211)
-    std::string env_game = "tictactoe";
+    std::string env_game = "tictactoe"; // tictactoe | go | nogo | othello | gomoku | hex | atari (env.h EnvOptions)
     bool atari_init_q = false;
     std::string env_atari_name = "ms_pacman";
     int env_atari_episode_length = 1000; // synthetic Atari-shaped environment: steps per episode

@@ -1,4 +1,5 @@
 // Host rules engines of libmzgpu — see env.h.  Not a translation of the reference's data structures:
+//   NoGo    : Go's board and planes, rules of its own (no capture, no suicide, no pass): flat byte board + early-exit flood fills.
 //   Go      : flat byte board + on-demand early-exit flood fills for captures (no incremental blocks /
 //             liberty bitsets / areas / Benson), one whole-board group pass only when a legal mask is
 //             needed, positional-superko set as a small open-addressing table that is copied with the env,
@@ -856,6 +857,149 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------
+// NoGo (ref nogo.h:18-86: NoGoEnv derives from GoEnv): Go's board, actions, planes and records with other rules — a move must neither capture
+// nor be suicide, nothing is ever removed, there is no pass, and the player to move without a legal point has lost.  A rules variant of Go's row
+// of game_kind.h (kNoGo).  Flat byte board + early-exit flood fills like Go; no hash, no superko set, no score.
+// ---------------------------------------------------------------------------------------------
+class NoGo final : public GameEnv {
+public:
+    NoGo(int n, float komi) : n_(n), P_(n * n), komi_(komi), st_(goStatic(n))
+    {
+        rot_ = rotationTables(n, n * n + 1);
+        reset();
+    }
+    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<NoGo>(*this); }
+    void copyFrom(const GameEnv& o) override { *this = static_cast<const NoGo&>(o); }
+    void reset() override
+    {
+        turn_ = 1;
+        action_ids_.clear();
+        action_players_.clear();
+        memset(board_, 0, sizeof(board_));
+        hist_len_ = 0;
+        for (auto& h : hist_) { h[0].clear(); h[1].clear(); }
+        stones_[0].clear();
+        stones_[1].clear();
+    }
+    // liberties of the block at `start`, counted up to `cap`
+    int liberties(int start, int cap) const
+    {
+        uint8_t mark[kMaxP];
+        int16_t grp[kMaxP];
+        memset(mark, 0, P_);
+        const uint8_t color = board_[start];
+        int head = 0, tail = 0, libs = 0;
+        grp[tail++] = static_cast<int16_t>(start);
+        mark[start] = 1;
+        while (head < tail) {
+            const int p = grp[head++];
+            for (int k = 0; k < st_->nnbr[p]; ++k) {
+                const int q = st_->nbr[p][k];
+                if (mark[q]) { continue; }
+                mark[q] = 1;
+                if (board_[q] == 0) { if (++libs >= cap) { return libs; } }
+                else if (board_[q] == color) { grp[tail++] = static_cast<int16_t>(q); }
+            }
+        }
+        return libs;
+    }
+    bool isLegal(int a, int player) const override // ref nogo.h:25-57
+    {
+        if (a < 0 || a >= P_ || board_[a] != 0) { return false; } // (the pass slot of the policy is never legal: nogo.h:30)
+        bool ok = false;
+        for (int k = 0; k < st_->nnbr[a]; ++k) {
+            const int q = st_->nbr[a][k];
+            if (board_[q] == 0) { ok = true; continue; }
+            const int libs = liberties(q, 2);
+            if (board_[q] == player) { ok |= libs > 1; }
+            else if (libs == 1) { return false; } // its last liberty is `a`: the move would capture
+        }
+        return ok; // else suicide: no empty neighbour and no own block that keeps a liberty
+    }
+    void legalMask(uint8_t* out) const override
+    {
+        for (int a = 0; a < P_; ++a) { out[a] = isLegal(a, turn_); }
+        out[P_] = 0;
+    }
+    bool act(int a, int player) override
+    {
+        if (!isLegal(a, player)) { return false; }
+        actUnchecked(a, player);
+        return true;
+    }
+    void actUnchecked(int a, int player) override // GoEnv::act (ref go.cpp:132-190) of a move that captures nothing
+    {
+        action_ids_.push_back(static_cast<int16_t>(a));
+        action_players_.push_back(static_cast<uint8_t>(player));
+        turn_ = 3 - player;
+        if (a >= 0 && a < P_) {
+            board_[a] = static_cast<uint8_t>(player);
+            stones_[player - 1].set(a);
+        }
+        hist_[hist_len_ & 7][0] = stones_[0];
+        hist_[hist_len_ & 7][1] = stones_[1];
+        ++hist_len_;
+    }
+    bool isTerminal() const override // ref nogo.h:59-66
+    {
+        for (int a = 0; a < P_; ++a) { if (isLegal(a, turn_)) { return false; } }
+        return true;
+    }
+    float evalScore(bool) const override { return scoreOf(3 - turn_); } // ref nogo.h:68-76: the player not to move, resign or not
+    void features(int r, float* out) const override // GoEnv::getFeatures (ref go.cpp:280-308)
+    {
+        const int* map = rot_->inv[r].data();
+        for (int k = 0; k < 8; ++k) {
+            float* own = out + (2 * k) * P_;
+            float* opp = own + P_;
+            if (hist_len_ - 1 - k < 0) {
+                memset(own, 0, 2 * P_ * sizeof(float));
+                continue;
+            }
+            const Bits* h = hist_[(hist_len_ - 1 - k) & 7];
+            const Bits& mine = h[turn_ - 1];
+            const Bits& theirs = h[2 - turn_];
+            for (int p = 0; p < P_; ++p) {
+                own[p] = mine.test(map[p]) ? 1.0f : 0.0f;
+                opp[p] = theirs.test(map[p]) ? 1.0f : 0.0f;
+            }
+        }
+        const float b = turn_ == 1 ? 1.0f : 0.0f, w = turn_ == 2 ? 1.0f : 0.0f;
+        for (int p = 0; p < P_; ++p) { out[16 * P_ + p] = b; out[17 * P_ + p] = w; }
+    }
+    GameKind deviceKind() const override { return kNoGo; }
+    void exportDeviceRoot(void* dst) const override // (go_body.h nogoLeafBody: the stones, the ring of past positions, the player to move)
+    {
+        static_assert(kWords == kGoMaxW, "device snapshot layout");
+        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
+        memcpy(s.stones, stones_, sizeof(s.stones));
+        memcpy(s.hist, hist_, sizeof(s.hist));
+        s.hash = 0;
+        s.hist_len = hist_len_;
+        s.turn = turn_;
+        s.nmoves = static_cast<int32_t>(action_ids_.size());
+        s.passes = 0;
+    }
+    int numInputChannels() const override { return 18; }
+    int boardSize() const override { return n_; }
+    int policySize() const override { return P_ + 1; }
+    std::string name() const override { return "nogo_" + std::to_string(n_) + "x" + std::to_string(n_); }
+    std::vector<std::pair<std::string, std::string>> loaderTags() const override // the loader is Go's (ref nogo.h:88, go.h:127-133)
+    {
+        return {{"SZ", std::to_string(n_)}, {"KM", std::to_string(komi_)}};
+    }
+
+private:
+    int n_, P_;
+    float komi_; // carried in the KM tag only
+    const GoStatic* st_;
+    uint8_t board_[kMaxP];
+    Bits stones_[2];
+    Bits hist_[8][2];
+    int hist_len_;
+};
+
+// ---------------------------------------------------------------------------------------------
 // Atari-shaped synthetic environment (BASELINE configs[4]; ALE, OpenCV and the ROMs are not available).
 // Feature contract of the reference's AtariEnv (ref atari.h:17-27, atari.cpp:48-131): 1 player, 18 actions all legal,
 // features = for the last 8 steps [1 plane action_id / 18, 3 planes RGB / 255 of a 96x96 screen], oldest first.
@@ -1047,7 +1191,7 @@ std::unique_ptr<GameEnv> createGameEnv(const EnvOptions& o)
 {
     if (o.game == "atari") { return std::make_unique<AtariSynth>(o.atari_name, o.atari_episode_length, std::max<size_t>(1, o.atari_recent_observations)); }
     const GameKind k = gameFromName(o.game.c_str());
-    if (k == kNoDeviceGame) { setError("unknown env_game '%s' (tictactoe | go | othello | gomoku | hex | atari)", o.game.c_str()); return nullptr; }
+    if (k == kNoDeviceGame) { setError("unknown env_game '%s' (tictactoe | go | nogo | othello | gomoku | hex | atari)", o.game.c_str()); return nullptr; }
     const int n = o.board_size > 0 ? o.board_size : gameDefaultBoard(k);
     switch (k) {
     case kTicTacToe: return std::make_unique<TicTacToe>();
@@ -1058,6 +1202,9 @@ std::unique_ptr<GameEnv> createGameEnv(const EnvOptions& o)
         if (n < 2 || n > kMaxN) { setError("go board size %d not supported (2..19)", n); return nullptr; }
         if (o.go_ko_rule != "positional" && o.go_ko_rule != "situational") { setError("env_go_ko_rule '%s' not supported (positional | situational, ref go.cpp:47)", o.go_ko_rule.c_str()); return nullptr; }
         return std::make_unique<Go>(n, o.go_komi, o.go_ko_rule == "situational");
+    case kNoGo: // ref nogo.h:12,22: 9x9; the smaller boards are for tests.  env_go_ko_rule is not read: nothing is captured, no position repeats
+        if (n < 2 || n > kNoGoMaxBoard) { setError("nogo board size %d not supported (2..%d)", n, kNoGoMaxBoard); return nullptr; }
+        return std::make_unique<NoGo>(n, o.go_komi);
     case kGomoku: // ref gomoku.h:13,21,44
         if (n > kMaxN) { setError("gomoku board size %d not supported (up to 19)", n); return nullptr; }
         return std::make_unique<Gomoku>(n, o.gomoku_rule == "outer_open", o.gomoku_exactly_five);

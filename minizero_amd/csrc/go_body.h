@@ -935,14 +935,161 @@ __device__ __forceinline__ void hexLeafBody(const GoDevView& v, const PoolView& 
     }
 }
 
+// ---- NoGo (ref nogo.h:25-76; a rules variant of Go, game_kind.h kNoGo): boards up to 9x9, so a position is two bitboards of two words, and the slot layout is
+// Gomoku's — the `stones` words, `meta` (moves played, unused).  Nothing is ever captured: the leaf is its parent's stones plus one, and the position k moves
+// before the leaf is the slot of the k-th ancestor (older than the root: the root's ring), as in Go.  The legal mask needs the liberties of whole blocks and no
+// block ids: every lane that holds a stone floods its OWN block — dilate by the four shifts, mask with the colour's stones, until no lane's block grows — and
+// counts popc(dilate(block) & empty).  A ballot of the enemy stones whose block has one liberty, dilated onto the empty points, is the set of capturing moves
+// (an empty point next to such a stone IS that liberty); a ballot of the own stones whose block has two or more, dilated, together with dilate(empty), is the
+// set of moves that are no suicide.  Terminal <=> the mask is empty; the result is the player not to move.
+struct NoGoMasks { unsigned long long full[2], ncl[2], ncr[2]; int n; }; // on the board; not column 0; not column n - 1
+__device__ __forceinline__ void nogoDilate(const NoGoMasks& k, const unsigned long long (&b)[2], unsigned long long (&out)[2])
+{
+    const int n = k.n; // 2 <= n <= 9: every shift count below is in 1 .. 63
+    const unsigned long long up1[2] = {b[0] << 1, (b[1] << 1) | (b[0] >> 63)}, dn1[2] = {(b[0] >> 1) | (b[1] << 63), b[1] >> 1};
+    const unsigned long long upn[2] = {b[0] << n, (b[1] << n) | (b[0] >> (64 - n))}, dnn[2] = {(b[0] >> n) | (b[1] << (64 - n)), b[1] >> n};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) { out[i] = ((up1[i] & k.ncl[i]) | (dn1[i] & k.ncr[i]) | upn[i] | dnn[i]) & k.full[i]; }
+}
+__device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
+{
+    const unsigned lo = __shfl(static_cast<unsigned>(v), src), hi = __shfl(static_cast<unsigned>(v >> 32), src);
+    return (static_cast<uint64_t>(hi) << 32) | lo;
+}
+
+__device__ __forceinline__ void nogoLeafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane)
+{
+    const int P = v.P, n = v.n, W = v.W, MD = pv.max_depth; // W <= 2 (GoDevice::init: boards up to kNoGoMaxBoard)
+    const int len = pv.path_len[g];
+    const int* path = pv.path + size_t(g) * MD;
+    const int* pact = pv.path_action + size_t(g) * MD;
+    const int depth = len - 1;
+    const GoRootSnapshot& S = v.snap[g];
+    const int root_turn = S.turn, root_hist_len = S.hist_len;
+    const size_t sb = size_t(g) * v.slots;
+    const int* hs = pv.hslot + size_t(g) * pv.cap;
+    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    unsigned long long st[2][2]; // [colour][word]
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        st[0][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 0) * W + i]) : 0ull;
+        st[1][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 1) * W + i]) : 0ull;
+    }
+    int nmoves = v.meta[(sb + src) * 2];
+    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
+    if (depth >= 1) { // GoEnv::act of a move that captures nothing (ref go.cpp:132-190): the stone is placed
+        const int a = pact[len - 1], m = 3 - t; // moved by the other player
+        ++nmoves;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) { // (selects, never a dynamic register index)
+            const unsigned long long bit = (a < P && i == (a >> 6)) ? 1ull << (a & 63) : 0ull;
+            st[0][i] |= m == 1 ? bit : 0ull;
+            st[1][i] |= m == 2 ? bit : 0ull;
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (i < W) {
+                    v.stones[((sb + slot) * 2 + 0) * W + i] = st[0][i];
+                    v.stones[((sb + slot) * 2 + 1) * W + i] = st[1][i];
+                }
+            }
+            v.meta[(sb + slot) * 2] = nmoves;
+            v.meta[(sb + slot) * 2 + 1] = 0;
+        }
+    }
+    NoGoMasks k;
+    k.n = n;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int p = 64 * i + lane, x = p % n;
+        k.full[i] = __ballot(p < P);
+        k.ncl[i] = __ballot(p < P && x != 0);
+        k.ncr[i] = __ballot(p < P && x != n - 1);
+    }
+    const unsigned long long empty[2] = {k.full[0] & ~(st[0][0] | st[1][0]), k.full[1] & ~(st[0][1] | st[1][1])};
+    // ---- the block of the lane's stone in each word (point 64 * i + lane), flooded; safe[i] / atari[i]: the stones of player t whose block has >= 2 liberties,
+    // the stones of the other player whose block has exactly one
+    unsigned long long safe[2] = {0, 0}, atari[2] = {0, 0};
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        if (i >= W) { continue; }
+        const bool isb = (st[0][i] >> lane) & 1, isw = (st[1][i] >> lane) & 1, has = isb || isw;
+        const unsigned long long mine[2] = {isb ? st[0][0] : st[1][0], isb ? st[0][1] : st[1][1]}; // the stones of the lane's colour
+        unsigned long long blk[2] = {(has && i == 0) ? 1ull << lane : 0ull, (has && i == 1) ? 1ull << lane : 0ull}, d[2];
+        for (int round = 0; round < P; ++round) { // (a block's diameter is below P: the bound is never what ends the loop)
+            nogoDilate(k, blk, d);
+            const unsigned long long g0 = d[0] & mine[0] & ~blk[0], g1 = d[1] & mine[1] & ~blk[1];
+            blk[0] |= g0; blk[1] |= g1;
+            if (__ballot((g0 | g1) != 0) == 0) { break; }
+        }
+        nogoDilate(k, blk, d);
+        const int libs = __popcll(d[0] & empty[0]) + __popcll(d[1] & empty[1]);
+        const int colour = isb ? 1 : 2;
+        safe[i] = __ballot(has && colour == t && libs >= 2);
+        atari[i] = __ballot(has && colour != t && libs == 1);
+    }
+    unsigned long long dsafe[2], datari[2], dempty[2];
+    nogoDilate(k, safe, dsafe);
+    nogoDilate(k, atari, datari);
+    nogoDilate(k, empty, dempty);
+    const unsigned long long legal[2] = {empty[0] & (dempty[0] | dsafe[0]) & ~datari[0], empty[1] & (dempty[1] | dsafe[1]) & ~datari[1]};
+    const bool terminal = (legal[0] | legal[1]) == 0; // ref nogo.h:59-66
+    if (lane == 0) { // (the pass slot, bit P, is never legal: nogo.h:30)
+        v.legal[size_t(g) * v.LW] = legal[0];
+        if (v.LW > 1) { v.legal[size_t(g) * v.LW + 1] = legal[1]; }
+    }
+    // ---- planes (ref go.cpp:280-308): 2k / 2k+1 = own / opponent stones k moves before the leaf under the rotation, 16 / 17 = black / white to move.  Lane j < 16 * W
+    // holds word j of the history block [8][2][W]; a point's bit is fetched from the lane of its word
+    {
+        const int avail = root_hist_len + depth;
+        uint64_t hw = 0;
+        if (lane < 16 * W) {
+            const int kk = lane / (2 * W), cw = lane % (2 * W);
+            if (kk < avail) {
+                if (kk == 0) { hw = cw / W == 0 ? (cw % W == 0 ? st[0][0] : st[0][1]) : (cw % W == 0 ? st[1][0] : st[1][1]); }
+                else if (kk < depth) { hw = v.stones[(sb + hs[path[len - 1 - kk]]) * 2 * W + cw]; }
+                else { hw = S.hist[(root_hist_len - 1 - (kk - depth)) & 7][cw / W][cw % W]; }
+            }
+        }
+        const uint16_t* map = v.inv + size_t(rot) * P;
+        uint32_t* out = v.feat + size_t(g) * 18 * v.W32;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            if (i >= W) { continue; }
+            const int p = 64 * i + lane;
+            const int q = p < P ? map[p] : 0;
+            uint64_t mine = 0; // lane ch keeps plane ch's word
+            for (int ch = 0; ch < 16; ++ch) {
+                const int kk = ch >> 1, colour = (ch & 1) == 0 ? t - 1 : 2 - t;
+                const uint64_t word = shfl64(hw, (kk * 2 + colour) * W + (q >> 6));
+                const uint64_t bal = __ballot(p < P && ((word >> (q & 63)) & 1));
+                if (lane == ch) { mine = bal; }
+            }
+            if (lane == 16) { mine = t == 1 ? k.full[i] : 0; }
+            if (lane == 17) { mine = t == 2 ? k.full[i] : 0; }
+            if (lane < 18) {
+                if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(mine); }
+                if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(mine >> 32); }
+            }
+        }
+    }
+    if (lane == 0) {
+        v.leaf_player[g] = t;
+        v.terminal[g] = terminal ? 1 : 0;
+        v.eval[g] = t == 2 ? 1.0f : -1.0f; // ref nogo.h:68-76: the player not to move
+    }
+}
+
 // leafBody<CPL> of the two-bitboard games (the template arguments behind CPL, `smem` and `seen_lds` are Go's: unused here)
 template <int CPL, bool EXT_PLANES = false, int PART = 0, bool SYNC = false, int ROLE = 0, std::enable_if_t<(CPL <= 0), int> = 0>
 __device__ __forceinline__ void leafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane, uint64_t* = nullptr, const uint64_t* = nullptr)
 {
-    static_assert(CPL == kRulesTicTacToe || CPL == kRulesOthello || CPL == kRulesGomoku || CPL == kRulesHex, "no leaf body for this rules argument");
+    static_assert(CPL == kRulesTicTacToe || CPL == kRulesOthello || CPL == kRulesGomoku || CPL == kRulesHex || CPL == kRulesNoGo, "no leaf body for this rules argument");
     if constexpr (CPL == kRulesTicTacToe) { tttLeafBody(v, pv, rot, slot, g, lane); }
     else if constexpr (CPL == kRulesOthello) { othLeafBody(v, pv, rot, slot, g, lane); }
     else if constexpr (CPL == kRulesGomoku) { gmkLeafBody(v, pv, rot, slot, g, lane); }
+    else if constexpr (CPL == kRulesNoGo) { nogoLeafBody(v, pv, rot, slot, g, lane); }
     else { hexLeafBody(v, pv, rot, slot, g, lane); }
 }
 

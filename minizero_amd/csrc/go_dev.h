@@ -48,7 +48,7 @@ struct RotPack { uint32_t w[kRotPackGames / 10]; }; // per-game feature rotation
 inline void rotPackSet(RotPack& r, int g, int rot) { r.w[g / 10] = (r.w[g / 10] & ~(7u << (3 * (g % 10)))) | (uint32_t(rot) << (3 * (g % 10))); }
 
 struct GoDevView {
-    int kind;                  // GameKind (game_kind.h); all but Go: two bitboards + two `meta` words per slot, no hash / group ids; same outputs
+    int kind;                  // GameKind (game_kind.h; a rules variant travels here as its own value: kNoGo); all but Go: two bitboards + two `meta` words per slot, no hash / group ids; same outputs
     int channels;              // feature planes of the game (gameChannels)
     int games, n, P, W, A, slots, Ppad, W32, LW;
     float komi;
@@ -103,7 +103,7 @@ inline bool forRulesArg(int cpl, F&& f)
     switch (cpl) {
 #define MZ_RULES_CASE(K) case K: f(std::integral_constant<int, K>{}); return true;
         MZ_RULES_CASE(1) MZ_RULES_CASE(2) MZ_RULES_CASE(3) MZ_RULES_CASE(4) MZ_RULES_CASE(5) MZ_RULES_CASE(6)
-        MZ_RULES_CASE(kRulesOthello) MZ_RULES_CASE(kRulesTicTacToe) MZ_RULES_CASE(kRulesGomoku) MZ_RULES_CASE(kRulesHex)
+        MZ_RULES_CASE(kRulesOthello) MZ_RULES_CASE(kRulesTicTacToe) MZ_RULES_CASE(kRulesGomoku) MZ_RULES_CASE(kRulesHex) MZ_RULES_CASE(kRulesNoGo)
 #undef MZ_RULES_CASE
     default: return false;
     }

@@ -308,9 +308,10 @@ bool Loader::parse(const std::string& content, LGame* g)
             const char* why = "not allowed by the rules";
             planes.resize(feat_size_);
             env->features(0, planes.data()); // planes 0 and 1: the stones of the player to move and of the other one, in all five games
-            if (a >= P_) { why = "pass while a move exists"; }
+            if (a >= P_) { why = proto_->deviceKind() == kNoGo ? "NoGo has no pass" : "pass while a move exists"; }
             else if (planes[a] != 0.0f || planes[P_ + a] != 0.0f) { why = "occupied point"; }
             else if (proto_->deviceKind() == kGo) { why = "suicide or repeated position"; }
+            else if (proto_->deviceKind() == kNoGo) { why = "captures or is suicide"; }
             else if (proto_->deviceKind() == kOthello) { why = "flips no stone"; }
             setError("loader: move %d of a record is illegal (%s), the device replay needs legal moves", i, why);
             return false;

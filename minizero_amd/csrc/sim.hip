@@ -678,6 +678,8 @@ bool Net::hasSimKernel(int board_n, int env_kind, int num_simulation) const
     if (H == h && W == w && c0 == cin0 && C == cpad && board_n == h && rulesArg(env_kind, h) == cpl) { return true; }
     MZ_SIM_CASES(MZ_SIM_HAS)
 #undef MZ_SIM_HAS
+    // the rules variants of a row (sim_nogo.hip): f32 towers only — with bf16x3 the pool plays in the lock-step mode on the device rules
+    if (isGameVariant(env_kind) && precision_ == 0 && simVariantKernel(H, W, c0, C, board_n, rulesArg(env_kind, board_n), nullptr, 0, nullptr, 0, 0, 0, 0, nullptr, nullptr)) { return true; }
     return false;
 }
 
@@ -782,6 +784,10 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     if (H == h && W == w && c0 == cin0 && C == cpad && gv.n == h && rulesArg(gv.kind, gv.n) == cpl) { *launched = true; return launchSimT<h, w, cin0, cpad, cpl>(reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, start_bits, lds, stream_); }
     MZ_SIM_CASES(MZ_SIM_LAUNCH)
 #undef MZ_SIM_LAUNCH
+    if (isGameVariant(gv.kind) && simVariantKernel(H, W, c0, C, gv.n, rulesArg(gv.kind, gv.n), reinterpret_cast<const SimArgs*>(sim_args_.p), gv.games, d_rot, sim0, nsims, start_bits, lds, stream_, &rc)) {
+        *launched = rc == MZ_OK;
+        return rc;
+    }
     return MZ_OK;
 }
 

@@ -115,4 +115,8 @@ __device__ __forceinline__ PoolView simPathViewSafe(PoolView pv, int* lds_path, 
     return pv;
 }
 
+// the instances of sim_kernel for the rules variants of a row (sim_nogo.hip); d_args == nullptr: a query.  true: there is one (launched when d_args != nullptr, *rc = its status)
+bool simVariantKernel(int H, int W, int c0, int C, int board_n, int cpl, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, size_t lds,
+                      hipStream_t s, int* rc);
+
 } // namespace mz

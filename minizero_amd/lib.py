@@ -636,7 +636,7 @@ def godev_playout(board_size, komi, actions, root_prefix, rots, device=0):
 
 
 def envdev_playout(game, board_size, komi, actions, root_prefix, rots, channels, num_actions, device=0):
-    """Device rules engine of `game` ("go", "othello", "tictactoe"): root = actions[:root_prefix] on the host engine, then one device move per
+    """Device rules engine of `game` ("go", "nogo", "othello", "tictactoe", "gomoku", "hex"): root = actions[:root_prefix] on the host engine, then one device move per
     remaining action.  Returns (feat_bits [steps][channels*W32], legal [steps][num_actions], terminal, eval, player)."""
     L = load()
     P = board_size * board_size

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Stand-alone cost of a device rules body per leaf: plays `moves` moves of 256 games in the lock-step mode (mz_sim_kernel=false), where every cycle is one launch of
-the game's leaf kernel (one wave per leaf: leaf_kernel<-3> for Hex, leaf_kernel<-2> for Gomoku — go_dev.hip leaf_kernel<rules argument>), so that a kernel trace of the run holds one duration per cycle, in playing order.
+the game's leaf kernel (one wave per leaf: leaf_kernel<-3> for Hex, leaf_kernel<-2> for Gomoku, leaf_kernel<-4> for NoGo — go_dev.hip leaf_kernel<rules argument>), so that a kernel trace of the run holds one duration per cycle, in playing order.
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/time_leaf_kernels.py run hex 100
     python tools/time_leaf_kernels.py report DIR 'leaf_kernel<-3>'
+NoGo: `run nogo 70` — a 9x9 game lasts 70 .. 79 moves, so the last third of the run is the late positions (long chains: the most flood rounds).
 `report` splits the launches of the named kernel into the first, middle and last third of the run (early, middle and late positions) and prints the median and the
 mean duration of each."""
 import csv
@@ -13,14 +14,14 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-GAMES = {"hex": ("hex_11x11", 11), "gomoku": ("gomoku_15x15", 15)}
+GAMES = {"hex": ("hex_11x11", 11, 4, 121), "gomoku": ("gomoku_15x15", 15, 4, 225), "nogo": ("nogo_9x9", 9, 18, 82)}  # name, board, planes, actions
 
 
 def run(game, moves, sims=16, games=256):
     import minizero_amd as mz
-    name, n = GAMES[game]
-    d = mz.make_desc(name, 4, n, n, 64, n, n, 1, 6, n * n)
-    conf = f"env_game={game}:actor_num_simulation={sims}:zero_num_parallel_games={games}:mz_sim_kernel=false:program_seed=1:nn_file_name=x.pt"
+    name, n, planes, actions = GAMES[game]
+    d = mz.make_desc(name, planes, n, n, 64, n, n, 1, 6, actions)
+    conf = f"env_game={game}:actor_resign_threshold=-2:actor_num_simulation={sims}:zero_num_parallel_games={games}:mz_sim_kernel=false:program_seed=1:nn_file_name=x.pt"
     wk = mz.Worker(conf, d, mz.generate_weights(d, 0))
     wk.command("start")
     cycles = moves * (sims + 1)
