@@ -226,7 +226,7 @@ int Pool::checkError()
     MZ_HIP(hipStreamSynchronize(stream_));
     if (e) {
         (void)hipMemsetAsync(game_i_.p + size_t(v_.games) * 3, 0, sizeof(int), stream_);
-        if (e >= 90 && e < 100) { // sim_cluster.h: 90 layer exchange, 91 placement (members on different XCDs), 92 command, 93 results, 94 octet exchange; sim_help.h: 95 layer exchange of a pair tower, 96 command
+        if (e >= 90 && e <= 100) { // sim_cluster.h: 90 layer exchange, 91 placement (members on different XCDs), 92 command, 93 results, 94 octet exchange; sim_help.h: 95 layer exchange of a pair tower, 96 command, 100 command of a lent tower
             setError("simulation kernel: a workgroup of a game's cluster did not arrive (wait %d timed out); the search state of this move is lost", e);
             return MZ_ERR_DEVICE;
         }

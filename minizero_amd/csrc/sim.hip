@@ -459,6 +459,7 @@ static int launchSimT(const SimArgs* d_args, int games, const uint8_t* d_rot, in
 // tail help (sim_help.h): launches shorter than this do not help, and a game with fewer simulations left than that is not claimed any more (a claim costs the
 // helper a scan of its XCD's games, ~2 us, and saves the owner ~50 us per simulation that runs the network: profiles/r08_pair_tower.txt)
 constexpr int kSimHelpMinLaunch = 64, kSimHelpMinLeft = 2;
+constexpr int kSimLendLead = 16; // lending (sim_help.h): simulations a game must trail by for another to lend it a tower (MZ_SIM_LEND_LEAD)
 
 #define MZ_SIM_CASES(X) \
     X(9, 9, 20, 64, 2)  /* 9x9 Go, 64 channels (BASELINE configs[1]) */ \
@@ -609,9 +610,10 @@ void Net::dumpSimProf()
             for (size_t g = 0; g < G; ++g) { tw += double(h[g * 8 + 1]); }
             // ("a pair tower" of the first line: a tower with at least one helper; the quad towers among them have the line after it)
             const double ran = sims_all - skipped, qn = double(tail[21]), qt = double(tail[22]), pn = double(tail[13]) + qn, pt = double(tail[14]) + qt;
+            const double ln = double(tail[33]), lt = double(tail[34]); // (towers lent by a volunteer are neither a helper's nor run alone: the line after these)
             fprintf(stderr, "[mz sim prof] tail help: %.0f of the %.0f simulations that ran the network had a pair tower (%.2f %%): tower %.2f us with a helper, %.2f us alone; %llu games helped, "
                             "a CU helps for %.1f us per launch after its own game (%.1f %% of the launch)\n",
-                    pn, ran, 100.0 * pn / std::max(1.0, ran), pt / std::max(1.0, pn) * 0.01, (tw - pt) / std::max(1.0, ran - pn) * 0.01, tail[15], helping,
+                    pn, ran, 100.0 * pn / std::max(1.0, ran), pt / std::max(1.0, pn) * 0.01, (tw - pt - lt) / std::max(1.0, ran - pn - ln) * 0.01, tail[15], helping,
                     100.0 * helping / std::max(1e-9, last));
             fprintf(stderr, "[mz sim prof] tail help, quad towers: %.0f of the %.0f simulations that ran the network had a quad tower (%.2f %%): tower %.2f us with three helpers, %.2f us with "
                             "one; %llu games went from pair to quad towers\n",
@@ -620,6 +622,15 @@ void Net::dumpSimProf()
             fprintf(stderr, "[mz sim prof] tail help, idle CU time by the reason the CU stopped looking for a game to help (%% of the launch): (a) every running game of its XCD had its "
                             "helpers %.2f %%, (b) no game of its XCD was running any more %.2f %%, (c) only games with fewer than help_min_left simulations were left %.2f %%\n",
                     100.0 * ia / std::max(1e-9, last), 100.0 * ib / std::max(1e-9, last), 100.0 * ic / std::max(1e-9, last));
+        }
+        if (tail[33] > 0 || tail[35] > 0 || tail[36] > 0) {
+            // lending (sim_help.h): [33] / [34] by the owners, [35 ..] by the volunteers
+            const double ran = sims_all - skipped, ln = double(tail[33]), taken = double(tail[35]);
+            fprintf(stderr, "[mz sim prof] lending: %.0f of the %.0f simulations that ran the network had a tower lent by a game that was ahead (%.2f %%): tower %.2f us with the volunteer; "
+                            "%llu offers taken, %llu of them withdrawn behind a terminal leaf, %llu taken too late; a volunteer waits %.2f us for its command and is away for %.2f us per "
+                            "offer taken, %.1f us per launch and CU (%.1f %% of the launch)\n",
+                    ln, ran, 100.0 * ln / std::max(1.0, ran), double(tail[34]) / std::max(1.0, ln) * 0.01, tail[35], tail[37], tail[36], double(tail[38]) / std::max(1.0, taken) * 0.01,
+                    double(tail[39]) / std::max(1.0, taken) * 0.01, double(tail[39]) / std::max(1.0, double(G)) / L * 0.01, 100.0 * double(tail[39]) / std::max(1.0, double(G)) / L * 0.01 / std::max(1e-9, last));
         }
     }
 }
@@ -745,13 +756,15 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     // game is claimed while it has >= min(k, kSimHelpMinLeft) simulations left.
     bool help = false;
     if (tail_help_ && !bf && !(a.no_spec & 32) && H == 9 && W == 9 && c0 == 20 && C == 64 && a.ta.OT == 4 && gv.n == 9 && gv.kind == kGo && gv.games >= 2 && gv.games <= cu_count_ &&
-        gv.games <= 1024 && helpCmdUnits(gv.channels * gv.W32) <= kHpMaxUnits) {
+        gv.games <= kHpMaxGames && helpCmdUnits(gv.channels * gv.W32) <= kHpMaxUnits) {
         const int env_min = getenv("MZ_SIM_HELP_MIN") ? std::max(1, atoi(getenv("MZ_SIM_HELP_MIN"))) : 0;
         const size_t words = helpWords(C, H * W);
         if (!sim_help_mem_.ensure(size_t(gv.games) * words)) { setError("hipMalloc of the help blocks failed"); return MZ_ERR_DEVICE; }
         a.help = sim_help_mem_.p;
         a.help_words = static_cast<int>(words);
         a.help_min_left = env_min ? std::min(env_min, kSimHelpMinLeft) : kSimHelpMinLeft;
+        // lending: MZ_SIM_LEND_LEAD=k (tests, experiments) sets the lead a lender needs, MZ_NO_SPEC=256 turns lending off
+        a.lend_lead = getenv("MZ_SIM_LEND_LEAD") ? std::max(1, atoi(getenv("MZ_SIM_LEND_LEAD"))) : kSimLendLead;
         help = nsims >= (env_min ? env_min : kSimHelpMinLaunch);
         if (help) { MZ_HIP(hipMemsetAsync(sim_help_mem_.p, 0, size_t(gv.games) * words * sizeof(unsigned), stream_)); }
     }

@@ -306,7 +306,13 @@ constexpr int kVfGather = 7;  // serial of the last gather that is done (wave 4 
 constexpr int kVfRank = 8;    // rank parts of waves 5 .. 7 done so far: 3 per simulation
 constexpr int kVfExpand = 9;  // serial of the last expand that is done (wave 4 -> wave 0: the joins)
 constexpr int kVfStats = 10;  // (MZ_SIM_PROF) walks that arrived at the previous leaf, those that waited there, their ticks, waits at the join in front of the leaf
-constexpr int kVfWords = 16;
+// lending (sim_help.h; wave 7 in front of the barrier behind the leaf -> every wave behind it)
+constexpr int kVfWalked = 14;   // serial of the last walk that is done (wave 0 -> wave 7: the leaf is about to start, the game's offer has to be closed)
+constexpr int kVfOffer = 15;    // this simulation's offer was taken by a volunteer
+constexpr int kVfLend = 16;     // 0, or 1 + the game whose offer this workgroup has taken, and [17] the sequence number of that offer
+constexpr int kVfLendStat = 18; // (MZ_SIM_PROF) offers taken, offers that were gone when the swap arrived, offers withdrawn behind a terminal leaf, ticks waited for the command
+constexpr int kVfLendBits = 24; // the planes of the command of a lent tower (3 * kHpMaxUnits words)
+constexpr int kVfWords = kVfLendBits + 3 * kHpMaxUnits;
 constexpr int kVfErr = 97;
 
 __device__ __forceinline__ bool vfWait(LdsI32* w, int want, int* err, int lane)
@@ -498,7 +504,9 @@ constexpr int kSimProfTail = 40; // ([16..20]: the value-first order: simulation
                                  //  tail help: [21] simulations that ran a quad tower, [22] their tower ticks, [23] games whose pair became a quad; why a finished CU stopped looking
                                  //  for a game to help — cause 0: every running game of its XCD with enough simulations left had its helpers, 1: no game of its XCD was running,
                                  //  2: only games with fewer than help_min_left simulations were left — [24 + cause] CUs and [27 + cause] the sum of the ticks at which they
-                                 //  stopped, of the running launch; [30 + cause] ticks per CU from there to the last game's exit, summed over the launches by sim_prof_fold)
+                                 //  stopped, of the running launch; [30 + cause] ticks per CU from there to the last game's exit, summed over the launches by sim_prof_fold;
+                                 //  lending: [33] simulations whose tower a volunteer shared, [34] their tower ticks, [35] offers taken, [36] swaps for an offer that came too late,
+                                 //  [37] offers withdrawn behind a terminal leaf, [38] ticks the volunteers waited for their commands, [39] ticks they were away from their own games)
 __device__ __forceinline__ void simProfEnter(unsigned long long* tail)
 {
     atomicMin(tail + 0, wall_clock64() - tail[4]);
@@ -550,7 +558,7 @@ __device__ __noinline__ const float* simTowerBf16(CSimArgs* __restrict__ a, int 
 // or quad tower.  Functions of their own beside simTower, so that the solo path keeps its register budget and code.  nullptr: a helper went missing (the error flag
 // is raised, the workgroup leaves the kernel).
 template <int H, int W, int CIN0_PAD, int CPAD, int MODE>
-__device__ __forceinline__ const float* simTowerHelped(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
+__device__ __forceinline__ const float* simTowerHelped(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds, bool lent = false)
 {
     g = __builtin_amdgcn_readfirstlane(g);
     seq = __builtin_amdgcn_readfirstlane(seq);
@@ -564,7 +572,7 @@ __device__ __forceinline__ const float* simTowerHelped(CSimArgs* __restrict__ a,
         u.x = bits[3 * tid];
         u.y = 3 * tid + 1 < fw ? bits[3 * tid + 1] : 0u;
         u.z = 3 * tid + 2 < fw ? bits[3 * tid + 2] : 0u;
-        u.w = hpCmdWord(unsigned(seq), MODE, xseq);
+        u.w = hpCmdWord(unsigned(seq), MODE, xseq, lent);
         asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(hb + kHpCmd + 4 * tid), "v"(u) : "memory");
     }
     HelpCtx c{hb, 0, xseq, abort_lds, a->err};
@@ -572,9 +580,10 @@ __device__ __forceinline__ const float* simTowerHelped(CSimArgs* __restrict__ a,
     else { return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c); }
 }
 template <int H, int W, int CIN0_PAD, int CPAD>
-__device__ __noinline__ const float* simTowerPair(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
+__device__ __noinline__ const float* simTowerPair(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds, int lent)
 {
-    return simTowerHelped<H, W, CIN0_PAD, CPAD, kHpModePair>(a, g, tid, tiles, xchg, seq, xseq, abort_lds);
+    // (lent: member 1 is the volunteer that took this simulation's offer, not the holder of slot 1)
+    return simTowerHelped<H, W, CIN0_PAD, CPAD, kHpModePair>(a, g, tid, tiles, xchg, seq, xseq, abort_lds, __builtin_amdgcn_readfirstlane(lent) != 0);
 }
 template <int H, int W, int CIN0_PAD, int CPAD>
 __device__ __noinline__ const float* simTowerQuad(CSimArgs* __restrict__ a, int g, int tid, float* tiles, float* xchg, int seq, unsigned xseq, int* abort_lds)
@@ -602,6 +611,127 @@ __device__ __noinline__ bool simHelpTower(CSimArgs* __restrict__ a, int o, int m
     HelpCtx c{a->help + size_t(o) * a->help_words, member, xseq, abort_lds, a->err};
     if constexpr (MODE == kHpModeQuad) { return towerBodyQuad<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c) != nullptr; }
     else { return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c) != nullptr; }
+}
+
+// Lending (sim_help.h), wave 7 in front of the barrier behind the leaf of simulation s, beside wave 0's walk.  A game without a helper in slot 1 opens the offer
+// of this simulation and closes it by compare-and-swap once the walk is done (kVfWalked: the swap's round trip lies beside the leaf's first half); a swap that fails
+// means a volunteer has taken the offer, and this simulation's tower is a pair tower with it.  Meanwhile the wave looks through the offers of its XCD's games, as
+// simHelpTail looks through their slots: the least-progress open offer of a game that trails this one by at least `lend_lead` simulations and has at least
+// help_min_left of them left.  Before it takes one it closes its own — a workgroup whose offer is open or taken never waits for anybody — and once it has taken one
+// it looks no further: one tower per simulation.  Results: s_help[1] the tower's mode by the slots (simHelpMode), [kVfOffer], [kVfLend], [kVfLend + 1].
+__device__ __noinline__ void simLendScan(CSimArgs* __restrict__ a, int g, int lane, int s, int nsims, unsigned* help_blk, int* s_help)
+{
+    g = __builtin_amdgcn_readfirstlane(g);
+    s = __builtin_amdgcn_readfirstlane(s);
+    nsims = __builtin_amdgcn_readfirstlane(nsims);
+    LdsI32* vf = (LdsI32*)s_help;
+    const unsigned seq = unsigned(s) + 1u;
+    const int mode = __builtin_amdgcn_readfirstlane(simHelpMode(help_blk));
+    int taken = 0, lend = 0, lend_seq = 0, late = 0;
+    if (mode == 0) {
+        if (lane == 0) { hpStoreU(help_blk + kHpOffer, seq); }
+        const int games = gridDim.x, words = a->help_words, min_left = a->help_min_left, lead = a->lend_lead;
+        const unsigned myxcc = hpXccId();
+        bool open = true, walked = false;
+        for (int i = 0; i < kHpPollLimit; ++i) {
+            walked = __builtin_amdgcn_readfirstlane(__hip_atomic_load(vf + kVfWalked, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) > s;
+            // (sequence number of the offer << 10) | game: the host only lets a launch help with at most kHpMaxGames games (sim.hip simLaunch), a launch has far fewer
+            // than 2^22 simulations, and the games of an XCD (every eighth) are one pass of the loop up to 512 of them, as in simHelpTail
+            static_assert(kHpMaxGames == 1 << 10, "the search key keeps the game in its 10 low bits");
+            unsigned key = ~0u;
+            if (!walked && !taken && !lend && int(seq) > lead) {
+                for (int o = (g & 7) + 8 * lane; o < games; o += 8 * 64) {
+                    const unsigned* ob = a->help + size_t(o) * words;
+                    const unsigned x = hpLoadU(ob + kHpXcc), q = hpLoadU(ob + kHpOffer);
+                    const bool ok = o != g && x == myxcc && q != 0u && q < kHpOfferClaimed && int(q) - 1 + min_left <= nsims && int(q) + lead <= int(seq);
+                    const unsigned k = (q << 10) | unsigned(o);
+                    if (ok && k < key) { key = k; }
+                }
+                for (int o = 32; o > 0; o >>= 1) { const unsigned k2 = __shfl_xor(key, o); key = k2 < key ? k2 : key; }
+            }
+            if (open && (walked || key != ~0u)) { // the own offer: closed for good, or taken
+                unsigned expected = seq;
+                if (lane == 0) { taken = __hip_atomic_compare_exchange_strong(help_blk + kHpOffer, &expected, 0u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1; }
+                taken = __builtin_amdgcn_readfirstlane(taken);
+                open = false;
+            }
+            if (key != ~0u && !taken) {
+                const unsigned q = key >> 10;
+                unsigned expected = q;
+                int got = 0;
+                if (lane == 0) {
+                    got = __hip_atomic_compare_exchange_strong(a->help + size_t(key & unsigned(kHpMaxGames - 1)) * words + kHpOffer, &expected, q | kHpOfferClaimed, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                               __HIP_MEMORY_SCOPE_AGENT) ? 1 : 0;
+                }
+                got = __builtin_amdgcn_readfirstlane(got);
+                if (got) { lend = int(key & unsigned(kHpMaxGames - 1)) + 1; lend_seq = int(q); }
+                else { late += 1; }
+            }
+            if (!open && (walked || taken || lend)) { break; }
+            __builtin_amdgcn_s_sleep(2);
+        }
+        if (open) { // the walk never ended within the poll limit: the error flag is raised, and the offer is closed like any other, so that no volunteer is left with it
+            unsigned expected = seq;
+            if (lane == 0) {
+                atomicExch(a->err, kVfErr);
+                taken = __hip_atomic_compare_exchange_strong(help_blk + kHpOffer, &expected, 0u, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? 0 : 1;
+            }
+            taken = __builtin_amdgcn_readfirstlane(taken);
+        }
+    }
+    if (lane == 0) {
+        s_help[1] = mode;
+        s_help[kVfOffer] = taken;
+        s_help[kVfLend] = lend;
+        s_help[kVfLend + 1] = lend_seq;
+        if (a->prof) { s_help[kVfLendStat] += lend ? 1 : 0; s_help[kVfLendStat + 1] += late; }
+    }
+}
+
+// Lending, the volunteer behind that barrier: its own walk and leaf are done, the tiles are free, every wave is here.  Wave 0 waits for the command of the offer
+// the workgroup has taken — the owner is resident and in front of its tower: it sends the command behind its own leaf and planes — or for the offer's withdrawal
+// (the owner's leaf was terminal: no tower), takes the planes into the staging words of s_help, and the workgroup runs that one tower as member 1 of the pair.
+// false: the owner went missing (the error flag is raised, the workgroup leaves the kernel).
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __noinline__ bool simLendTower(CSimArgs* __restrict__ a, int o, int seq, int tid, float* tiles, int* s_help)
+{
+    o = __builtin_amdgcn_readfirstlane(o);
+    seq = __builtin_amdgcn_readfirstlane(seq);
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fw = a->gv.channels * a->gv.W32, units = helpCmdUnits(fw);
+    const unsigned* ob = a->help + size_t(o) * a->help_words;
+    unsigned* bits = reinterpret_cast<unsigned*>(s_help + kVfLendBits);
+    if (wave == 0) {
+        const unsigned long long tw0 = a->prof ? wall_clock64() : 0;
+        int st = 0;
+        hpu4 u;
+        for (int i = 0; i < kHpPollLimit && st == 0; ++i) {
+            const unsigned* src = ob + kHpCmd + 4 * (lane < units ? lane : 0);
+            asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(u) : "v"(src) : "memory");
+            const unsigned cw = __builtin_amdgcn_readfirstlane(u.w);
+            if (__all(u.w == cw) && hpCmdSeq(cw) == unsigned(seq) && hpCmdLent(cw) && hpCmdMode(cw) == kHpModePair) { st = 1; }
+            else if (hpLoadU(ob + kHpOffer) != (unsigned(seq) | kHpOfferClaimed)) { st = 2; } // withdrawn (behind a tower the word changes only after this member's last exchange)
+            else { __builtin_amdgcn_s_sleep(4); }
+        }
+        if (st == 1 && lane < units) {
+            bits[3 * lane] = u.x;
+            if (3 * lane + 1 < fw) { bits[3 * lane + 1] = u.y; }
+            if (3 * lane + 2 < fw) { bits[3 * lane + 2] = u.z; }
+        }
+        if (lane == 0) {
+            if (st == 0) { atomicExch(a->err, kHpErrLend); }
+            s_help[3] = st;
+            s_help[2] = int(hpCmdXseq(__builtin_amdgcn_readfirstlane(u.w)));
+            if (a->prof) { s_help[kVfLendStat + 2] += st == 2 ? 1 : 0; s_help[kVfLendStat + 3] += int(wall_clock64() - tw0); }
+        }
+    }
+    __syncthreads();
+    const int st = __builtin_amdgcn_readfirstlane(s_help[3]);
+    const unsigned xseq = unsigned(__builtin_amdgcn_readfirstlane(s_help[2]));
+    if (st == 0) { return false; }
+    if (st == 1 && !simHelpTower<H, W, CIN0_PAD, CPAD, kHpModePair>(a, o, 1, xseq, tid, tiles, bits, s_help)) { return false; }
+    __syncthreads();
+    return true;
 }
 
 // Tail help, helper side: the workgroup of game g has finished its simulations of this launch and written its results.  It looks among the games of its XCD
@@ -685,7 +815,8 @@ __device__ __noinline__ void simHelpTail(CSimArgs* __restrict__ a, int g, int ti
                     if (__all(u.w == cw) && sq > last && sq <= unsigned(nsims)) {
                         last = sq;
                         // (the holder of slot 2 or 3 has no part in a pair tower: it waits for the command after it)
-                        if (slot == 1 || hpCmdMode(cw) == kHpModeQuad) { st = 1 + hpCmdMode(cw); s_help[2] = int(hpCmdXseq(cw)); }
+                        // ... and no holder of a slot has a part in a tower lent to a volunteer (a claim of slot 1 beside a taken offer)
+                        if (!hpCmdLent(cw) && (slot == 1 || hpCmdMode(cw) == kHpModeQuad)) { st = 1 + hpCmdMode(cw); s_help[2] = int(hpCmdXseq(cw)); }
                     }
                     else if (hpLoadU(ob + kHpProgress) >= unsigned(nsims)) { st = 3; }
                     else { __builtin_amdgcn_s_sleep(4); }
@@ -777,7 +908,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     if (prof && tid == 0) { simProfEnter(a->prof + size_t(games) * 8); }
     // Tail help (sim_help.h; bit 1 of host_start: this launch helps): the game publishes the XCD it runs on — from here on it can be claimed by a workgroup of
     // that XCD whose own game is done.  s_help: [0] abort flag of the exchanges, [1] the game's tower as of this simulation (0: solo, 1: pair, 2: quad), [2], [3] the
-    // helper's scratch.
+    // helper's scratch (and the volunteer's, simLendTower).
     constexpr bool kHelp = !BF && WPE == 2 && CPL > 0 && pairTowerShape<H, W, CPAD>();
     __shared__ int s_help[kHelp ? kVfWords : 4]; // (+ the words of the value-first order: kVfBackup ..)
     const bool help_on = kHelp && (host_start & 2) != 0;
@@ -785,6 +916,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     unsigned help_xseq = 0;                        // layer exchanges of this game's pair and quad towers so far
     unsigned long long pair_n = 0, pair_t = 0;     // (MZ_SIM_PROF) simulations that ran a pair tower, their tower ticks
     unsigned long long quad_n = 0, quad_t = 0;     // ... a quad tower
+    unsigned long long lent_n = 0, lent_t = 0;     // ... a pair tower with a volunteer (lending), counted by the owner
+    unsigned long long lend_t = 0;                 // ... ticks this workgroup spent as a volunteer
     if (help_on && tid == 0) { s_help[0] = 0; s_help[1] = 0; hpStoreU(help_blk + kHpXcc, hpXccId()); }
     // The value-first order (simWalkVf .. simCandPipeVf above): the same for every simulation of the launch and for every wave, so each wave passes the same barriers
     bool vf = false;
@@ -794,6 +927,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         if (tid >= kVfBackup && tid < kVfWords) { s_help[tid] = 0; }
     }
     unsigned long long vf_t0 = 0, vf_n = 0; // (MZ_SIM_PROF) the start of the walk that ran in the iteration before, simulations in the new order
+    // Lending (sim_help.h): in a launch that helps, in the value-first order (MZ_NO_SPEC=256: off)
+    const bool lend_on = kHelp && help_on && vf && !(a->no_spec & 256);
     __syncthreads();
     for (int s = 0; s < nsims; ++s) {
         const int slot = sim0 + s; // simulation index within the move = position slot of its leaf
@@ -806,6 +941,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                     if (s == 0) { // (the first walk of the launch; every later one ran behind the backup of the simulation before it)
                         if (slot == 1 && a->root_noise) { simApplyRootNoise<WPE>(a, g, lane); }
                         simWalkVf(a, g, lane, rcp_lds, spec, xchg, (a->no_spec & 2) ? 0 : 1, -1, 0, s_help);
+                        if (lend_on && lane == 0) { __hip_atomic_store((LdsI32*)s_help + kVfWalked, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
                     } else {
                         // the join in front of the leaf: leafBody writes the hand-over block the candidate pipeline reads, and the node count is the expand's
                         const bool waited = vfWait((LdsI32*)s_help + kVfExpand, s, a->err, lane);
@@ -818,6 +954,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                     simLeafVf<CPL>(a, rot, slot, g, lane, xchg, seen_lds, leaf_smem, s_help);
                 } else if (s == 0 && wave <= kHelpSegs && spec.w && !(a->no_spec & 2)) {
                     simSelectHelper(a, g, lane, wave, 1, rcp_lds, spec);
+                } else if (lend_on && wave == 7) {
+                    simLendScan(a, g, lane, s, nsims, help_blk, s_help); // (the game's offer and the offers of the others; s_help[1] like below)
                 } else if (help_on && tid == 7 * 64) {
                     // (wave 7 arrives here behind its rank shares of simulation s - 1, not beside the walk as in the old order: a claim made during the walk of s is
                     //  picked up one simulation later)
@@ -837,12 +975,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         }
         __syncthreads();
         const int help_mode = (kHelp && help_on) ? __builtin_amdgcn_readfirstlane(s_help[1]) : 0;
-        const bool pair = help_mode == 1, quad = help_mode == 2;
+        const bool lent = lend_on && __builtin_amdgcn_readfirstlane(s_help[kVfOffer]) != 0; // a volunteer has taken this simulation's offer: member 1 of its pair tower
+        const bool pair = help_mode == 1 || lent, quad = help_mode == 2;
         // A terminal leaf has no children and its value is the game result (zero_actor.cpp:85): nobody reads the network's outputs, so planes, tower and heads
         // are not run for it.  The flag is wave 0's (simLeafTerminal), read by every wave behind the barrier: the branches on it are uniform over the workgroup,
         // and every wave passes the same barriers on either side.  (Each phase is skipped on its own, the barriers behind tower and heads stay where they are:
         // with one branch around all three the 128-VGPR kernels spilled 34 VGPRs instead of 24 (23 before the skip), and BASELINE configs[2] ran 2-3 % slower.)
         const bool term = simLeafTerminal(a, xchg);
+        if constexpr (kHelp) {
+            if (lend_on) {
+                if (lent && term && tid == 7 * 64) { hpStoreU(help_blk + kHpOffer, 0u); } // no tower: the offer is withdrawn, the volunteer goes on
+                const int lend_to = __builtin_amdgcn_readfirstlane(s_help[kVfLend]);
+                if (lend_to != 0) { // one tower of a game that is behind, then this game's own planes and tower
+                    const unsigned long long tl0 = prof ? wall_clock64() : 0;
+                    if (!simLendTower<H, W, CIN0_PAD, CPAD>(a, lend_to - 1, __builtin_amdgcn_readfirstlane(s_help[kVfLend + 1]), tid, tiles, s_help)) { return; }
+                    if (prof) { const unsigned long long d = wall_clock64() - tl0; t0 += d; lend_t += d; } // (not part of this game's walk and leaf)
+                }
+            }
+        }
         if constexpr (CPL > 0) {
             if (!term) {
                 simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
@@ -862,9 +1012,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
             }
             else if constexpr (kHelp) {
                 if (pair) { // with the game's helper: half of the output channels each (sim_help.h)
-                    xt = simTowerPair<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg, s + 1, help_xseq, s_help);
+                    xt = simTowerPair<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg, s + 1, help_xseq, s_help, lent ? 1 : 0);
                     if (!xt) { return; } // the helper went missing: the error flag is raised
                     help_xseq += unsigned(a->ta.nlayers);
+                    if (lent && tid == 7 * 64) { hpStoreU(help_blk + kHpOffer, 0u); } // (the volunteer's last exchange is read: the word is reset)
                 }
                 else if (quad) { // with three helpers: one oc-tile each
                     xt = simTowerQuad<H, W, CIN0_PAD, CPAD>(a, g, tid, tiles, xchg, s + 1, help_xseq, s_help);
@@ -895,8 +1046,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                         t4 = wall_clock64(); // ("cand+expand": what is exposed between the heads and the next walk)
                         prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
                         prof[4] += 1 + (static_cast<unsigned long long>(term) << 32);
-                        if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
+                        if (pair && !lent && !term) { pair_n += 1; pair_t += t2 - t1; }
                         if (quad && !term) { quad_n += 1; quad_t += t2 - t1; }
+                        if (lent && !term) { lent_n += 1; lent_t += t2 - t1; }
                         vf_n += 1;
                     }
                     vf_t0 = t4;
@@ -906,6 +1058,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                             simApplyRootNoise<WPE>(a, g, lane);
                         }
                         simWalkVf(a, g, lane, rcp_lds, spec, xchg, (a->no_spec & 2) ? 0 : s + 2, __builtin_amdgcn_readfirstlane(s_help[kVfLeaf]), s + 1, s_help);
+                        if (lend_on && lane == 0) { __hip_atomic_store((LdsI32*)s_help + kVfWalked, s + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
                     }
                 } else if (wave <= kHelpSegs) {
                     if (more && spec.w && !(a->no_spec & 2)) { // (their blocks claim "with the records as they are": behind the backup)
@@ -950,6 +1103,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                 unsigned long long* ptail = a->prof + size_t(games) * 8;
                 atomicAdd(ptail + 16, vf_n);
                 for (int i = 0; i < 4; ++i) { atomicAdd(ptail + 17 + i, static_cast<unsigned long long>(s_help[kVfStats + i])); }
+                if (lend_on) { // lending: [33] towers with a volunteer, [34] their tower ticks; the volunteers' side: [35] offers taken, [36] taken too late, [37] withdrawn, [38] ticks
+                               // waited for the command, [39] ticks from the barrier behind the leaf to the end of the lent tower
+                    atomicAdd(ptail + 33, lent_n); atomicAdd(ptail + 34, lent_t);
+                    for (int i = 0; i < 4; ++i) { atomicAdd(ptail + 35 + i, static_cast<unsigned long long>(s_help[kVfLendStat + i])); }
+                    atomicAdd(ptail + 39, lend_t);
+                }
             }
         }
     }

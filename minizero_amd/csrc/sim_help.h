@@ -24,6 +24,32 @@
 // game's mode only ever goes solo -> pair -> quad within a launch.  The invariants above hold as they are: every wait is a bounded poll with s_sleep (error flags
 // 95 / 96 for the pair's exchange and command, kHpErrQuad / kHpErrQuadCmd for the quad's); a slot is only claimed in a game that published its XCC_ID in this
 // launch, by a workgroup that runs on the same XCD; the owner waits only for members whose slots it has seen claimed; no cooperative launch is needed.
+//
+// Lending: a game that is AHEAD lends one tower to a game of its XCD that is behind, in mid-launch.  A CU only becomes a helper once its own game is done; by then few
+// games are left.  A game that leads another by `lend_lead` simulations has the same slack earlier and can spend it on pair towers, one at a time, spread over all
+// the slow games (sim_az_body.h simLendScan / simLendTower; only in the value-first order, MZ_NO_SPEC=256: off).
+//  * The offer word (kHpOffer) of a game: 0 closed, s = open for the game's simulation s (its sequence number, 1 ..), s | kHpOfferClaimed = taken by a volunteer.
+//    Wave 7 of a game WITHOUT a helper in slot 1 opens the offer of simulation s when it arrives in front of the barrier behind the leaf — beside wave 0's walk — and
+//    closes it by compare-and-swap s -> 0 when the walk is done, beside the leaf's first half.  A swap that fails has met s | kHpOfferClaimed: this simulation's tower
+//    is a pair tower with the volunteer as member 1, commanded exactly as a slot-1 helper is.  A terminal leaf has no tower: the owner stores 0 (the offer is
+//    withdrawn).  Behind the tower the owner stores 0 too.  The sequence number in the word keeps a late swap from hitting a later offer.
+//  * The volunteer: while its own offer is open, wave 7 reads the XCC_ID and offer words of the games of its XCD past the vector cache (the loop of simHelpTail).
+//    It takes the open offer of least progress of a game that published the same XCC_ID, has at least help_min_left simulations left and trails by at least
+//    `lend_lead` — by compare-and-swap s -> s | kHpOfferClaimed, and only after it has closed its OWN offer of this simulation by compare-and-swap (a swap that
+//    fails there means it has a volunteer itself and takes nothing).  Behind the barrier — its own walk and leaf are done, its hand-over block is complete, the tiles
+//    are free, every wave is present — it waits for the command of simulation s, takes the planes into staging words of its own (not its hand-over block, which
+//    holds its own leaf), runs ONE pair tower as member 1 and goes on with its own planes and tower.
+//  * Whom a command is for: bit 27 of the command word (hpCmdLent; the sequence number keeps 27 bits).  A finished workgroup that claims slot 1 of a game in the
+//    same simulation in which a volunteer has taken its offer skips the lent command like the holder of slot 2 skips a pair command, and a volunteer only takes a
+//    command with the bit set and its offer's sequence number.  help_xseq advances by nlayers for a lent tower like for any pair tower, and the command carries it.
+// The invariants, with lending: every wait is a bounded poll (kHpPollLimit) that raises the pool's error flag and leaves (kHpErrLend: the volunteer's wait for its
+// command; kVfErr: wave 7's wait for the end of the walk, behind which it still closes its offer like any other, so that nobody who might take it is left waiting).  A volunteer waits only for an owner that is resident and in front of its tower: the offer it took was
+// open, so the owner had not passed the barrier behind its leaf, and an owner whose offer is taken does not lend in that simulation — it sends the command behind its
+// own leaf and planes, or withdraws the offer.  An owner waits (in the tower's first exchange) only for a volunteer whose claim it has seen.  Nobody waits for a
+// workgroup that has an offer of its own open: a volunteer has closed its own before it takes one, so chains and cycles of waiting workgroups cannot form.  There
+// is no cooperative launch: owner and volunteer are both resident and running when the claim is made.  Lending stays within one XCD.  Tail help works as before, and
+// slots 2 and 3 are never taken by a volunteer.  A game with a helper in slot 1 neither offers nor lends.  The exchange buffers are re-used as between any two pair
+// towers of a game: the owner sends the next command — to whichever member 1 — only after it has read the last exchange of the tower before.
 #pragma once
 #include "net_body.h"
 
@@ -36,15 +62,24 @@ constexpr int kHpHelper = 32;   // 0 or (helper's game index + 1), claimed by co
 constexpr int kHpCmd = 64;      // up to 32 units of 16 bytes: {three words of the leaf's planes, hpCmdWord of the simulation}
 constexpr int kHpHelper2 = 192; // helper slots 2 and 3, like kHpHelper, each on a line of its own behind the command
 constexpr int kHpHelper3 = 224;
+constexpr int kHpOffer = 256;   // lending: 0 closed, the owner's sequence number = open for that simulation, | kHpOfferClaimed = a volunteer has taken it (a line of its own)
+constexpr unsigned kHpOfferClaimed = 0x40000000u;
 constexpr int kHpXbuf = 320;    // 2 x [C][P] floats
 constexpr int kHpPollLimit = 1 << 21;
 constexpr int kHpMaxUnits = 32;
+constexpr int kHpMaxGames = 1024; // games of a launch that helps (simLaunch's gate): simHelpTail and simLendScan pack (progress << 10) | game into one search key
 constexpr int kHpErrQuad = 98, kHpErrQuadCmd = 99; // error flags: a quad tower's exchange timed out (95: the pair's), the holder of slot 2 or 3 saw no command (96: slot 1)
+constexpr int kHpErrLend = 100;                    // a volunteer saw neither the command of the offer it had claimed nor its withdrawal
 constexpr int kHpModePair = 0, kHpModeQuad = 1;
-// the last word of every command unit: the simulation's sequence number (1 ..), the tower's mode and the exchange count it starts at (its two low bits: hpPart and
-// hpSign use no others); a unit is valid when all units of the command carry the same word
-__host__ __device__ constexpr unsigned hpCmdWord(unsigned seq, int mode, unsigned xseq) { return (seq & 0x0FFFFFFFu) | (unsigned(mode) << 28) | ((xseq & 3u) << 29); }
-__host__ __device__ constexpr unsigned hpCmdSeq(unsigned w) { return w & 0x0FFFFFFFu; }
+// the last word of every command unit: the simulation's sequence number (1 ..), whether the command is for a volunteer (lending) or for the holders of the helper
+// slots, the tower's mode and the exchange count it starts at (its two low bits: hpPart and hpSign use no others); a unit is valid when all units of the command
+// carry the same word
+__host__ __device__ constexpr unsigned hpCmdWord(unsigned seq, int mode, unsigned xseq, bool lent = false)
+{
+    return (seq & 0x07FFFFFFu) | (lent ? 0x08000000u : 0u) | (unsigned(mode) << 28) | ((xseq & 3u) << 29);
+}
+__host__ __device__ constexpr unsigned hpCmdSeq(unsigned w) { return w & 0x07FFFFFFu; }
+__host__ __device__ constexpr bool hpCmdLent(unsigned w) { return (w & 0x08000000u) != 0u; }
 __host__ __device__ constexpr int hpCmdMode(unsigned w) { return int((w >> 28) & 1u); }
 __host__ __device__ constexpr unsigned hpCmdXseq(unsigned w) { return w >> 29; }
 typedef unsigned hpu4 __attribute__((ext_vector_type(4)));
