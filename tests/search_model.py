@@ -1,6 +1,7 @@
 """A plain, slow model of the reference's search, written from the reference's text: actor/mcts.cpp (tree, PUCT, backup, value bound, max count, resign),
 actor/gumbel_zero.cpp (the Gumbel root: sequential halving, the start child of a simulation, the completed-Q policy) and actor/zero_actor.cpp:51-98,159-245
-(one simulation around a network call, candidates, noise, the decision).  Every float of the reference is a numpy float32 here and every promotion to double
+(one simulation around a network call, candidates, Gumbel and Dirichlet noise at the root, the decision), player succession from
+environment/base/base_env.cpp:27-42.  Every float of the reference is a numpy float32 here and every promotion to double
 is spelled out; nothing is computed with a tolerance.  The environment and the network are handed in; this file imports neither the oracle nor the product.
 
 std::sort: libstdc++ sorts a range of at most 16 elements by insertion, which is stable; a longer range goes through introsort, whose result is defined by
@@ -22,7 +23,7 @@ class AmbiguousOrder(Exception):
 
 
 class Cfg:
-    """the keys of config/configuration.cpp:13-34,45 the search reads, with their defaults"""
+    """the keys of config/configuration.cpp:13-34,45 the search reads, with their defaults (the noise draws themselves are handed to search())"""
 
     def __init__(self, **kw):
         self.actor_num_simulation = 50
@@ -35,6 +36,8 @@ class Cfg:
         self.actor_gumbel_sample_size = 16
         self.actor_gumbel_sigma_visit_c = 50.0
         self.actor_gumbel_sigma_scale_c = 1.0
+        self.actor_use_dirichlet_noise = True  # only search() with a root_noise reads it
+        self.actor_dirichlet_noise_epsilon = 0.25
         self.actor_resign_threshold = -0.9
         self.atari_init_q = False  # the reference decides this at compile time (#if ATARI, mcts.cpp:211)
         for k, v in kw.items():
@@ -286,8 +289,30 @@ class GumbelRoot:
         return out
 
 
-def other(player):
-    return WHITE if player == BLACK else BLACK  # getPreviousPlayer / nextPlayer of a two-player game
+def next_player(player, num_player=2):
+    """getNextPlayer (environment/base/base_env.cpp:27-36); getPreviousPlayer (:38-42) is the same function for one and two players"""
+    assert num_player in (1, 2)
+    if num_player == 1:
+        return player
+    return WHITE if player == BLACK else BLACK
+
+
+other = next_player  # the two-player case
+
+
+def add_root_noise(cfg, t, root_noise):
+    """addNoiseToNodeChildren (zero_actor.cpp:194-213) with the draws handed in, one per child in child order.  Dirichlet (:197-204): epsilon is a float, so
+    1 - epsilon, both products and the sum are float, and the logits stay as they are; Gumbel (:205-211): the noise goes onto the logit"""
+    assert len(root_noise) == t.nkids[0]
+    if cfg.actor_use_dirichlet_noise:
+        eps = f32(cfg.actor_dirichlet_noise_epsilon)
+        for c, d in zip(t.kids(0), root_noise):
+            t.noise[c] = f32(d)
+            t.policy[c] = f32(f32(f32(f32(1) - eps) * t.policy[c]) + f32(eps * f32(d)))
+    else:
+        for c, g in zip(t.kids(0), root_noise):
+            t.noise[c] = f32(g)
+            t.logit[c] = f32(t.logit[c] + f32(g))
 
 
 def _sorted_candidates(cands):
@@ -297,9 +322,11 @@ def _sorted_candidates(cands):
 
 def search(cfg, env, net, muzero=False, root_noise=None, halvings=None):
     """One move's search, n + 1 simulations of ZeroActor::beforeNNEvaluation / afterNNEvaluation (zero_actor.cpp:51-98) one at a time, then the decision
-    (:159-192).  root_noise: the Gumbel draws for the root's children in child order (addNoiseToNodeChildren, :205-211).  Returns (tree, selected, gumbel root)."""
+    (:159-192).  root_noise: the Dirichlet draws (with cfg.actor_use_dirichlet_noise) or else the Gumbel draws for the root's children in child order (see
+    add_root_noise).  The environment says how many players take turns (num_players(), base_env.h:101).  Returns (tree, selected, gumbel root)."""
+    players = env.num_players()
     t = Tree(cfg)
-    t.reset(other(env.turn()))
+    t.reset(next_player(env.turn(), players))  # getPreviousPlayer (zero_actor.cpp:33)
     gz = GumbelRoot(cfg)
     selected = None
     while t.num_simulation() < cfg.actor_num_simulation + 1:
@@ -322,16 +349,13 @@ def search(cfg, env, net, muzero=False, root_noise=None, halvings=None):
                 r = 0.0
             else:
                 p, l, v, r, h = net.recurrent(t.hidden[path[-2]], env.action_features(t.action[leaf], t.player[leaf]))
-            turn = other(t.player[leaf])
+            turn = next_player(t.player[leaf], players)  # Action::nextPlayer (zero_actor.cpp:235, base_env.h:335, atari.h:40)
             legal = env.legal() if leaf == 0 else None
             t.expand(leaf, _sorted_candidates([(a, turn, f32(p[a]), f32(l[a])) for a in range(len(p)) if legal is None or legal[a]]))
             t.backup(path, v, r)
             t.hidden[leaf] = h
         if leaf == 0 and root_noise is not None:
-            assert len(root_noise) == t.nkids[0]
-            for c, g in zip(t.kids(0), root_noise):
-                t.noise[c] = f32(g)
-                t.logit[c] = f32(t.logit[c] + f32(g))
+            add_root_noise(cfg, t, root_noise)
         if t.num_simulation() == cfg.actor_num_simulation + 1:
             selected = gz.decide(t) if cfg.actor_use_gumbel else t.select_by_max_count()
         if cfg.actor_use_gumbel:
@@ -342,18 +366,21 @@ def search(cfg, env, net, muzero=False, root_noise=None, halvings=None):
 
 
 def play(cfg, env, net, moves, muzero=False, first_noise=None, resign_enabled=True):
-    """The first `moves` moves of one game from the position `env` holds: per search a dict of the action id, the P tag as a dictionary, the V tag and whether
-    the actor resigns instead of playing (actor_group.cpp:116-134 with zero_actor.h:40,50-51).  Ends early at a resignation or a terminal position."""
+    """The first `moves` moves of one game from the position `env` holds: per search a dict of the action id, the P tag as a dictionary, the V tag, whether
+    the actor resigns instead of playing (actor_group.cpp:116-134 with zero_actor.h:40,50-51) and, for a move that is played, the R tag: the reward the
+    environment reports after the move, printed by an ostream of precision 6 (base_actor.cpp:22-28,64 with zero_actor.cpp:122-127).  Ends early at a
+    resignation or a terminal position."""
     out = []
     for k in range(moves):
         if env.terminal():
             break
         t, sel, gz = search(cfg, env, net, muzero, first_noise if k == 0 else None)
         resign = resign_enabled and t.is_resign(sel)
-        out.append(dict(action=t.action[sel], P=gz.policy(t) if cfg.actor_use_gumbel else t.distribution(), V=t.root_value_string(), resign=resign))
+        out.append(dict(action=t.action[sel], P=gz.policy(t) if cfg.actor_use_gumbel else t.distribution(), V=t.root_value_string(), R=None, resign=resign))
         if resign:
             break
         env.act(t.action[sel], t.player[sel])
+        out[-1]["R"] = "%g" % float(env.reward())
     return out
 
 

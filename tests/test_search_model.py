@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from atari_synth import AtariSynth
 import hand_cases as H
 from helpers import sharpen
 import search_model as S
@@ -137,6 +138,7 @@ class OracleEnvAdapter:
         assert self.e.act(a, player), (a, player, self.hist)
         self.hist.append((a, player))
 
+    def num_players(self): return 2
     def turn(self): return self.e.turn()
     def legal(self): return self.e.legal_mask()
     def terminal(self): return self.e.is_terminal()
@@ -163,6 +165,7 @@ class TicTacToe:
         assert self.board[a] == 0
         self.board[a], self.to_move = player, 3 - player
 
+    def num_players(self): return 2
     def turn(self): return self.to_move
     def legal(self): return [int(b == 0) for b in self.board]
 
@@ -218,6 +221,33 @@ def test_python_tictactoe_equals_oracle_env(oracle):
             theirs.act(a, p)
 
 
+def test_python_atari_equals_oracle_env(oracle):
+    """the synthetic Atari-shaped game of tests/atari_synth.py against the oracle's: the float arrays bit for bit, at every step of random games to their end"""
+    rng = np.random.default_rng(5)
+    for length in (1, 3, 11, 30):
+        theirs = OracleEnvAdapter(oracle, f"env_game=atari:env_atari_episode_length={length}")
+        mine = AtariSynth(theirs.e.seed(), length)
+        steps = 0
+        while True:
+            assert mine.turn() == theirs.turn() == 1 and mine.terminal() == theirs.terminal() and list(theirs.legal()) == mine.legal()
+            f, g = mine.features(), theirs.features()
+            assert f.dtype == g.dtype == np.float32 and f.shape == g.shape and np.array_equal(f.view(np.uint32), g.view(np.uint32))
+            assert mine.eval_score() == theirs.eval_score() and mine.reward() == theirs.reward()
+            if mine.terminal():
+                break
+            a = int(rng.integers(18))
+            assert np.array_equal(mine.action_features(a, 1).view(np.uint32), theirs.action_features(a, 1).view(np.uint32))
+            mine.act(a, 1)
+            theirs.act(a, 1)
+            steps += 1
+        assert steps == length
+    # a seed with the sign bit set hashes as its 32-bit pattern; a reward of 1 is in reach of a short game (5 % a step)
+    e = AtariSynth(-5, 200)
+    for _ in range(200):
+        e.act(0)
+    assert AtariSynth(-5, 1).useed == 2 ** 32 - 5 and 1 <= float(e.eval_score()) <= 30
+
+
 # ---------------------------------------------------------------------------------------------
 # the table of configurations (shared with tests/test_gpu_search_model.py)
 # ---------------------------------------------------------------------------------------------
@@ -228,11 +258,27 @@ GO8_MZ = GO8[:12] + ("muzero",)
 GO128 = ("go_9x9", 18, 9, 9, 128, 9, 9, 1, 1, 82, 16, 1, "alphazero")
 OTH8 = ("othello_8x8", 4, 8, 8, 8, 8, 8, 1, 1, 65, 16, 1, "alphazero")
 TTT16 = ("tictactoe", 4, 3, 3, 16, 3, 3, 1, 1, 9, 16, 1, "alphazero")
+ATARI32 = ("atari_ms_pacman", 32, 96, 96, 32, 6, 6, 18, 1, 18, 32, 601, "muzero_atari")
+ATARI_C5 = ("atari_ms_pacman", 32, 96, 96, 64, 6, 6, 18, 6, 18, 256, 601, "muzero_atari")  # the network of the benchmark's Atari-shaped configuration
+
+
+def full_conf(conf, games=None):
+    """The string all three sides are configured with: QUIET first, so that a case's own keys (the Dirichlet noise of a noisy case) replace it"""
+    return QUIET[1:] + ":" + conf + ("" if games is None else f":zero_num_parallel_games={games}")
 
 
 def _gumbel(n, m, noise=False):
     return f":actor_num_simulation={n}:actor_use_gumbel=true:actor_gumbel_sample_size={m}:actor_use_gumbel_noise={'true' if noise else 'false'}"
 
+
+def _atari(moves, rescale=True, discount=0.997):
+    """The Atari-shaped search: one player, value rescaling over the value-bound multiset, a reward discount, the init-Q of the reference's ATARI build.  Every
+    game ends after `moves` moves, so its line carries SD, the moves and the end; the threshold keeps resignation out of it"""
+    return (f"env_game=atari:nn_type_name=muzero:env_atari_episode_length={moves}:zero_actor_intermediate_sequence_length=0:actor_resign_threshold=-2"
+            f":actor_mcts_value_rescale={'true' if rescale else 'false'}:actor_mcts_reward_discount={discount}:atari_init_q=true")
+
+
+DIRICHLET = ":actor_use_dirichlet_noise=true:actor_dirichlet_noise_alpha=0.03:actor_dirichlet_noise_epsilon=0.25"
 
 # name -> (configuration, network, weight seeds, moves, games, gain on the value head's last layer or None).  The weight seeds are those for which the model raises no AmbiguousOrder (chosen on the CPU with
 # the model alone; a seed that raised it would fail its case in test_model_equals_oracle).
@@ -250,22 +296,52 @@ CASES["ttt_puct_n16"] = ("env_game=tictactoe:actor_num_simulation=16", TTT16, (1
 for _n, _m in ((16, 16), (50, 16), (33, 6), (12, 8)):
     CASES[f"go_mz_gumbel_n{_n}_m{_m}"] = ("env_game=go:env_board_size=9:nn_type_name=muzero" + _gumbel(_n, _m), GO8_MZ, (2, 3), 3, 4, None)
 CASES["go128_gumbel_n50_m16"] = ("env_game=go:env_board_size=9" + _gumbel(50, 16), GO128, (1,), 3, 4, None)
+# MuZero with PUCT: the hidden-state slab, children that are never masked below the root, the reward in the backup.  Weight seed 4 raises AmbiguousOrder at n = 24.
+CASES["go_mz_puct_n24"] = ("env_game=go:env_board_size=9:nn_type_name=muzero:actor_num_simulation=24", GO8_MZ, (2,), 3, 4, None)
+CASES["go_mz_puct_n50"] = ("env_game=go:env_board_size=9:nn_type_name=muzero:actor_num_simulation=50", GO8_MZ, (3,), 2, 4, None)
+# The Atari-shaped rows.  Each game draws its own seed (its SD tag) and is compared with the model's game of that seed.  (16, 4): the small row the GPU file
+# runs on every execution mode; (16, 16): never halved; (7, 16): n < m; (50, 12): m no power of two; (40, 18): every root child sampled, sorts beyond 16.
+ATARI_MOVES, ATARI_GAMES = 3, 3
+for _n, _m in ((16, 4), (16, 16), (7, 16), (50, 12), (40, 18)):
+    CASES[f"atari_gumbel_n{_n}_m{_m}"] = (_atari(ATARI_MOVES) + _gumbel(_n, _m), ATARI32, (1, 2) if (_n, _m) == (16, 4) else (2,), ATARI_MOVES, ATARI_GAMES, None)
+CASES["atari_c5_gumbel_n16_m4"] = (_atari(ATARI_MOVES) + _gumbel(16, 4), ATARI_C5, (1,), ATARI_MOVES, ATARI_GAMES, None)
+for _n in (12, 24):
+    CASES[f"atari_puct_n{_n}"] = (_atari(ATARI_MOVES) + f":actor_num_simulation={_n}", ATARI32, (1,), ATARI_MOVES, ATARI_GAMES, None)
+# rescale on and off at discount 1.0: the value-bound multiset is all that differs between these two; the first differs from atari_gumbel_n16_m4 in the discount
+CASES["atari_gumbel_n16_m4_undiscounted"] = (_atari(ATARI_MOVES, True, 1.0) + _gumbel(16, 4), ATARI32, (1,), ATARI_MOVES, ATARI_GAMES, None)
+CASES["atari_gumbel_n16_m4_plain"] = (_atari(ATARI_MOVES, False, 1.0) + _gumbel(16, 4), ATARI32, (1,), ATARI_MOVES, ATARI_GAMES, None)
 
-# the noisy first move: (configuration, network, weight seed, action count of the first position)
+# the noisy first move: (configuration, network, weight seed, kind of noise at the root)
 NOISY = {
-    "ttt": ("env_game=tictactoe" + _gumbel(16, 4, True), TTT16, 1),
-    "othello": ("env_game=othello:env_board_size=8" + _gumbel(16, 16, True), OTH8, 1),
-    "go": ("env_game=go:env_board_size=9" + _gumbel(50, 16, True), GO8, 1),
+    "ttt": ("env_game=tictactoe" + _gumbel(16, 4, True), TTT16, 1, "gumbel"),
+    "othello": ("env_game=othello:env_board_size=8" + _gumbel(16, 16, True), OTH8, 1, "gumbel"),
+    "go": ("env_game=go:env_board_size=9" + _gumbel(50, 16, True), GO8, 1, "gumbel"),
+    "atari": (_atari(1) + _gumbel(16, 4, True), ATARI32, 1, "gumbel"),
+    "go_dirichlet": ("env_game=go:env_board_size=9:actor_num_simulation=24" + DIRICHLET, GO8, 2, "dirichlet"),
+    "go_mz_dirichlet": ("env_game=go:env_board_size=9:nn_type_name=muzero:actor_num_simulation=24" + DIRICHLET, GO8_MZ, 2, "dirichlet"),
+    "othello_dirichlet": ("env_game=othello:env_board_size=8:actor_num_simulation=24" + DIRICHLET, OTH8, 1, "dirichlet"),
+    "atari_dirichlet": (_atari(1) + ":actor_num_simulation=24" + DIRICHLET, ATARI32, 1, "dirichlet"),
 }
 NOISY_GAMES = 8
 
-MOVE = re.compile(r";([BW])\[(\d+)\]P\[([^\]]*)\]V\[([^\]]*)\]R\[[^\]]*\]")
+MOVE = re.compile(r";([BW])\[(\d+)\]P\[([^\]]*)\]V\[([^\]]*)\]R\[([^\]]*)\]")
+SEED = re.compile(r"SD\[(-?\d+)\]")
 
 
 def model_cfg(conf):
-    kv = dict(x.split("=", 1) for x in conf.split(":") if x)
-    kw = dict(actor_num_simulation=int(kv.get("actor_num_simulation", 50)), actor_use_gumbel=kv.get("actor_use_gumbel") == "true",
-              actor_gumbel_sample_size=int(kv.get("actor_gumbel_sample_size", 16)), actor_resign_threshold=float(kv.get("actor_resign_threshold", -0.9)))
+    """(the model's Cfg, MuZero?, all keys) of a case's configuration string: every key of Cfg is read from full_conf(conf), so the string alone defines the case"""
+    kv = dict(x.split("=", 1) for x in full_conf(conf).split(":") if x)
+    kw = {}
+    for key, default in vars(S.Cfg()).items():
+        if key not in kv:
+            continue
+        if key == "actor_mcts_value_flipping_player":
+            kw[key] = {"B": S.BLACK, "W": S.WHITE}[kv[key]]
+        elif isinstance(default, bool):
+            assert kv[key] in ("true", "false"), (key, kv[key])
+            kw[key] = kv[key] == "true"
+        else:
+            kw[key] = type(default)(kv[key])
     return S.Cfg(**kw), kv.get("nn_type_name") == "muzero", kv
 
 
@@ -275,59 +351,70 @@ def case_weights(oracle, desc_args, wseed, vgain=None):
     return w if vgain is None else sharpen(od, w, 1, vgain)
 
 
-def make_env(oracle, conf):
+def is_atari(conf):
+    return model_cfg(conf)[2]["env_game"] == "atari"
+
+
+def make_env(oracle, conf, env_seed=None):
+    """the environment the model plays in; an Atari-shaped game is that of `env_seed`, the SD tag of the record it is compared with"""
     kv = model_cfg(conf)[2]
     if kv["env_game"] == "tictactoe":
         return TicTacToe()
+    if kv["env_game"] == "atari":
+        assert env_seed is not None, "an Atari-shaped game is defined by its seed"
+        return AtariSynth(env_seed, int(kv["env_atari_episode_length"]))
     return OracleEnvAdapter(oracle, ":".join(f"{k}={kv[k]}" for k in ("env_game", "env_board_size") if k in kv))
 
 
 def parse_record(record, moves):
-    """[(action id, P dictionary, V string)] of the first `moves` moves of a record"""
+    """[(action id, P dictionary, V string, R string)] of the first `moves` moves of a record"""
     out = []
-    for _, a, p, v in MOVE.findall(record)[:moves]:
-        out.append((int(a), {int(x.split(":")[0]): x.split(":")[1] for x in p.split(",")} if p else {}, v))
+    for _, a, p, v, r in MOVE.findall(record)[:moves]:
+        out.append((int(a), {int(x.split(":")[0]): x.split(":")[1] for x in p.split(",")} if p else {}, v, r))
     return out
 
 
-def expected_from_model(oracle, conf, desc_args, wseed, moves, first_noise=None, weights=None, halvings=None):
-    """what the model plays: ([(action, P, V)] of the moves played, resigned at the next search?, finished (terminal or resigned) within `moves`)"""
+def expected_from_model(oracle, conf, desc_args, wseed, moves, first_noise=None, weights=None, halvings=None, env_seed=None):
+    """what the model plays: ([(action, P, V, R)] of the moves played, resigned at the next search?, finished (terminal or resigned) within `moves`)"""
     cfg, muzero, _ = model_cfg(conf)
     od = oracle.make_desc(*desc_args[:10], vh=desc_args[10], dv=desc_args[11], type_name=desc_args[12])
     w = oracle.gen_weights(od, wseed) if weights is None else weights
-    env = make_env(oracle, conf)
+    env = make_env(oracle, conf, env_seed)
     got = S.play(cfg, env, NetAdapter(oracle.OracleNet(od, w)), moves, muzero, first_noise)
     resigned = bool(got) and got[-1]["resign"]
-    played = [(g["action"], g["P"], g["V"]) for g in got if not g["resign"]]
+    played = [(g["action"], g["P"], g["V"], g["R"]) for g in got if not g["resign"]]
     return played, resigned, resigned or env.terminal()
 
 
 def games_of(lines, records, games, moves):
-    """per game: the first finished record if the game has ended, else the record as it stands -> ([(action, P, V)], finished)"""
+    """per game: the first finished record if the game has ended, else the record as it stands -> ([(action, P, V, R)], finished, SD tag or None)"""
     out = []
     for g in range(games):
         done = len(lines) >= games
         rec = lines[g] if done else records[g]
         mv = parse_record(rec, moves)
-        out.append((mv, done and len(MOVE.findall(rec)) <= moves))
+        sd = SEED.search(rec)
+        out.append((mv, done and len(MOVE.findall(rec)) <= moves, int(sd.group(1)) if sd else None))
     return out
 
 
 def check_against(model, games):
-    """the comparison of §2b / §3: every game equals the model (and so its neighbours): moves, P, V as strings, and whether the game ended where the model's did"""
-    played, resigned, finished = model
-    for g, (mv, done) in enumerate(games):
+    """the comparison of §2b / §3: every game equals the model (and so its neighbours): moves, P, V, R as strings, and whether the game ended where the model's
+    did.  `model` is the model's game, or for games that differ by their seed a function from a game's SD tag to the model's game of that seed"""
+    for g, (mv, done, sd) in enumerate(games):
+        played, resigned, finished = model(sd) if callable(model) else model
         assert [m[0] for m in mv] == [m[0] for m in played], f"game {g}: actions {[m[0] for m in mv]} != model {[m[0] for m in played]}"
         for k, (a, b) in enumerate(zip(mv, played)):
             assert a[2] == b[2], f"game {g} move {k}: V {a[2]} != model {b[2]}"
             assert a[1] == b[1], f"game {g} move {k}: P differs from the model: {sorted(set(a[1].items()) ^ set(b[1].items()))}"
+            assert b[3] is None or a[3] == b[3], f"game {g} move {k}: R {a[3]} != model {b[3]}"
         assert done == finished, f"game {g}: ended {done}, model {finished} (resigned {resigned})"
 
 
 def oracle_games(oracle, conf, desc_args, w, games, moves):
     cfg = model_cfg(conf)[0]
     od = oracle.make_desc(*desc_args[:10], vh=desc_args[10], dv=desc_args[11], type_name=desc_args[12])
-    og = oracle.OracleGroup(conf + f":zero_num_parallel_games={games}" + QUIET, od, w)
+    og = oracle.OracleGroup(full_conf(conf, games), od, w)
     og.cycles((cfg.actor_num_simulation + 1) * (moves + 1))
     return games_of(og.lines(), og.peek_records(games), games, moves)
 
@@ -335,12 +422,28 @@ def oracle_games(oracle, conf, desc_args, w, games, moves):
 _MODEL_CACHE = {}
 
 
-def model_of(oracle, name, wseed):
+def model_of(oracle, name, wseed, env_seed=None):
     """the model's games are computed once and shared (the GPU file asks for the same ones)"""
-    if (name, wseed) not in _MODEL_CACHE:
+    if (name, wseed, env_seed) not in _MODEL_CACHE:
         conf, desc_args, _, moves, _, vgain = CASES[name]
-        _MODEL_CACHE[name, wseed] = expected_from_model(oracle, conf, desc_args, wseed, moves, weights=case_weights(oracle, desc_args, wseed, vgain))
-    return _MODEL_CACHE[name, wseed]
+        _MODEL_CACHE[name, wseed, env_seed] = expected_from_model(oracle, conf, desc_args, wseed, moves, weights=case_weights(oracle, desc_args, wseed, vgain),
+                                                                  env_seed=env_seed)
+    return _MODEL_CACHE[name, wseed, env_seed]
+
+
+def case_model(oracle, name, wseed):
+    """what check_against takes for a row: the one game all games of the pool play, or for an Atari-shaped row the game of each seed"""
+    if is_atari(CASES[name][0]):
+        return lambda sd: model_of(oracle, name, wseed, sd)
+    return model_of(oracle, name, wseed)
+
+
+def check_atari_pool_shows_something(games):
+    """A multi-move Atari-shaped row must show a reward of 1 and, at some move, two different V strings over its games: without the first the reward's way
+    into the backup and the R tag goes unseen, without the second a leak between games does"""
+    assert all(sd is not None for _, _, sd in games) and len({sd for _, _, sd in games}) == len(games)
+    assert any(m[3] == "1" for mv, _, _ in games for m in mv), "no game of the pool earned a reward"
+    assert any(len({mv[k][2] for mv, _, _ in games}) > 1 for k in range(min(len(mv) for mv, _, _ in games))), "all games have the same values"
 
 
 ALL_CASES = [(name, s) for name, c in CASES.items() for s in c[2]]
@@ -350,9 +453,14 @@ ALL_CASES = [(name, s) for name, c in CASES.items() for s in c[2]]
 def test_model_equals_oracle(oracle, name, wseed):
     """§2b; an AmbiguousOrder raised by the model fails the case: the committed seeds raise none"""
     conf, desc_args, _, moves, games, vgain = CASES[name]
-    model = model_of(oracle, name, wseed)
-    check_against(model, oracle_games(oracle, conf, desc_args, case_weights(oracle, desc_args, wseed, vgain), games, moves))
-    assert len(model[0]) >= 1 or model[1]
+    model = case_model(oracle, name, wseed)
+    got = oracle_games(oracle, conf, desc_args, case_weights(oracle, desc_args, wseed, vgain), games, moves)
+    check_against(model, got)
+    if callable(model):
+        check_atari_pool_shows_something(got)
+        assert all(len(model(sd)[0]) == moves and model(sd)[2] for _, _, sd in got)
+    else:
+        assert len(model[0]) >= 1 or model[1]
 
 
 def test_resign_case_resigns_and_plays(oracle):
@@ -361,38 +469,59 @@ def test_resign_case_resigns_and_plays(oracle):
     assert any(o[1] for o in outcomes) and any(len(o[0]) > 0 for o in outcomes)
 
 
+def test_model_cfg_reads_every_key():
+    """a case is defined by its configuration string alone: every key of the model's Cfg comes out of it"""
+    keys = dict(actor_num_simulation=(9, "9"), actor_mcts_puct_base=(100.0, "100"), actor_mcts_puct_init=(2.5, "2.5"), actor_mcts_reward_discount=(0.997, "0.997"),
+                actor_mcts_value_rescale=(True, "true"), actor_mcts_value_flipping_player=(S.BLACK, "B"), actor_use_gumbel=(True, "true"),
+                actor_gumbel_sample_size=(5, "5"), actor_gumbel_sigma_visit_c=(40.0, "40"), actor_gumbel_sigma_scale_c=(0.1, "0.1"),
+                actor_use_dirichlet_noise=(True, "true"), actor_dirichlet_noise_epsilon=(0.5, "0.5"), actor_resign_threshold=(-2.0, "-2"), atari_init_q=(True, "true"))
+    assert set(keys) == set(vars(S.Cfg()))
+    cfg = model_cfg("env_game=go:" + ":".join(f"{k}={v[1]}" for k, v in keys.items()))[0]
+    assert vars(cfg) == {k: v[0] for k, v in keys.items()}
+    quiet = model_cfg("env_game=go")[0]
+    assert vars(quiet) == dict(vars(S.Cfg()), actor_use_dirichlet_noise=False)
+
+
 # ---------------------------------------------------------------------------------------------
 # c. the noisy first move
 # ---------------------------------------------------------------------------------------------
-def gumbel_draws(oracle, seed, games, nc):
-    """the first games * nc values of the Gumbel stream (kind 3 of mzo_rng_vector, pinned to the reference in tests/golden/ref_rng_rotation_config.json)"""
+def noise_draws(oracle, kind, seed, games, nc, alpha=0.0):
+    """the first `games` vectors of nc values of the Gumbel stream (kind 3 of mzo_rng_vector) or the Dirichlet stream (kind 2), both pinned to the reference in
+    tests/golden/ref_rng_rotation_config.json"""
     out = np.zeros(games * nc, np.float64)
-    oracle.lib().mzo_rng_vector(seed, 3, games * nc, nc, 0.0, out.ctypes.data_as(C.POINTER(C.c_double)))
+    oracle.lib().mzo_rng_vector(seed, {"dirichlet": 2, "gumbel": 3}[kind], games * nc, nc, alpha, out.ctypes.data_as(C.POINTER(C.c_double)))
     return out.astype(np.float32).reshape(games, nc)
 
 
-def noisy_models(oracle, name):
+def noisy_model(oracle, name, g, env_seed=None):
     """With rotation off, selection by count and one RNG stream, nothing draws from the slave thread's generator (seeded program_seed + 0, actor_group.cpp:66-70)
-    before the first root is expanded: the resign coin of the first reset() comes from the main thread's generator (actor_group.cpp:179-187).  The actors expand
-    their first roots in index order in the second cycle, so game g takes draws [g * nc, (g + 1) * nc) of the Gumbel stream; test_noisy_first_move establishes
-    it on the oracle by playing eight different first moves right."""
-    if ("noisy", name) not in _MODEL_CACHE:
-        conf, desc_args, wseed = NOISY[name]
-        nc = int(np.sum(make_env(oracle, conf).legal()))
-        draws = gumbel_draws(oracle, 7, NOISY_GAMES, nc)
-        _MODEL_CACHE["noisy", name] = [expected_from_model(oracle, conf, desc_args, wseed, 1, first_noise=draws[g]) for g in range(NOISY_GAMES)]
-    return _MODEL_CACHE["noisy", name]
+    before the first root is expanded: the resign coin of the first reset() comes from the main thread's generator (actor_group.cpp:179-187), and so does the
+    seed an Atari-shaped game draws there.  The actors expand their first roots in index order in the second cycle, so game g takes draws [g * nc, (g + 1) * nc)
+    of the noise stream, Gumbel or Dirichlet; test_noisy_first_move establishes it on the oracle by playing eight different first moves right."""
+    if ("noisy", name, g, env_seed) not in _MODEL_CACHE:
+        conf, desc_args, wseed, kind = NOISY[name]
+        cfg, _, kv = model_cfg(conf)
+        assert (kind == "dirichlet") == cfg.actor_use_dirichlet_noise and (kind == "gumbel") == (kv.get("actor_use_gumbel_noise") == "true")
+        nc = int(np.sum(make_env(oracle, conf, env_seed).legal()))
+        draws = noise_draws(oracle, kind, int(kv["program_seed"]), NOISY_GAMES, nc, float(kv.get("actor_dirichlet_noise_alpha", 0.03)))
+        _MODEL_CACHE["noisy", name, g, env_seed] = expected_from_model(oracle, conf, desc_args, wseed, 1, first_noise=draws[g], env_seed=env_seed)
+    return _MODEL_CACHE["noisy", name, g, env_seed]
 
 
-def check_noisy(models, games):
+def check_noisy(oracle, name, games):
+    """every game against the model under its own noise vector (and in its own Atari-shaped game) -> the set of first actions"""
+    assert len(games) == NOISY_GAMES
+    first = set()
     for g, game in enumerate(games):
-        check_against(models[g], [game])
-    return {m[0][0][0] for m in models}
+        assert (game[2] is not None) == is_atari(NOISY[name][0])
+        model = noisy_model(oracle, name, g, game[2])
+        check_against(model, [game])
+        first.add(model[0][0][0])
+    return first
 
 
 @pytest.mark.parametrize("name", list(NOISY))
 def test_noisy_first_move(oracle, name):
-    conf, desc_args, wseed = NOISY[name]
-    models = noisy_models(oracle, name)
-    first_actions = check_noisy(models, oracle_games(oracle, conf, desc_args, case_weights(oracle, desc_args, wseed), NOISY_GAMES, 1))
+    conf, desc_args, wseed, _ = NOISY[name]
+    first_actions = check_noisy(oracle, name, oracle_games(oracle, conf, desc_args, case_weights(oracle, desc_args, wseed), NOISY_GAMES, 1))
     assert len(first_actions) > 1, "eight noise vectors that all lead to one first move show nothing"
