@@ -676,5 +676,223 @@ __device__ __forceinline__ void headsBody(const float* __restrict__ x, const Hea
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// The heads of the 9x9 x 64 one-game-per-CU simulation kernel (sim_kernel<9,9,20,64,2>) with their operands delivered AHEAD of the chains.
+// headsBody's chains fetch their weights in groups of 16 behind the fmas of the group before: every group pays one whole L2 round trip, and the three
+// ordered chains (64 + 162 + 256 steps) ran at ~43 cycles per step where the arithmetic needs 13-15.  Same chains, same order, same fmaf here — only
+// where the operands come from changes:
+//  * the small weights that never change during a launch (both conv1x1, all biases, the value FC2) lie in an LDS block staged once per launch;
+//  * each thread's column of the policy FC / value FC1 weights is requested with GLOBAL loads at the heads' entry, in front of the conv1x1 chains, and
+//    arrives during them; the half of the policy column that does not fit the registers follows in groups that are in flight during the fmas before them;
+//  * every x operand is an LDS read at an immediate offset (the shape is a compile-time constant), four at a time where the chain walks a dense row.
+// ---------------------------------------------------------------------------------------------
+struct HeadsAhead {
+    static constexpr int C = 64, P = 81, N = 9, A = 82, PC = 2, VH = 256;
+    // the LDS block (floats; every row starts on 16 bytes)
+    static constexpr int kPconvW = 0, kVconvW = 128, kConvB = 192, kFc2W = 196, kFc2B = 452, kPfcB = 456, kFc1B = 540, kWords = 796;
+    // the scratch at the start of tile 0 (floats; rows on 16 bytes and padded to whole quads: the chains read them four at a time)
+    static constexpr int kPf = 0, kVf = 164, kH1 = 248, kLg = 504, kScratch = 504 + 82 + 16;
+    static constexpr int kRows = 81, kGroup = 27; // weights per thread requested at the entry; the rest of the policy column follows in groups of kGroup
+    __host__ __device__ static bool shape(const HeadParams& hp) { return hp.C == C && hp.P == P && hp.A == A && hp.PC == PC && hp.VH == VH; }
+};
+
+// once per launch, by all NT threads of the workgroup (the caller passes a barrier before the first heads): a weight swap between two launches is safe
+__device__ __forceinline__ void headsAheadStage(const HeadParams& hp, float* __restrict__ hw, int tid, int NT)
+{
+    typedef HeadsAhead L;
+    for (int i = tid; i < L::PC * L::C; i += NT) { hw[L::kPconvW + i] = hp.pconv_w[i]; }
+    for (int i = tid; i < L::C; i += NT) { hw[L::kVconvW + i] = hp.vconv_w[i]; }
+    for (int i = tid; i < 4; i += NT) { hw[L::kConvB + i] = i < L::PC ? hp.pconv_b[i] : i == L::PC ? hp.vconv_b[0] : 0.0f; }
+    for (int i = tid; i < L::VH; i += NT) { hw[L::kFc2W + i] = hp.vfc2_w[i]; }
+    for (int i = tid; i < 4; i += NT) { hw[L::kFc2B + i] = i == 0 ? hp.vfc2_b[0] : 0.0f; }
+    for (int i = tid; i < L::kFc1B - L::kPfcB; i += NT) { hw[L::kPfcB + i] = i < L::A ? hp.pfc_b[i] : 0.0f; }
+    for (int i = tid; i < L::VH; i += NT) { hw[L::kFc1B + i] = hp.vfc1_b[i]; }
+}
+
+// acc = fmaf(x[i], wf(i), acc) for i = I0 .. I1 - 1 in order: x a dense LDS row (16-byte aligned, padded to whole quads) read four at a time, the quads of
+// group g + 1 (GQ of them) in flight during the fmas of group g; wf(i) names the register that holds weight i; pre(g) runs in front of group g's fmas (the
+// policy FC requests the next part of its column there).  The scheduling barriers keep the compiler from pulling all reads to the front (registers) or sinking them.
+template <int I0, int I1, int GQ, class WF, class PRE>
+__device__ __forceinline__ void aheadChain(float& acc, __attribute__((address_space(3))) const float* x, WF wf, PRE pre)
+{
+    typedef float vf4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) const vf4 LF4;
+    constexpr int Q0 = I0 / 4, NQ = (I1 + 3) / 4 - Q0, NG = (NQ + GQ - 1) / GQ;
+    vf4 xb[2][GQ];
+#pragma unroll
+    for (int k = 0; k < GQ; ++k) { if (k < NQ) { xb[0][k] = *(LF4*)(x + 4 * (Q0 + k)); } }
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        pre(g);
+#pragma unroll
+        for (int k = 0; k < GQ; ++k) { if ((g + 1) * GQ + k < NQ) { xb[(g + 1) & 1][k] = *(LF4*)(x + 4 * (Q0 + (g + 1) * GQ + k)); } }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < GQ; ++k) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int i = 4 * (Q0 + g * GQ + k) + e;
+                if (i >= I0 && i < I1) { acc = __builtin_fmaf(xb[g & 1][k][e], wf(i), acc); }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// CS / PW: plane and row stride of the activation tile `xlds` (padded planes, 1-pixel border).  Passes the two workgroup barriers headsBody passes.
+// Waves 6 and 7, if they come here at all (the Go leaf in one piece), have no share but the barriers.
+template <int CS, int PW>
+__device__ __forceinline__ void headsBodyAhead(const HeadParams& hp, float* __restrict__ policy_, float* __restrict__ logit_, float* __restrict__ value_, int tid,
+                                               float* __restrict__ sm, const float* __restrict__ xlds, const float* __restrict__ hw_)
+{
+    typedef HeadsAhead L;
+    typedef float vf4 __attribute__((ext_vector_type(4)));
+    typedef __attribute__((address_space(3))) const float LF;
+    typedef __attribute__((address_space(3))) float LFW;
+    typedef __attribute__((address_space(3))) const vf4 LF4;
+    typedef __attribute__((address_space(1))) const float GF;
+    static_assert((L::C - 1) * CS * 4 + (L::N + 1) * PW * 4 < 65536, "the conv1x1 reads its x operand at immediate offsets");
+    LF* hw = (LF*)hw_;
+    LF* xt = (LF*)xlds;
+    LFW* s = (LFW*)sm;
+    const int lane = tid & 63, wave = tid >> 6;
+
+    MZ_HPROF(5);
+    // stage-2 weights: waves 0-1 one logit per thread (rows 0 .. kRows-1 of its 162), waves 2-5 one hidden unit per thread (all 81 rows).  ONE piece of code
+    // for both roles — column, row stride, x row and bias differ by values the compiler cannot see through: written as two branches, each role's 81 registers
+    // were live across the other's code and the conv1x1 between them (162 and more: spills).
+    constexpr int R = L::kRows, G = L::kGroup;
+    const bool pol = wave < 2;
+    const int a = tid < L::A ? tid : L::A - 1, o = (tid - 128) & (L::VH - 1);
+    GF* wcol = pol ? (GF*)hp.pfc_wT + a : (GF*)hp.vfc1_wT + o;
+    int wstride = __builtin_amdgcn_readfirstlane(pol ? L::A : L::VH);
+    int wnext = __builtin_amdgcn_readfirstlane(pol ? R : 0); // the rows requested behind the barrier: the policy column's second half.  FC1 has none: its waves run the
+    // same requests (one code path, see above; behind a branch on the role the kernel went to 256 VGPRs with 53 spilled) with row stride 0, i.e. 81 times the word they
+    // already hold — one line of the vector cache, no L2 read, and nothing reads the registers they land in
+    int wstride2 = __builtin_amdgcn_readfirstlane(pol ? L::A : 0);
+    int xrow = pol ? L::kPf : L::kVf, brow = pol ? L::kPfcB + a : L::kFc1B + o;
+    asm volatile("" : "+v"(wcol), "+s"(wstride), "+s"(wnext), "+s"(wstride2), "+v"(xrow), "+v"(brow));
+    float w[R];
+    if (wave < 6) {
+#pragma unroll
+        for (int k = 0; k < R; ++k) { w[k] = wcol[k * wstride]; }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+
+    // conv1x1 + folded BN + ReLU: PC policy planes and 1 value plane, one output element per thread
+    if (tid < (L::PC + 1) * L::P) {
+        const int j = tid / L::P, p = tid - j * L::P;
+        LF* xp = xt + (p / L::N + 1) * PW + p % L::N + 1;
+        LF* wj = hw + (j < L::PC ? L::kPconvW + j * L::C : L::kVconvW);
+        float acc = 0.0f;
+        // 4 groups of 16 channels: the 16 x values and 4 weight quads of group g + 1 in flight during the fmas of group g
+        constexpr int CG = 16;
+        float xv[2][CG];
+        vf4 wq[2][CG / 4];
+#pragma unroll
+        for (int k = 0; k < CG; ++k) { xv[0][k] = xp[k * CS]; }
+#pragma unroll
+        for (int k = 0; k < CG / 4; ++k) { wq[0][k] = *(LF4*)(wj + 4 * k); }
+#pragma unroll
+        for (int g = 0; g < L::C / CG; ++g) {
+            if (g + 1 < L::C / CG) {
+#pragma unroll
+                for (int k = 0; k < CG; ++k) { xv[(g + 1) & 1][k] = xp[((g + 1) * CG + k) * CS]; }
+#pragma unroll
+                for (int k = 0; k < CG / 4; ++k) { wq[(g + 1) & 1][k] = *(LF4*)(wj + (g + 1) * CG + 4 * k); }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < CG; ++k) { acc = __builtin_fmaf(xv[g & 1][k], wq[g & 1][k / 4][k & 3], acc); }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        float v = acc + hw[L::kConvB + j];
+        v = v > 0.0f ? v : 0.0f;
+        s[j < L::PC ? L::kPf + tid : L::kVf + p] = v;
+    }
+    __syncthreads();
+    MZ_HPROF(6);
+
+    if (wave < 6) {
+        // rows 0 .. 80 of both roles; meanwhile rows kRows .. 161 of the policy column are requested in three groups of kGroup, each 60 or more fmas in front of
+        // its first use: into w3, and into w[0 .. 2G) behind the fmas that read it (x groups of 20 rows: g == 2 is behind row 39, g == 3 behind row 59)
+        constexpr int GQ = 5;
+        static_assert(R == 3 * G && L::PC * L::P == 2 * R && L::P == R, "three groups at the entry, three behind them");
+        static_assert(2 * 4 * GQ >= G && 3 * 4 * GQ >= 2 * G, "a group of w is refilled behind the fmas that read it");
+        float w3[G];
+        float acc = 0.0f;
+        GF* wn = wcol + wnext * wstride;
+        aheadChain<0, R, GQ>(acc, s + xrow, [&](int i) { return w[i]; },
+            [&](int g) {
+                if (g == 0) {
+#pragma unroll
+                    for (int k = 0; k < G; ++k) { w3[k] = wn[k * wstride2]; }
+                }
+                if (g == 2) {
+#pragma unroll
+                    for (int k = 0; k < G; ++k) { w[k] = wn[(G + k) * wstride2]; }
+                }
+                if (g == 3) {
+#pragma unroll
+                    for (int k = 0; k < G; ++k) { w[G + k] = wn[(2 * G + k) * wstride2]; }
+                }
+            });
+        if (pol) { // rows 81 .. 161: row i lives in w3[i - R] (i < R + G), then in w[i - R - G]
+            aheadChain<R, 2 * R, GQ>(acc, s + L::kPf, [&](int i) { return i < R + G ? w3[i - R] : w[i - R - G]; }, [](int) {});
+        }
+        const float v = acc + hw[brow];
+        if (pol) {
+            if (tid < L::A) {
+                s[L::kLg + tid] = v;
+                logit_[tid] = v;
+            }
+        } else {
+            s[L::kH1 + o] = v > 0.0f ? v : 0.0f;
+        }
+    }
+    __syncthreads();
+    MZ_HPROF(7);
+
+    // value FC2 + tanh: one lane's chain (wave 1, lane 0) while wave 0 does the softmax; weights and h1 four at a time from LDS
+    if (tid == 64) {
+        float acc = 0.0f;
+        // 16 groups of 16 steps: the 4 quads of h1 and of the weights of group g + 1 in flight during the fmas of group g
+        constexpr int GQ = 4;
+        vf4 hb[2][GQ], wb[2][GQ];
+#pragma unroll
+        for (int k = 0; k < GQ; ++k) { hb[0][k] = *(LF4*)(s + L::kH1 + 4 * k); wb[0][k] = *(LF4*)(hw + L::kFc2W + 4 * k); }
+#pragma unroll
+        for (int g = 0; g < L::VH / (4 * GQ); ++g) {
+            if (g + 1 < L::VH / (4 * GQ)) {
+#pragma unroll
+                for (int k = 0; k < GQ; ++k) {
+                    hb[(g + 1) & 1][k] = *(LF4*)(s + L::kH1 + 4 * ((g + 1) * GQ + k));
+                    wb[(g + 1) & 1][k] = *(LF4*)(hw + L::kFc2W + 4 * ((g + 1) * GQ + k));
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < GQ; ++k) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { acc = __builtin_fmaf(hb[g & 1][k][e], wb[g & 1][k][e], acc); }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        value_[0] = mz_tanhf(acc + hw[L::kFc2B]);
+    }
+    if (wave == 0) {
+        float* lg = sm + L::kLg;
+        float m = -3.4e38f;
+        for (int i = lane; i < L::A; i += 64) { m = lg[i] > m ? lg[i] : m; }
+        for (int o = 32; o > 0; o >>= 1) { float m2 = __shfl_xor(m, o); m = m2 > m ? m2 : m; }
+        for (int i = lane; i < L::A; i += 64) { lg[i] = mz_expf(lg[i] - m); }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const float sum = orderedSumWave(lg, L::A, lane);
+        for (int i = lane; i < L::A; i += 64) { policy_[i] = lg[i] / sum; }
+        MZ_HPROF(8);
+    }
+}
+
 
 } // namespace mz

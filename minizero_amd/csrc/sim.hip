@@ -596,6 +596,9 @@ void Net::dumpSimProf()
         fprintf(stderr, "[mz sim prof] terminal leaves: network skipped in %.0f of %.0f simulations (%.2f %%; the game with the most: %.2f %%) -> per simulation that ran them: tower %.2f us, heads %.2f us\n",
                 skipped, sims_all, 100.0 * skipped / std::max(1.0, sims_all), 100.0 * skipped_max, tw / ran * 0.01, hd / ran * 0.01);
     }
+    // sim_kernel<9,9,20,64,2>: the simulations whose heads had their operands delivered ahead (net_body.h headsBodyAhead; tail word [7], a running sum)
+    fprintf(stderr, "[mz sim prof] heads ahead: %llu of the %.0f simulations that ran the network used the heads with their operands delivered ahead\n", tail[7],
+            sims_all - skipped);
     // the value-first order of sim_kernel (sim_az_body.h): what the walk beside the previous simulation's expand met
     fprintf(stderr, "[mz sim prof] value first: %llu of %.0f simulations in the new order; %llu walks arrived at the previous simulation's leaf, %llu waited there (avg %.2f us); "
                     "%llu waits at the join in front of the leaf\n",
@@ -636,6 +639,8 @@ void Net::dumpSimProf()
 }
 
 // upper bound of the dynamic LDS a simulation kernel needs for searches of n simulations (the launch computes the exact figure)
+// The LDS block of sim_kernel<9,9,20,64,2>'s heads (HeadsAhead::kWords floats behind everything counted here) is NOT part of the bound: it is optional — a launch
+// that has no room for it runs the old heads (simLaunch) — and must never turn down a search that fitted without it.
 static size_t simLdsBound(size_t tile_bytes, int n, int A, size_t head_floats)
 {
     const size_t rcp_n = size_t(n) + 5, max_depth = size_t(n) + 3;
@@ -782,9 +787,20 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     }
     // (+ the path-speculation memory of the one-game-per-CU kernels: same condition as simWavesPerEu() == 2)
     const bool two_per_cu = !bf && H * W <= 64 && tile_bytes <= size_t(76) * 1024;
-    const size_t lds = tile_bytes + size_t(a.rcp_n) * sizeof(double) +
+    size_t lds = tile_bytes + size_t(a.rcp_n) * sizeof(double) +
                        (two_per_cu ? 0 : size_t(a.rcp_n) * (sizeof(double) + sizeof(float)) + kSpecWords * sizeof(int)) + (simXchgWords(gv.A, gv.channels, gv.W32) + 2 + 2 * size_t(pool.v_.max_depth) + 2) * sizeof(float) +
                        ((gv.kind == kGo && !two_per_cu) ? size_t(kGoSeenCap) * sizeof(uint64_t) + ((goLeafSmemBytes(gv, pool.v_.max_depth) + 7) & ~size_t(7)) : 0);
+    // sim_kernel<9,9,20,64,2>: the block of launch-invariant head weights behind everything else, on 16 bytes (net_body.h HeadsAhead) — if the network's heads are of
+    // the shape the body is written for and the block still fits; otherwise (or with MZ_SIM_HEADS_LDS=0: tests) the launch keeps the old heads and the old figure
+    if (!bf && !two_per_cu && H == 9 && W == 9 && c0 == 20 && C == 64 && gv.n == 9 && rulesArg(gv.kind, gv.n) == 2 && HeadsAhead::shape(a.hp) &&
+        !(getenv("MZ_SIM_HEADS_LDS") && atoi(getenv("MZ_SIM_HEADS_LDS")) == 0)) {
+        const size_t off = (lds + 15) & ~size_t(15), end = off + HeadsAhead::kWords * sizeof(float);
+        // (the 160 KB hold the instance's static LDS too — s_help, kVfWords words: a block that only fits without them would fail the launch instead of falling back)
+        if (end + kVfWords * sizeof(int) <= size_t(160) * 1024 && HeadsAhead::kScratch * sizeof(float) <= tile_bytes / kTowerTiles) {
+            a.heads_lds = static_cast<int>(off / sizeof(float));
+            lds = end;
+        }
+    }
     rc = uploadSimArgs(a);
     if (rc) { return rc; }
     if (lds > size_t(160) * 1024) { setError("simLaunch: %zu bytes of LDS needed", lds); return MZ_OK; }

@@ -45,7 +45,8 @@ struct SimArgs {
     int no_spec;                      // MZ_NO_SPEC bits (experiments, tests): 1 path speculation of the walk off, 2 helper waves off, 4 fault injection (sim_cluster.h),
                                       // 8 the Go leaf in one piece, 16 the network also runs at terminal leaves (sim_kernel), 32 no tail help (sim_help.h),
                                       // 64 no value-first order: candidates + expand + backup of a simulation in front of the next walk (sim_az_body.h simWalkVf),
-                                      // 128 one helper per game (sim_help.h), 256 no lending (sim_help.h)
+                                      // 128 one helper per game (sim_help.h), 256 no lending (sim_help.h),
+                                      // 512 sim_kernel<9,9,20,64,2> runs the heads of the other instances (net_body.h headsBody) instead of headsBodyAhead
     int cand_coop;                    // the candidate rank sort is shared by the 8 waves (its scratch fits the tower tiles)
     // opt-in bf16x3 tower (net_bf16_body.h): fragments + layer table; used by the BF instantiations of sim_kernel and by sim_kernel_wide_bf16
     const uint4* wfrag;
@@ -66,6 +67,9 @@ struct SimArgs {
     unsigned* help;                   // per-game blocks of `help_words` words, cleared before every launch that helps; nullptr: never
     int help_words;
     int lend_lead;                    // lending (sim_help.h): a workgroup only takes the offer of a game that trails its own by at least this many simulations
+    // sim_kernel<9,9,20,64,2>: word offset, from the start of the dynamic LDS, of the block of launch-invariant head weights (net_body.h HeadsAhead); 0: the launch
+    // has none (no room in the LDS, another head shape, MZ_SIM_HEADS_LDS=0) and runs headsBody.  Last, so that no other field moves.
+    int heads_lds;
 };
 
 // SimArgs never changes during a launch: the device functions read it through the CONSTANT address space, i.e. with scalar loads whose

@@ -488,6 +488,19 @@ __device__ __noinline__ void simHeads(CSimArgs* __restrict__ a, int g, int tid, 
     simHeadsImpl<WPE, BIGA, FP>(a, g, tid, tiles, xtile, xcs, xpw, xchg);
 }
 
+// sim_kernel<9,9,20,64,2> only: the heads with their operands delivered ahead (net_body.h headsBodyAhead); `hw` is the launch's LDS block of small weights.
+// Inlined into the kernel, unlike simHeads: as a function of its own it saved 15 callee-saved VGPRs per wave and call, and it reads the argument block with scalar
+// loads this way; the kernel keeps its 248 VGPRs.  The outputs go to the hand-over block through LDS pointers of game 0's indexing.
+template <int H, int W>
+__device__ __forceinline__ void simHeadsAhead(CSimArgs* __restrict__ a, int tid, float* tiles, const float* xtile, float* xchg, const float* hw)
+{
+    MZ_HPROF(0);
+    const HeadParams hp = ldc(&a->hp);
+    const SimXchg x{HeadsAhead::A + (HeadsAhead::A & 1)};
+    headsBodyAhead<planeStride(H, W), W + 2>(hp, xchg + x.policy(), xchg + x.logit(), xchg + x.scalars(), tid, tiles, xtile, hw);
+    MZ_HPROF(1);
+}
+
 // The terminal flag of the simulation's leaf: wave 0 wrote it into the hand-over block before the first barrier of the simulation (the leaf's first half), every
 // wave reads it behind that barrier.  Scalar, so that the branch on it is one s_cbranch.  MZ_NO_SPEC=16: the network runs at terminal leaves too (A/B, tests).
 __device__ __forceinline__ bool simLeafTerminal(CSimArgs* __restrict__ a, const float* xchg)
@@ -500,7 +513,7 @@ __device__ __forceinline__ bool simLeafTerminal(CSimArgs* __restrict__ a, const 
 
 // MZ_SIM_PROF: the words behind the per-game counters (kSimProfTail of them).  [0..3] belong to the launch that is running — earliest start, first and last exit
 // of a game (100-MHz ticks from [4], the stamp of the previous fold), sum of the exits; sim_prof_fold (sim.hip) adds them to [8..] between two launches.
-constexpr int kSimProfTail = 40; // ([16..20]: the value-first order: simulations, walks that arrived at the previous leaf, waits there, their ticks, waits in front of the leaf;
+constexpr int kSimProfTail = 40; // ([7]: simulations that ran the heads with their operands ahead (simHeadsAhead), a running sum; [16..20]: the value-first order: simulations, walks that arrived at the previous leaf, waits there, their ticks, waits in front of the leaf;
                                  //  tail help: [21] simulations that ran a quad tower, [22] their tower ticks, [23] games whose pair became a quad; why a finished CU stopped looking
                                  //  for a game to help — cause 0: every running game of its XCD with enough simulations left had its helpers, 1: no game of its XCD was running,
                                  //  2: only games with fewer than help_min_left simulations were left — [24 + cause] CUs and [27 + cause] the sum of the ticks at which they
@@ -902,6 +915,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
             __syncthreads();
         }
     }
+    // 9x9 Go x 64 channels: the small launch-invariant weights of the heads in an LDS block of their own behind everything above (net_body.h HeadsAhead), staged
+    // once per launch — the weights only change between launches.  a->heads_lds is the block's word offset, 0 where the launch has no room for it or the network
+    // is not of the shape: the old heads then.  MZ_NO_SPEC=512: the old heads beside a staged block (A/B, tests).
+    constexpr bool kAhead = !BF && H == 9 && W == 9 && CIN0_PAD == 20 && CPAD == 64 && CPL == 2;
+    [[maybe_unused]] const float* heads_w = nullptr;
+    [[maybe_unused]] unsigned long long ahead_n = 0; // (MZ_SIM_PROF) simulations whose heads were the new ones
+    if constexpr (kAhead) {
+        const int off = a->heads_lds;
+        if (off > 0) {
+            headsAheadStage(ldc(&a->hp), tiles + off, tid, 512); // (the barrier in front of the first simulation is behind it)
+            if (!(a->no_spec & 512)) { heads_w = tiles + off; }
+        }
+    }
     unsigned long long* prof = a->prof ? a->prof + size_t(g) * 8 : nullptr;
     int* const node_count = reinterpret_cast<int*>(xchg) - 1; // (the spare word of the path block: simPathView)
     if (tid == 0) { *node_count = a->pv.num_nodes[g]; }
@@ -1031,7 +1057,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         // (the leaf's second half — a terminal leaf's score among it — runs on waves 6 and 7 either way; it passes two barriers, like the heads beside it)
         if constexpr (WPE == 4) { if (!term) { simHeadsImpl<WPE>(a, g, tid, tiles, xt, planeStride(H, W), W + 2, xchg); } }
         else if (leaf_smem && wave >= 6) { simLeafRest<CPL>(a, rot, slot, g, lane, xchg, seen_lds, leaf_smem, 7 - wave); }
-        else if (!term) { simHeads<WPE, false, (MZ_HEADS_FP != 0)>(a, g, tid, tiles, xt, planeStride(H, W), W + 2, xchg); }
+        else if (!term) {
+            bool ahead = false;
+            if constexpr (kAhead) { ahead = heads_w != nullptr; }
+            if (ahead) { if constexpr (kAhead) { simHeadsAhead<H, W>(a, tid, tiles, xt, xchg, heads_w); } }
+            else { simHeads<WPE, false, (MZ_HEADS_FP != 0)>(a, g, tid, tiles, xt, planeStride(H, W), W + 2, xchg); }
+        }
         else if (leaf_smem) { __syncthreads(); __syncthreads(); }
         __syncthreads();
         if (prof) { t3 = wall_clock64(); }
@@ -1049,6 +1080,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                         if (pair && !lent && !term) { pair_n += 1; pair_t += t2 - t1; }
                         if (quad && !term) { quad_n += 1; quad_t += t2 - t1; }
                         if (lent && !term) { lent_n += 1; lent_t += t2 - t1; }
+                        if constexpr (kAhead) { if (heads_w && !term) { ahead_n += 1; } }
                         vf_n += 1;
                     }
                     vf_t0 = t4;
@@ -1092,6 +1124,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
             prof[4] += 1 + (static_cast<unsigned long long>(term) << 32); // simulations | those whose network evaluation was skipped
             if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
             if (quad && !term) { quad_n += 1; quad_t += t2 - t1; }
+            if constexpr (kAhead) { if (heads_w && !term) { ahead_n += 1; } }
         }
         if (kHelp && help_on && tid == 0) { hpStoreU(help_blk + kHpProgress, unsigned(s) + 1u); } // (nsims: the game is done, its helper looks for another one)
     }
@@ -1115,6 +1148,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     if (tid == 0) { a->pv.num_nodes[g] = *node_count; }
     if (prof && tid == 0) {
         simProfExit(a->prof + size_t(games) * 8);
+        if constexpr (kAhead) { if (ahead_n) { atomicAdd(a->prof + size_t(games) * 8 + 7, ahead_n); } } // tail word [7]: simulations that ran the heads with their operands ahead
         if (pair_n) { atomicAdd(a->prof + size_t(games) * 8 + 13, pair_n); atomicAdd(a->prof + size_t(games) * 8 + 14, pair_t); }
         if (quad_n) { atomicAdd(a->prof + size_t(games) * 8 + 21, quad_n); atomicAdd(a->prof + size_t(games) * 8 + 22, quad_t); atomicAdd(a->prof + size_t(games) * 8 + 23, pair_n ? 1ull : 0ull); }
     }
