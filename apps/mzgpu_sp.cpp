@@ -1,5 +1,5 @@
 // mzgpu_sp — the self-play worker executable: drop-in for `minizero_<game> -mode sp` as scripts/zero-worker.sh:160-162
-// launches it:   mzgpu_sp -conf_file F -conf_str "k=v:k=v" -mode sp [-gpu N] [-game go|nogo|othello|tictactoe|atari|gomoku|hex]
+// launches it:   mzgpu_sp -conf_file F -conf_str "k=v:k=v" -mode sp [-gpu N] [-game go|nogo|othello|tictactoe|atari|gomoku|hex|havannah]
 // (argument parsing: ref console/mode_handler.cpp:42-57; the reference bakes the game in at compile time, here it is
 //  the extra key env_game / flag -game).  Without -gpu the process drives EVERY visible GPU, like the reference's ActorGroup
 //  (ref actor/actor_group.cpp:168-187): the unchanged zero-worker.sh (-g 01234567, zero_num_parallel_games = batch x #GPUs) uses the whole node.

@@ -77,6 +77,9 @@ inline std::string mzgpuCollectConfiguration()
 #elif defined(HEX) && HEX
     // the key the reference registers for this game only (configuration.cpp:185)
     o << "env_hex_use_swap_rule=" << env_hex_use_swap_rule << ":env_game=hex";
+#elif defined(HAVANNAH) && HAVANNAH
+    // the key the reference registers for this game only; env_board_size is the edge size N, the network is (2N - 1) x (2N - 1)
+    o << "env_havannah_use_swap_rule=" << env_havannah_use_swap_rule << ":env_game=havannah";
 #elif defined(ATARI) && ATARI
     o << "env_game=atari:atari_init_q=true"; // the #if ATARI init-Q rule of mcts.cpp:211-216
 #else

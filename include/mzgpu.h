@@ -176,7 +176,8 @@ int mz_pool_num_nodes(mz_pool* pool, int game);
 typedef struct mz_worker mz_worker;
 
 /* conf: the reference's "k=v:k=v" configuration string (ref config/configure_loader.cpp:51-117) plus
- * env_game=tictactoe|go|nogo|othello|gomoku|hex|atari (the reference picks the game at compile time).  The worker owns a
+ * env_game=tictactoe|go|nogo|othello|gomoku|hex|havannah|atari (the reference picks the game at compile time; havannah:
+ * env_board_size is the edge size N, the network's board is 2N - 1, AlphaZero networks only).  The worker owns a
  * pool of zero_num_parallel_games trees and a network on `device`. */
 /* desc == NULL and weights == NULL: the network is read from the configuration's nn_file_name (mz_net_read_weight_file), as
  * ActorGroup::createNeuralNetworks does (ref actor_group.cpp:168-177). */
@@ -351,7 +352,7 @@ int mz_env_name(const mz_env* e, char* out, int cap);
  * ------------------------------------------------------------------------------------------ */
 int mz_godev_playout(int device, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots,
                      uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
-/* the same for any game with a device engine ("go", "nogo", "othello", "tictactoe", "gomoku", "hex"): feat_out [steps][channels*ceil(P/32)], legal_out [steps][actions] */
+/* the same for any game with a device engine ("go", "nogo", "othello", "tictactoe", "gomoku", "hex", "havannah": board_size = the edge size, the planes are of the 2N - 1 array): feat_out [steps][channels*ceil(P/32)], legal_out [steps][actions] */
 int mz_envdev_playout(int device, const char* game, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots,
                       uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
 /* ... with the game and its rules from a configuration string as mz_env_create takes it (env_game=gomoku:env_gomoku_rule=outer_open:..., env_game=hex:env_hex_use_swap_rule=false) */

@@ -25,7 +25,7 @@ const Key kKeys[] = {
     K(zero_disable_resign_ratio, T_FLOAT), K(zero_actor_intermediate_sequence_length, T_INT), K(zero_actor_ignored_command, T_STRING),
     K(learner_muzero_unrolling_step, T_INT), K(learner_n_step_return, T_INT), K(zero_num_games_per_iteration, T_INT), K(zero_replay_buffer, T_INT),
     K(learner_use_per, T_BOOL), K(learner_per_alpha, T_FLOAT), K(learner_per_init_beta, T_FLOAT), K(learner_batch_size, T_INT), K(nn_file_name, T_STRING), K(nn_type_name, T_STRING),
-    K(env_board_size, T_INT), K(env_go_komi, T_FLOAT), K(env_go_ko_rule, T_STRING), K(env_gomoku_rule, T_STRING), K(env_gomoku_exactly_five_stones, T_BOOL), K(env_hex_use_swap_rule, T_BOOL), K(env_game, T_STRING), K(atari_init_q, T_BOOL), K(mz_pipeline_lanes, T_INT), K(mz_rng_streams, T_INT), K(mz_zero_copy, T_INT), K(mz_cpu_base, T_INT), K(mz_signal_wait, T_BOOL), K(mz_device_env, T_BOOL), K(mz_raw_observations, T_BOOL), K(mz_sim_kernel, T_BOOL), K(mz_sim_cluster, T_BOOL), K(mz_sim_split, T_BOOL), K(mz_sim_rounds, T_BOOL), K(mz_sim_round_min, T_INT), K(mz_sim_round_alt, T_BOOL), K(mz_sim_round_batch, T_BOOL), K(mz_sim_rounds_board, T_BOOL), K(mz_sim_round_pairs, T_BOOL), K(mz_sim_round_leaves, T_INT), K(mz_manual_step, T_BOOL), K(mz_nn_precision, T_STRING), K(env_atari_name, T_STRING), K(env_atari_episode_length, T_INT),
+    K(env_board_size, T_INT), K(env_go_komi, T_FLOAT), K(env_go_ko_rule, T_STRING), K(env_gomoku_rule, T_STRING), K(env_gomoku_exactly_five_stones, T_BOOL), K(env_hex_use_swap_rule, T_BOOL), K(env_havannah_use_swap_rule, T_BOOL), K(env_game, T_STRING), K(atari_init_q, T_BOOL), K(mz_pipeline_lanes, T_INT), K(mz_rng_streams, T_INT), K(mz_zero_copy, T_INT), K(mz_cpu_base, T_INT), K(mz_signal_wait, T_BOOL), K(mz_device_env, T_BOOL), K(mz_raw_observations, T_BOOL), K(mz_sim_kernel, T_BOOL), K(mz_sim_cluster, T_BOOL), K(mz_sim_split, T_BOOL), K(mz_sim_rounds, T_BOOL), K(mz_sim_round_min, T_INT), K(mz_sim_round_alt, T_BOOL), K(mz_sim_round_batch, T_BOOL), K(mz_sim_rounds_board, T_BOOL), K(mz_sim_round_pairs, T_BOOL), K(mz_sim_round_leaves, T_INT), K(mz_manual_step, T_BOOL), K(mz_nn_precision, T_STRING), K(env_atari_name, T_STRING), K(env_atari_episode_length, T_INT),
 };
 #undef K
 
@@ -36,7 +36,7 @@ const char* const kPassiveKeys[] = {
     "learner_per_beta_anneal", "learner_training_step", "learner_training_display_step",
     "learner_optimizer", "learner_learning_rate", "learner_momentum", "learner_weight_decay", "learner_value_loss_scale",
     "learner_num_thread", "nn_num_blocks", "nn_num_hidden_channels", "nn_num_value_hidden_channels", "env_atari_rom_dir",
-    "env_conhex_use_swap_rule", "env_havannah_use_swap_rule",
+    "env_conhex_use_swap_rule",
     "env_killallgo_ko_rule", "env_killallgo_use_seki", "env_rubiks_scramble_rotate", "env_surakarta_no_capture_plies",
     "env_tetris_block_puzzle_num_holding_block", "env_tetris_block_puzzle_num_preview_holding_block",
 };
@@ -113,6 +113,7 @@ EnvOptions envOptions(const WorkerConfig& c, size_t recent_observations)
     o.gomoku_rule = c.env_gomoku_rule;
     o.gomoku_exactly_five = c.env_gomoku_exactly_five_stones;
     o.hex_use_swap_rule = c.env_hex_use_swap_rule;
+    o.havannah_use_swap_rule = c.env_havannah_use_swap_rule;
     o.atari_name = c.env_atari_name;
     o.atari_episode_length = c.env_atari_episode_length;
     o.atari_recent_observations = recent_observations;

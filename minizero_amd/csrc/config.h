@@ -56,8 +56,9 @@ struct WorkerConfig {
     std::string env_gomoku_rule = "standard"; // env_game=gomoku only: "outer_open" restricts the first move, any other value is the standard rule
     bool env_gomoku_exactly_five_stones = true;
     bool env_hex_use_swap_rule = true; // env_game=hex only (ref hex.cpp:28-47): the second action may take over the first stone
+    bool env_havannah_use_swap_rule = true; // env_game=havannah only (ref havannah.cpp:113-122): the second action may take over the first stone, in the same place
     // run-time replacements of the reference's compile-time switches (-D<GAME>, #if ATARI in mcts.cpp:211)
-    std::string env_game = "tictactoe"; // tictactoe | go | nogo | othello | gomoku | hex | atari (env.h EnvOptions)
+    std::string env_game = "tictactoe"; // tictactoe | go | nogo | othello | gomoku | hex | havannah | atari (env.h EnvOptions)
     bool atari_init_q = false;
     std::string env_atari_name = "ms_pacman";
     int env_atari_episode_length = 1000; // synthetic Atari-shaped environment: steps per episode

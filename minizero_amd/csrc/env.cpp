@@ -1,4 +1,5 @@
 // Host rules engines of libmzgpu — see env.h.  Not a translation of the reference's data structures:
+//   Havannah: two feature bitboards as the reference keeps them + a ring of the last eight, the group of the new stone by a flood, the ring test by a flood of the complement.
 //   NoGo    : Go's board and planes, rules of its own (no capture, no suicide, no pass): flat byte board + early-exit flood fills.
 //   Go      : flat byte board + on-demand early-exit flood fills for captures (no incremental blocks /
 //             liberty bitsets / areas / Benson), one whole-board group pass only when a legal mask is
@@ -12,7 +13,9 @@
 #include "env.h"
 #include "go_dev.h"
 #include "common.h"
+#include <atomic>
 #include <cctype>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -1000,6 +1003,233 @@ private:
 };
 
 // ---------------------------------------------------------------------------------------------
+// Havannah (ref havannah.h:37-75, havannah.cpp:38-231,272-496): a game past the rows of game_kind.h with facts of its own (kHavannah).  Edge size N
+// (env_board_size, the record's SZ, name()) plays on an E x E array, E = 2N - 1 = boardSize(): cell (i, j) has id i * E + j and is on the board iff
+// N - 1 <= i + j <= 3N - 3 (havannah.cpp:321-327); its neighbours are (i-1,j) (i-1,j+1) (i,j-1) (i,j+1) (i+1,j-1) (i+1,j) (havannah.cpp:301-303).  E * E
+// actions, no pass, off-board cells never legal, no symmetries.  With the swap rule every on-board cell is legal on the second action, and choosing the
+// occupied one makes that cell White's where it is (havannah.cpp:113-122).  THE QUIRK THAT IS KEPT: the reference's feature bitboards never clear Black's bit
+// on a swap (havannah.cpp:147 only sets), so from then on the cell is in both history planes while its owner is White — fb_ are those two bitboards as
+// the reference keeps them, and a cell's owner is black = fb_[0] & ~fb_[1], white = fb_[1].
+// The mover wins when the group through the new stone holds two corners (bridge), meets three sides (fork; the corners belong to no side,
+// havannah.cpp:64-86) or closes a ring (isCycle, havannah.cpp:377-395: >= 6 cells, the new stone has >= 2 own neighbours, and either a neighbour of the new
+// stone has six own neighbours or detectHole).  detectHole (havannah.cpp:407-496) floods the complement of the group inside the group's bounding box plus a
+// frame of one cell; everything outside the box is complement and joined to the frame, so this is a flood of the complement over the whole E x E array
+// from its rim — the form used here and on the device.  The reference joins groups incrementally; here the group is found by a flood.
+// ---------------------------------------------------------------------------------------------
+// MZ_HAV_PROF=1 (measurements, tools/hav_flood_share.py): how many win tests ran, passed the ring's two gates, and went on to flood the complement —
+// counted on the host engine, whose leaves under mz_device_env=false are the device engine's leaves (the records of the paths are equal).  Printed at exit.
+struct HavProf {
+    const bool on = getenv("MZ_HAV_PROF") != nullptr;
+    std::atomic<long> tests{0}, gated{0}, flooded{0};
+    ~HavProf() { if (on) { fprintf(stderr, "havannah win tests %ld, past the ring's gates %ld, complement floods %ld\n", tests.load(), gated.load(), flooded.load()); } }
+};
+static HavProf g_hav_prof;
+
+class Havannah final : public GameEnv {
+public:
+    Havannah(int edge, bool swap) : N_(edge), n_(2 * edge - 1), P_(n_ * n_), swap_(swap)
+    {
+        rot_ = rotationTables(n_, P_, true);
+        valid_.clear();
+        corners_.clear();
+        for (auto& s : sides_) { s.clear(); }
+        cells_ = 0;
+        for (int i = 0; i < n_; ++i) { for (int j = 0; j < n_; ++j) { if (onBoard(i, j)) { valid_.set(i * n_ + j); ++cells_; } } }
+        const int N = N_, E = n_;
+        for (int i = 0; i < N - 2; ++i) { // havannah.cpp:69-76
+            sides_[0].set(N + i);
+            sides_[1].set((i + 1) * E + N - 2 - i);
+            sides_[2].set((N + i) * E);
+            sides_[3].set((E - 1) * E + 1 + i);
+            sides_[4].set((E - 1 - i) * E - N + 1 + i);
+            sides_[5].set((N - 1 - i) * E - 1);
+        }
+        for (int c : {N - 1, E - 1, (N - 1) * E, N * E - 1, (E - 1) * E, (E - 1) * E - 1 + N}) { corners_.set(c); } // havannah.cpp:79-85
+        reset();
+    }
+    std::unique_ptr<GameEnv> clone() const override { return std::make_unique<Havannah>(*this); }
+    void copyFrom(const GameEnv& o) override { *this = static_cast<const Havannah&>(o); }
+    void reset() override
+    {
+        turn_ = 1;
+        action_ids_.clear();
+        action_players_.clear();
+        fb_[0].clear();
+        fb_[1].clear();
+        for (auto& h : hist_) { h[0].clear(); h[1].clear(); }
+        hist_len_ = 0;
+        winner_ = 0;
+        first_ = -1;
+    }
+    bool onBoard(int i, int j) const { return i >= 0 && i < n_ && j >= 0 && j < n_ && i + j >= N_ - 1 && i + j <= 3 * N_ - 3; } // havannah.cpp:321-327
+    int owner(int p) const { return fb_[1].test(p) ? 2 : (fb_[0].test(p) ? 1 : 0); }
+    bool isLegal(int a, int) const override // ref havannah.cpp:164-177
+    {
+        if (a < 0 || a >= P_ || !valid_.test(a)) { return false; }
+        return (swap_ && hist_len_ == 1) || owner(a) == 0;
+    }
+    void legalMask(uint8_t* out) const override { for (int a = 0; a < P_; ++a) { out[a] = isLegal(a, turn_); } }
+    bool act(int a, int player) override
+    {
+        if (!isLegal(a, player)) { return false; }
+        actUnchecked(a, player);
+        return true;
+    }
+    void actUnchecked(int a, int player) override // ref havannah.cpp:107-151
+    {
+        action_ids_.push_back(static_cast<int16_t>(a)); // the chosen id, also for a swap (B[k];W[k])
+        action_players_.push_back(static_cast<uint8_t>(player));
+        turn_ = 3 - player;
+        if (hist_len_ == 0) { first_ = a; }
+        // a swap (the second action repeats the first, rule on) needs nothing more than the stone: White's bit decides the owner, Black's bit stays (the quirk)
+        fb_[player - 1].set(a);
+        hist_[hist_len_ & 7][0] = fb_[0];
+        hist_[hist_len_ & 7][1] = fb_[1];
+        ++hist_len_;
+        if (winner_ == 0 && wins(a, player)) { winner_ = player; } // a winner never goes away
+    }
+    template <class F>
+    void forNeighbours(int p, F&& f) const // the on-board neighbours (havannah.cpp:293-313)
+    {
+        static const int di[6] = {-1, -1, 0, 0, 1, 1}, dj[6] = {0, 1, -1, 1, -1, 0};
+        const int i = p / n_, j = p % n_;
+        for (int k = 0; k < 6; ++k) { if (onBoard(i + di[k], j + dj[k])) { f((i + di[k]) * n_ + j + dj[k]); } }
+    }
+    int ownNeighbours(int p, int player) const // havannah.cpp:397-405
+    {
+        int c = 0;
+        forNeighbours(p, [&](int q) { c += owner(q) == player; });
+        return c;
+    }
+    bool wins(int a, int player) const // havannah.cpp:272-291 on the group through `a`
+    {
+        Bits grp;
+        grp.clear();
+        int16_t stack[kMaxP];
+        int top = 0, size = 0;
+        stack[top++] = static_cast<int16_t>(a);
+        grp.set(a);
+        while (top) {
+            const int p = stack[--top];
+            ++size;
+            forNeighbours(p, [&](int q) {
+                if (owner(q) == player && !grp.test(q)) { grp.set(q); stack[top++] = static_cast<int16_t>(q); }
+            });
+        }
+        if (g_hav_prof.on) { ++g_hav_prof.tests; }
+        int corners = 0, sides = 0;
+        for (int w = 0; w < kWords; ++w) { corners += __builtin_popcountll(grp.w[w] & corners_.w[w]); }
+        if (corners >= 2) { return true; } // bridge
+        for (const Bits& s : sides_) {
+            bool meets = false;
+            for (int w = 0; w < kWords; ++w) { meets |= (grp.w[w] & s.w[w]) != 0; }
+            sides += meets;
+        }
+        if (sides >= 3) { return true; } // fork
+        if (size < 6 || ownNeighbours(a, player) < 2) { return false; } // havannah.cpp:380-385
+        bool interior = false;
+        forNeighbours(a, [&](int q) { interior |= ownNeighbours(q, player) == 6; }); // havannah.cpp:388-391: a neighbour of any colour, empty or not
+        if (g_hav_prof.on) { ++g_hav_prof.gated; g_hav_prof.flooded += interior ? 0 : 1; }
+        return interior || hasHole(grp);
+    }
+    // a cell of the array outside the group that the array's rim cannot reach through cells outside the group (six-neighbour adjacency, off-board cells included)
+    bool hasHole(const Bits& grp) const
+    {
+        Bits seen;
+        seen.clear();
+        int16_t stack[kMaxP];
+        int top = 0;
+        for (int p = 0; p < P_; ++p) {
+            const int i = p / n_, j = p % n_;
+            if ((i == 0 || j == 0 || i == n_ - 1 || j == n_ - 1) && !grp.test(p)) { seen.set(p); stack[top++] = static_cast<int16_t>(p); }
+        }
+        static const int di[6] = {-1, -1, 0, 0, 1, 1}, dj[6] = {0, 1, -1, 1, -1, 0};
+        while (top) {
+            const int p = stack[--top], i = p / n_, j = p % n_;
+            for (int k = 0; k < 6; ++k) {
+                const int u = i + di[k], v = j + dj[k];
+                if (u < 0 || u >= n_ || v < 0 || v >= n_) { continue; }
+                const int q = u * n_ + v;
+                if (grp.test(q) || seen.test(q)) { continue; }
+                seen.set(q);
+                stack[top++] = static_cast<int16_t>(q);
+            }
+        }
+        for (int p = 0; p < P_; ++p) { if (!grp.test(p) && !seen.test(p)) { return true; } }
+        return false;
+    }
+    bool isTerminal() const override // ref havannah.cpp:179-184: a winner, or no empty cell on the board (a draw)
+    {
+        if (winner_ != 0) { return true; }
+        int stones = 0;
+        for (int w = 0; w < kWords; ++w) { stones += __builtin_popcountll(fb_[0].w[w] | fb_[1].w[w]); }
+        return stones == cells_;
+    }
+    float evalScore(bool is_resign) const override { return scoreOf(is_resign ? 3 - turn_ : winner_); } // ref havannah.cpp:186-194
+    bool swappable() const { return swap_ && hist_len_ == 1; } // ref havannah.h isSwappable
+    void features(int, float* out) const override // ref havannah.cpp:196-231 (the rotation is the identity: havannah.h:71)
+    {
+        for (int k = 0; k < 8; ++k) {
+            float* own = out + (2 * k) * P_;
+            float* opp = own + P_;
+            // (the reference's history starts with the empty position, whose planes are as empty as those of a position that does not exist)
+            if (hist_len_ - 1 - k < 0) {
+                memset(own, 0, 2 * P_ * sizeof(float));
+                continue;
+            }
+            const Bits* h = hist_[(hist_len_ - 1 - k) & 7];
+            for (int p = 0; p < P_; ++p) {
+                own[p] = h[turn_ - 1].test(p) ? 1.0f : 0.0f;
+                opp[p] = h[2 - turn_].test(p) ? 1.0f : 0.0f;
+            }
+        }
+        const float sw = swappable() ? 1.0f : 0.0f, b = turn_ == 1 ? 1.0f : 0.0f, w = turn_ == 2 ? 1.0f : 0.0f;
+        for (int p = 0; p < P_; ++p) {
+            out[16 * P_ + p] = valid_.test(p) ? 1.0f : 0.0f;
+            out[17 * P_ + p] = sw;
+            out[18 * P_ + p] = b;
+            out[19 * P_ + p] = w;
+        }
+    }
+    int actionFromString(const std::string& str) const override // console coordinates on the E x E array (havannah.h:30), on-board cells only; no pass
+    {
+        std::string up = str;
+        for (char& c : up) { c = static_cast<char>(std::toupper(static_cast<unsigned char>(c))); }
+        if (up == "PASS") { return -1; }
+        const int a = GameEnv::actionFromString(str);
+        return a >= 0 && a < P_ && valid_.test(a) ? a : -1;
+    }
+    GameKind deviceKind() const override { return kHavannah; }
+    void exportDeviceRoot(void* dst) const override // (go_body.h havLeafBody: the two feature bitboards, the ring of past positions, the winner, the swap flag)
+    {
+        static_assert(kWords == kGoMaxW, "device snapshot layout");
+        GoRootSnapshot& s = *static_cast<GoRootSnapshot*>(dst);
+        memcpy(s.stones, fb_, sizeof(s.stones));
+        memcpy(s.hist, hist_, sizeof(s.hist));
+        s.hash = swap_ ? kHavSwap : 0; // (hist_len is taken by the ring, so the rule flag travels in the word only Go uses)
+        s.hist_len = hist_len_;
+        s.turn = turn_;
+        s.nmoves = static_cast<int32_t>(action_ids_.size());
+        s.winner() = winner_;
+    }
+    int numInputChannels() const override { return gameChannels(kHavannah); }
+    int boardSize() const override { return n_; } // the network board E (game_kind.h networkBoard); the edge size is in name() and the SZ tag
+    int policySize() const override { return P_; }
+    std::string name() const override { return "havannah" + std::to_string(N_) + "x" + std::to_string(N_); } // ref havannah.h:68 (no underscore)
+    std::vector<std::pair<std::string, std::string>> loaderTags() const override { return {{"SZ", std::to_string(N_)}}; } // the edge size (base_env.h: SZ = env_board_size)
+
+private:
+    int N_, n_, P_; // edge size, side of the array, cells of the array
+    bool swap_;
+    int cells_;     // cells on the board: 3N(N - 1) + 1
+    Bits valid_, corners_, sides_[6];
+    Bits fb_[2];    // the reference's bitboard_pair_ (black keeps the bit of a swapped stone)
+    Bits hist_[8][2];
+    int hist_len_;  // positions so far = actions played (a swap is one)
+    int winner_, first_;
+};
+
+// ---------------------------------------------------------------------------------------------
 // Atari-shaped synthetic environment (BASELINE configs[4]; ALE, OpenCV and the ROMs are not available).
 // Feature contract of the reference's AtariEnv (ref atari.h:17-27, atari.cpp:48-131): 1 player, 18 actions all legal,
 // features = for the last 8 steps [1 plane action_id / 18, 3 planes RGB / 255 of a 96x96 screen], oldest first.
@@ -1191,7 +1421,7 @@ std::unique_ptr<GameEnv> createGameEnv(const EnvOptions& o)
 {
     if (o.game == "atari") { return std::make_unique<AtariSynth>(o.atari_name, o.atari_episode_length, std::max<size_t>(1, o.atari_recent_observations)); }
     const GameKind k = gameFromName(o.game.c_str());
-    if (k == kNoDeviceGame) { setError("unknown env_game '%s' (tictactoe | go | nogo | othello | gomoku | hex | atari)", o.game.c_str()); return nullptr; }
+    if (k == kNoDeviceGame) { setError("unknown env_game '%s' (tictactoe | go | nogo | othello | gomoku | hex | havannah | atari)", o.game.c_str()); return nullptr; }
     const int n = o.board_size > 0 ? o.board_size : gameDefaultBoard(k);
     switch (k) {
     case kTicTacToe: return std::make_unique<TicTacToe>();
@@ -1211,6 +1441,10 @@ std::unique_ptr<GameEnv> createGameEnv(const EnvOptions& o)
     case kHex: // ref hex.h:12,63
         if (n < 2 || n > kMaxN) { setError("hex board size %d not supported (2..19)", n); return nullptr; }
         return std::make_unique<Hex>(n, o.hex_use_swap_rule);
+    case kHavannah: // ref havannah.h:41,74: edge size 8; the array of edge size 10 is 19 x 19, the widest the bitboards hold
+        if (n < gameMinBoard(kHavannah)) { setError("havannah board size %d not supported: the edge size is at least %d (ref havannah.h:41)", n, gameMinBoard(kHavannah)); return nullptr; }
+        if (n > kHavannahMaxBoard) { setError("havannah board size %d not supported: edge sizes up to %d (a %dx%d array) have an engine", n, kHavannahMaxBoard, networkBoard(kHavannah, kHavannahMaxBoard), networkBoard(kHavannah, kHavannahMaxBoard)); return nullptr; }
+        return std::make_unique<Havannah>(n, o.havannah_use_swap_rule);
     default: return nullptr;
     }
 }

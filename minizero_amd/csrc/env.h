@@ -89,14 +89,15 @@ protected:
 
 // What createGameEnv needs to know, by configuration key (config.h envOptions fills it from a WorkerConfig).
 struct EnvOptions {
-    std::string game = "tictactoe";          // env_game: "tictactoe" | "go" | "nogo" | "othello" | "gomoku" | "hex" (game_kind.h), or "atari": the synthetic Atari-shaped
+    std::string game = "tictactoe";          // env_game: "tictactoe" | "go" | "nogo" | "othello" | "gomoku" | "hex" | "havannah" (game_kind.h), or "atari": the synthetic Atari-shaped
                                              // environment (18 actions, 32 x 96 x 96 features, 1 player)
-    int board_size = 0;                      // env_board_size; 0 = the game's default (gameDefaultBoard)
+    int board_size = 0;                      // env_board_size; 0 = the game's default (gameDefaultBoard).  Havannah: the edge size N, the engine's board is 2N - 1 (networkBoard)
     float go_komi = 7.5f;                    // (NoGo: carried in the record's KM tag only; go_ko_rule is ignored there)
     std::string go_ko_rule = "positional";
     std::string gomoku_rule = "standard";    // "outer_open" restricts the first move; any other value is the standard rule, as in ref gomoku.cpp:52
     bool gomoku_exactly_five = true;         // env_gomoku_exactly_five_stones (an overline does not win)
     bool hex_use_swap_rule = true;           // env_hex_use_swap_rule (ref hex.cpp:28-47,86-99)
+    bool havannah_use_swap_rule = true;      // env_havannah_use_swap_rule (ref havannah.cpp:113-122,174-176)
     std::string atari_name = "ms_pacman";
     int atari_episode_length = 1000;
     // observation strings kept for the OBS tag (ref atari.cpp:87: intermediate sequence length + 8 + n-step + unrolling + 1, or everything when sequences are off)

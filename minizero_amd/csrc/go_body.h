@@ -1081,15 +1081,230 @@ __device__ __forceinline__ void nogoLeafBody(const GoDevView& v, const PoolView&
     }
 }
 
+// ---- Havannah (ref havannah.cpp:38-231,272-496; a game past the rows, game_kind.h kHavannah): the view's board is the E x E array (E = 2N - 1 for edge
+// size N, game_kind.h networkBoard), cell (r, c) = id r * E + c is on the board iff N - 1 <= r + c <= 3N - 3, a cell's neighbours are at -E, -E+1, -1, +1,
+// +E-1, +E (havannah.cpp:301-303).  The slot layout is Gomoku's: the two FEATURE bitboards as the reference keeps them — after a swap the cell is in both,
+// havannah.cpp:147 only sets — and `meta` (actions played, the winner); a cell's owner is black = fb[0] & ~fb[1], white = fb[1], so a swap is nothing but
+// White's bit on an occupied cell.  History planes as in NoGo: the position k actions before the leaf is the slot of the k-th ancestor, older ones are in the
+// root's ring.  The position is wave-uniform, so every set below is a bitboard of NW scalar words (1, 2, 4 or kGoMaxW as the array needs; word indices static):
+//   group   = flood of the mover's cells from the new stone by six-shift dilation to a fixpoint;
+//   bridge  = the group holds two of the six corners, fork = it meets three of the six sides (masks by ballot from the lane's (r, c); havannah.cpp:64-86);
+//   ring    = >= 6 cells, the new stone has >= 2 own neighbours, and either a neighbour of the new stone has six own neighbours (six shifted ANDs) or the
+//             complement of the group, flooded inside the array from the array's rim, leaves a cell out (detectHole, havannah.cpp:407-496: its bounding
+//             box plus frame is this flood restricted to where it can matter — DESIGN.md §3.13).  Most leaves fail a gate and never flood the complement.
+template <int NW>
+struct HavGeo {
+    unsigned long long full[NW], ncl[NW], ncr[NW], board[NW]; // in the array; not column 0; not column E - 1; on the board
+    int r[NW], c[NW];                                         // the lane's cell 64 * i + lane
+    int E, N, lane;
+};
+
+// the six neighbour terms of a set: any[i] = cells with a neighbour in b (the dilation), all[i] = cells whose six neighbours are all in b
+template <int NW>
+__device__ __forceinline__ void havTerms(const HavGeo<NW>& k, const unsigned long long (&b)[NW], unsigned long long (&any)[NW], unsigned long long (&all)[NW])
+{
+    const int s1 = k.E, sm = k.E - 1; // 6 <= sm < s1 <= 19: every shift count below is in 1 .. 63
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const unsigned long long below = i > 0 ? b[i - 1] : 0ull, above = i + 1 < NW ? b[i + 1] : 0ull;
+        const unsigned long long a1 = ((b[i] << 1) | (below >> 63)) & k.ncl[i];          // bit x = b[x - 1]:     (r, c - 1)
+        const unsigned long long a2 = ((b[i] >> 1) | (above << 63)) & k.ncr[i];          // bit x = b[x + 1]:     (r, c + 1)
+        const unsigned long long a3 = (b[i] << s1) | (below >> (64 - s1));               // bit x = b[x - E]:     (r - 1, c)
+        const unsigned long long a4 = (b[i] >> s1) | (above << (64 - s1));               // bit x = b[x + E]:     (r + 1, c)
+        const unsigned long long a5 = ((b[i] << sm) | (below >> (64 - sm))) & k.ncr[i];  // bit x = b[x - E + 1]: (r - 1, c + 1)
+        const unsigned long long a6 = ((b[i] >> sm) | (above << (64 - sm))) & k.ncl[i];  // bit x = b[x + E - 1]: (r + 1, c - 1)
+        any[i] = (a1 | a2 | a3 | a4 | a5 | a6) & k.full[i];
+        all[i] = a1 & a2 & a3 & a4 & a5 & a6 & k.full[i];
+    }
+}
+
+// `seed`, grown through `through` to a fixpoint (seed must lie in `through`)
+template <int NW>
+__device__ __forceinline__ void havFlood(const HavGeo<NW>& k, const unsigned long long (&through)[NW], unsigned long long (&r)[NW])
+{
+    for (int round = 0; round < k.E * k.E; ++round) { // (a set's diameter is below the cell count: the bound is never what ends the loop)
+        unsigned long long d[NW], all[NW], grown = 0;
+        havTerms<NW>(k, r, d, all);
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const unsigned long long grow = d[i] & through[i] & ~r[i];
+            r[i] |= grow;
+            grown |= grow;
+        }
+        if (grown == 0) { break; }
+    }
+}
+
+// has the mover, whose cells are `mine`, won with the stone at `a`?  (updateWinner, havannah.cpp:272-291)
+template <int NW>
+__device__ __forceinline__ bool havWins(const HavGeo<NW>& k, const unsigned long long (&mine)[NW], int a)
+{
+    const int E = k.E, N = k.N;
+    unsigned long long one[NW], grp[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { one[i] = i == (a >> 6) ? 1ull << (a & 63) : 0ull; grp[i] = one[i]; }
+    havFlood<NW>(k, mine, grp);
+    int corners = 0, size = 0;
+    unsigned sides = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int r = k.r[i], c = k.c[i], s = r + c;
+        const bool e0 = r == 0, e1 = s == N - 1, e2 = c == 0, e3 = r == E - 1, e4 = s == 3 * N - 3, e5 = c == E - 1; // the six edge lines of the hexagon
+        const int lines = int(e0) + int(e1) + int(e2) + int(e3) + int(e4) + int(e5);
+        const bool onb = (k.board[i] >> k.lane) & 1;
+        corners += __popcll(grp[i] & __ballot(onb && lines == 2)); // a corner lies on two lines (havannah.cpp:79-85), a side cell on one (havannah.cpp:64-76)
+        sides |= (grp[i] & __ballot(onb && lines == 1 && e0)) != 0 ? 1u : 0u;
+        sides |= (grp[i] & __ballot(onb && lines == 1 && e1)) != 0 ? 2u : 0u;
+        sides |= (grp[i] & __ballot(onb && lines == 1 && e2)) != 0 ? 4u : 0u;
+        sides |= (grp[i] & __ballot(onb && lines == 1 && e3)) != 0 ? 8u : 0u;
+        sides |= (grp[i] & __ballot(onb && lines == 1 && e4)) != 0 ? 16u : 0u;
+        sides |= (grp[i] & __ballot(onb && lines == 1 && e5)) != 0 ? 32u : 0u;
+        size += __popcll(grp[i]);
+    }
+    if (corners >= 2 || __popc(sides) >= 3) { return true; } // bridge, fork
+    // ring (isCycle, havannah.cpp:377-395): the two gates, the shortcut, then the flood of the complement
+    if (size < 6) { return false; }
+    unsigned long long near[NW], inner[NW], unused[NW];
+    havTerms<NW>(k, one, near, unused);  // the neighbours of the new stone
+    havTerms<NW>(k, mine, unused, inner); // the cells with six own neighbours (of any colour, empty or not: havannah.cpp:388-391)
+    int own = 0;
+    unsigned long long blob = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { own += __popcll(near[i] & mine[i]); blob |= near[i] & inner[i]; }
+    if (own < 2) { return false; }
+    if (blob != 0) { return true; }
+    unsigned long long bg[NW], reach[NW];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const bool in = (k.full[i] >> k.lane) & 1;
+        bg[i] = k.full[i] & ~grp[i];
+        reach[i] = bg[i] & __ballot(in && (k.r[i] == 0 || k.c[i] == 0 || k.r[i] == E - 1 || k.c[i] == E - 1));
+    }
+    havFlood<NW>(k, bg, reach);
+    unsigned long long hole = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { hole |= bg[i] & ~reach[i]; }
+    return hole != 0;
+}
+
+template <int NW>
+__device__ __forceinline__ void havLeafBodyT(const GoDevView& v, const PoolView& pv, int slot, int g, int lane)
+{
+    const int P = v.P, E = v.n, W = v.W, MD = pv.max_depth; // W <= NW
+    const int len = pv.path_len[g];
+    const int* path = pv.path + size_t(g) * MD;
+    const int* pact = pv.path_action + size_t(g) * MD;
+    const int depth = len - 1;
+    const GoRootSnapshot& S = v.snap[g];
+    const int root_turn = S.turn, root_hist_len = S.hist_len;
+    const bool rule = (S.hash & kHavSwap) != 0;
+    const size_t sb = size_t(g) * v.slots;
+    const int* hs = pv.hslot + size_t(g) * pv.cap;
+    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    unsigned long long fb[2][NW]; // [black, white][word]: the feature bitboards
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        fb[0][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 0) * W + i]) : 0ull;
+        fb[1][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 1) * W + i]) : 0ull;
+    }
+    int nact = __builtin_amdgcn_readfirstlane(v.meta[(sb + src) * 2]), winner = __builtin_amdgcn_readfirstlane(v.meta[(sb + src) * 2 + 1]);
+    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
+    HavGeo<NW> k;
+    k.E = E;
+    k.N = (E + 1) / 2;
+    k.lane = lane;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const int q = 64 * i + lane, r = q / E, c = q - r * E;
+        const bool in = q < P;
+        k.r[i] = r;
+        k.c[i] = c;
+        k.full[i] = __ballot(in);
+        k.ncl[i] = __ballot(in && c != 0);
+        k.ncr[i] = __ballot(in && c != E - 1);
+        k.board[i] = __ballot(in && r + c >= k.N - 1 && r + c <= 3 * k.N - 3); // havannah.cpp:321-327
+    }
+    if (depth >= 1) { // havannah.cpp:107-151
+        const int a = __builtin_amdgcn_readfirstlane(pact[len - 1]), m = 3 - t; // moved by the other player
+        ++nact;
+        unsigned long long mine[NW];
+#pragma unroll
+        for (int i = 0; i < NW; ++i) { // (selects, never a dynamic register index)
+            const unsigned long long bit = i == (a >> 6) ? 1ull << (a & 63) : 0ull;
+            fb[0][i] |= m == 1 ? bit : 0ull;
+            fb[1][i] |= m == 2 ? bit : 0ull; // on the occupied cell, on the second action: the swap — the cell is White's from here on
+            mine[i] = m == 1 ? fb[0][i] & ~fb[1][i] : fb[1][i];
+        }
+        if (winner == 0 && havWins<NW>(k, mine, a)) { winner = m; } // a winner never goes away (and the floods are skipped)
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < NW; ++i) {
+                if (i < W) {
+                    v.stones[((sb + slot) * 2 + 0) * W + i] = fb[0][i];
+                    v.stones[((sb + slot) * 2 + 1) * W + i] = fb[1][i];
+                }
+            }
+            v.meta[(sb + slot) * 2] = nact;
+            v.meta[(sb + slot) * 2 + 1] = winner;
+        }
+    }
+    int stones = 0, cells = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) { stones += __popcll(fb[0][i] | fb[1][i]); cells += __popcll(k.board[i]); }
+    const bool terminal = winner != 0 || stones == cells; // ref havannah.cpp:179-184: a full board is a draw
+    const bool swappable = rule && nact == 1;             // havannah.cpp:174-176: every cell of the board is legal on the second action
+    // planes (ref havannah.cpp:196-231): lane ch < 16 holds plane ch = own / opponent feature bitboard ch / 2 actions before the leaf (no rotation: the maps are
+    // the identity, so a plane's word is the history word itself), lanes 16 .. 19 the board, swappable, black to move, white to move
+    const int avail = root_hist_len + depth;
+    const int kk = lane >> 1, colour = (lane & 1) == 0 ? t - 1 : 2 - t;
+    uint32_t* out = v.feat + size_t(g) * 20 * v.W32;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        if (i >= W) { continue; }
+        if (lane == 0) { v.legal[size_t(g) * v.LW + i] = swappable ? k.board[i] : k.board[i] & ~(fb[0][i] | fb[1][i]); }
+        unsigned long long word = 0;
+        if (lane < 16) {
+            if (kk < avail) {
+                if (kk == 0) { word = colour == 0 ? fb[0][i] : fb[1][i]; }
+                else if (kk < depth) { word = v.stones[((sb + hs[path[len - 1 - kk]]) * 2 + colour) * W + i]; }
+                else { word = S.hist[(root_hist_len - 1 - (kk - depth)) & 7][colour][i]; }
+            }
+        }
+        if (lane == 16) { word = k.board[i]; }
+        if (lane == 17) { word = swappable ? k.full[i] : 0ull; }
+        if (lane == 18) { word = t == 1 ? k.full[i] : 0ull; }
+        if (lane == 19) { word = t == 2 ? k.full[i] : 0ull; }
+        if (lane < 20) {
+            if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(word); }
+            if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(word >> 32); }
+        }
+    }
+    if (lane == 0) {
+        v.leaf_player[g] = t;
+        v.terminal[g] = terminal ? 1 : 0;
+        v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); // ref havannah.cpp:186-194
+    }
+}
+
+__device__ __forceinline__ void havLeafBody(const GoDevView& v, const PoolView& pv, int /*rot: no symmetries, havannah.h:71*/, int slot, int g, int lane)
+{
+    // NW = the words the array needs: 1 for N = 4 (7x7), 2 up to N = 6, 4 for the default N = 8 (15x15), kGoMaxW up to N = 10 (19x19)
+    if (v.W <= 1) { havLeafBodyT<1>(v, pv, slot, g, lane); }
+    else if (v.W <= 2) { havLeafBodyT<2>(v, pv, slot, g, lane); }
+    else if (v.W <= 4) { havLeafBodyT<4>(v, pv, slot, g, lane); }
+    else { havLeafBodyT<kGoMaxW>(v, pv, slot, g, lane); }
+}
+
 // leafBody<CPL> of the two-bitboard games (the template arguments behind CPL, `smem` and `seen_lds` are Go's: unused here)
 template <int CPL, bool EXT_PLANES = false, int PART = 0, bool SYNC = false, int ROLE = 0, std::enable_if_t<(CPL <= 0), int> = 0>
 __device__ __forceinline__ void leafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane, uint64_t* = nullptr, const uint64_t* = nullptr)
 {
-    static_assert(CPL == kRulesTicTacToe || CPL == kRulesOthello || CPL == kRulesGomoku || CPL == kRulesHex || CPL == kRulesNoGo, "no leaf body for this rules argument");
+    static_assert(CPL == kRulesTicTacToe || CPL == kRulesOthello || CPL == kRulesGomoku || CPL == kRulesHex || CPL == kRulesNoGo || CPL == kRulesHavannah, "no leaf body for this rules argument");
     if constexpr (CPL == kRulesTicTacToe) { tttLeafBody(v, pv, rot, slot, g, lane); }
     else if constexpr (CPL == kRulesOthello) { othLeafBody(v, pv, rot, slot, g, lane); }
     else if constexpr (CPL == kRulesGomoku) { gmkLeafBody(v, pv, rot, slot, g, lane); }
     else if constexpr (CPL == kRulesNoGo) { nogoLeafBody(v, pv, rot, slot, g, lane); }
+    else if constexpr (CPL == kRulesHavannah) { havLeafBody(v, pv, rot, slot, g, lane); }
     else { hexLeafBody(v, pv, rot, slot, g, lane); }
 }
 

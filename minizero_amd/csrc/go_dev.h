@@ -43,6 +43,7 @@ static_assert(offsetof(GoRootSnapshot, hist_len) == offsetof(GoRootSnapshot, has
 // GoRootSnapshot::ruleBits() of Gomoku (env_gomoku_rule=outer_open, env_gomoku_exactly_five_stones) and of Hex (env_hex_use_swap_rule)
 constexpr int kGmkOuterOpen = 1, kGmkExactlyFive = 2;
 constexpr int kHexSwap = 1;
+constexpr int kHavSwap = 1; // Havannah (env_havannah_use_swap_rule): in `hash`, which only Go uses — `hist_len` is taken by the ring of past positions there
 
 struct RotPack { uint32_t w[kRotPackGames / 10]; }; // per-game feature rotation of one cycle, passed as a kernel argument
 inline void rotPackSet(RotPack& r, int g, int rot) { r.w[g / 10] = (r.w[g / 10] & ~(7u << (3 * (g % 10)))) | (uint32_t(rot) << (3 * (g % 10))); }
@@ -103,7 +104,7 @@ inline bool forRulesArg(int cpl, F&& f)
     switch (cpl) {
 #define MZ_RULES_CASE(K) case K: f(std::integral_constant<int, K>{}); return true;
         MZ_RULES_CASE(1) MZ_RULES_CASE(2) MZ_RULES_CASE(3) MZ_RULES_CASE(4) MZ_RULES_CASE(5) MZ_RULES_CASE(6)
-        MZ_RULES_CASE(kRulesOthello) MZ_RULES_CASE(kRulesTicTacToe) MZ_RULES_CASE(kRulesGomoku) MZ_RULES_CASE(kRulesHex) MZ_RULES_CASE(kRulesNoGo)
+        MZ_RULES_CASE(kRulesOthello) MZ_RULES_CASE(kRulesTicTacToe) MZ_RULES_CASE(kRulesGomoku) MZ_RULES_CASE(kRulesHex) MZ_RULES_CASE(kRulesNoGo) MZ_RULES_CASE(kRulesHavannah)
 #undef MZ_RULES_CASE
     default: return false;
     }

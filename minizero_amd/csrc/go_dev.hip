@@ -66,6 +66,10 @@ int GoDevice::init(int device, int games, int board_n, float komi, int action_si
     const GameKind kind = static_cast<GameKind>(kind_arg);
     if (kind == kOthello && board_n > gameMaxBoard(kOthello)) { setError("GoDevice: Othello boards up to 8x8"); return MZ_ERR_ARG; }
     if (kind == kNoGo && board_n > kNoGoMaxBoard) { setError("GoDevice: NoGo boards up to %dx%d", kNoGoMaxBoard, kNoGoMaxBoard); return MZ_ERR_ARG; } // (nogoLeafBody: two words per bitboard)
+    if (kind == kHavannah && (board_n % 2 == 0 || board_n < networkBoard(kHavannah, gameMinBoard(kHavannah)) || board_n > networkBoard(kHavannah, kHavannahMaxBoard))) { // (board_n: the array's side 2N - 1)
+        setError("GoDevice: Havannah arrays of 7x7 .. 19x19 (edge sizes %d .. %d)", gameMinBoard(kHavannah), kHavannahMaxBoard);
+        return MZ_ERR_ARG;
+    }
     if (kind == kTicTacToe && (board_n != 3 || action_size != 9)) { setError("GoDevice: TicTacToe is 3x3 with 9 actions"); return MZ_ERR_ARG; }
     if (board_n < 2 || board_n > kGoMaxN || games < 1 || games > kRotPackGames || action_size != board_n * board_n + (gameHasPass(kind) ? 1 : 0)) {
         setError("GoDevice: unsupported shape (board %d, %d games, %d actions)", board_n, games, action_size);

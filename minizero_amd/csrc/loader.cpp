@@ -287,7 +287,9 @@ bool Loader::parse(const std::string& content, LGame* g)
     auto tag = [&](const char* k) -> const std::string* { for (auto& kv : tags) { if (kv.first == k) { return &kv.second; } } return nullptr; };
     g->board = board_size;
     const int n = g->size();
-    if (!atari_ && board_size != proto_->boardSize()) { setError("loader: record of a %dx%d board, the loader is configured for %dx%d", board_size, board_size, proto_->boardSize(), proto_->boardSize()); return false; }
+    // (the record's SZ is env_board_size: the engine's board everywhere but in Havannah, whose SZ is the edge size N of a 2N - 1 array — game_kind.h networkBoard)
+    const int proto_sz = atari_ ? 0 : (proto_->deviceKind() == kHavannah ? (proto_->boardSize() + 1) / 2 : proto_->boardSize());
+    if (!atari_ && board_size != proto_sz) { setError("loader: record of a %dx%d board, the loader is configured for %dx%d", board_size, board_size, proto_sz, proto_sz); return false; }
     for (int i = 0; i < n; ++i) { if (g->action[i] < 0 || g->action[i] >= A_) { setError("loader: action %d out of range in a record", g->action[i]); return false; } }
     // The device replay (loader_kernels.hip) takes the mover from the move's parity: the reference replays act(action) with the RECORDED player
     // (base_env.h:235-241), so a record whose colours do not alternate from the first player (handicap stones, hand-edited files) would give other
@@ -304,11 +306,15 @@ bool Loader::parse(const std::string& content, LGame* g)
         std::vector<float> planes;
         for (int i = 0; i < n; ++i) {
             const int a = g->action[i];
-            if (env->act(a, g->player[i])) { continue; }
+            // (Havannah's rules go on accepting stones after a win: a record that plays on past the end is refused, the device replay keeps the first winner)
+            const bool over = proto_->deviceKind() == kHavannah && env->isTerminal();
+            if (!over && env->act(a, g->player[i])) { continue; }
             const char* why = "not allowed by the rules";
             planes.resize(feat_size_);
             env->features(0, planes.data()); // planes 0 and 1: the stones of the player to move and of the other one, in all five games
             if (a >= P_) { why = proto_->deviceKind() == kNoGo ? "NoGo has no pass" : "pass while a move exists"; }
+            else if (over) { why = "the game has ended"; }
+            else if (proto_->deviceKind() == kHavannah && planes[16 * P_ + a] == 0.0f) { why = "off the board"; } // plane 16: the cells of the hexagon
             else if (planes[a] != 0.0f || planes[P_ + a] != 0.0f) { why = "occupied point"; }
             else if (proto_->deviceKind() == kGo) { why = "suicide or repeated position"; }
             else if (proto_->deviceKind() == kNoGo) { why = "captures or is suicide"; }

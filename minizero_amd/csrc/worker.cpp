@@ -352,6 +352,10 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     device_ = device;
     if (device >= 0 && device < 64) { counted_device_ = device; g_workers_on_device[device].fetch_add(1); }
     if (cfg_.nn_type_name == "muzero" && desc.type == 0) { setError("nn_type_name=muzero but the network descriptor is alphazero"); return MZ_ERR_ARG; }
+    if (gameFromName(cfg_.env_game.c_str()) == kHavannah && (cfg_.nn_type_name != "alphazero" || desc.type != 0)) { // ref havannah.cpp:233-236: getActionFeatures throws
+        setError("env_game=havannah has no action features: a MuZero network cannot play it (nn_type_name=alphazero only, ref havannah.cpp:233-236)");
+        return MZ_ERR_ARG;
+    }
     if (cfg_.zero_num_parallel_games <= 0 || cfg_.actor_num_simulation <= 0) { setError("zero_num_parallel_games and actor_num_simulation must be > 0"); return MZ_ERR_ARG; }
     if (cfg_.zero_num_parallel_games > 4096) { setError("zero_num_parallel_games > 4096 (ref alphazero_network.h:120 kReserved_batch_size)"); return MZ_ERR_ARG; }
     if (cfg_.mz_nn_precision != "f32" && cfg_.mz_nn_precision != "bf16x3") { setError("mz_nn_precision '%s' unknown (f32 | bf16x3)", cfg_.mz_nn_precision.c_str()); return MZ_ERR_ARG; }
@@ -1987,6 +1991,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         if (gameFromName(cfg_.env_game.c_str()) == kGomoku) { MZ_FIXED(env_gomoku_rule) MZ_FIXED(env_gomoku_exactly_five_stones) }
         // ... and so does Hex's swap rule
         if (gameFromName(cfg_.env_game.c_str()) == kHex) { MZ_FIXED(env_hex_use_swap_rule) }
+        if (gameFromName(cfg_.env_game.c_str()) == kHavannah) { MZ_FIXED(env_havannah_use_swap_rule) }
 #undef MZ_FIXED
         if (fixed) { setError("update_config: %s is fixed when the worker is created (restart the worker to change it)", fixed); return MZ_ERR_ARG; }
         cfg_ = nc;

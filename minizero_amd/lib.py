@@ -61,6 +61,8 @@ DESCS = {
     "c3": lambda: make_desc("othello_8x8", 4, 8, 8, 64, 8, 8, 1, 6, 65),
     "c4": lambda: make_desc("go_9x9", 18, 9, 9, 64, 9, 9, 1, 6, 82, type_name="muzero"),
     "c5": lambda: make_desc("atari_ms_pacman", 32, 96, 96, 64, 6, 6, 18, 6, 18, 256, 601, type_name="muzero_atari"),
+    # Havannah at its default edge size 8: the network's board is the 15x15 array (2N - 1), 20 planes, no pass
+    "havannah8x64": lambda: make_desc("havannah8x8", 20, 15, 15, 64, 15, 15, 1, 6, 225),
 }
 CONFIGS = {
     "c1": "env_game=tictactoe:actor_num_simulation=16:zero_num_parallel_games=8:zero_num_threads=1",
@@ -74,6 +76,7 @@ CONFIGS = {
            "actor_use_gumbel_noise=true:actor_gumbel_sample_size=16:actor_gumbel_sigma_scale_c=0.1:actor_mcts_value_rescale=true:"
            "actor_mcts_reward_discount=0.997:atari_init_q=true:zero_actor_intermediate_sequence_length=200:learner_n_step_return=10:"
            "zero_num_parallel_games=64"),
+    "havannah8x64": "env_game=havannah:env_board_size=8:actor_num_simulation=400:zero_num_parallel_games=256",
 }
 
 
@@ -636,7 +639,7 @@ def godev_playout(board_size, komi, actions, root_prefix, rots, device=0):
 
 
 def envdev_playout(game, board_size, komi, actions, root_prefix, rots, channels, num_actions, device=0):
-    """Device rules engine of `game` ("go", "nogo", "othello", "tictactoe", "gomoku", "hex"): root = actions[:root_prefix] on the host engine, then one device move per
+    """Device rules engine of `game` ("go", "nogo", "othello", "tictactoe", "gomoku", "hex"; "havannah" through envdev_playout_conf): root = actions[:root_prefix] on the host engine, then one device move per
     remaining action.  Returns (feat_bits [steps][channels*W32], legal [steps][num_actions], terminal, eval, player)."""
     L = load()
     P = board_size * board_size
@@ -657,7 +660,7 @@ def envdev_playout(game, board_size, komi, actions, root_prefix, rots, channels,
 
 def envdev_playout_conf(conf, board_size, actions, root_prefix, rots, channels, num_actions, device=0):
     """envdev_playout with the game and its rules from a configuration string, as Env takes it (e.g. "env_game=gomoku:env_gomoku_rule=outer_open",
-    "env_game=hex:env_hex_use_swap_rule=false")."""
+    "env_game=hex:env_hex_use_swap_rule=false").  board_size: the side of the planes (Havannah: 2N - 1 for env_board_size=N)."""
     L = load()
     P = board_size * board_size
     acts = np.ascontiguousarray(actions, np.int32)

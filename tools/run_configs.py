@@ -66,6 +66,8 @@ EXTRA_CONFIGS = {
     "h11x256": ("h11x256", "env_game=hex:actor_num_simulation=400:zero_num_parallel_games=256"),
     # NoGo (a rules variant of Go) on Go's 9x9 network, BASELINE configs[1]'s search and shape: the difference to c2 is the leaf (its legal mask in front of the tower) and no tail help
     "nogo9x64": ("nogo9x64", "env_game=nogo:env_board_size=9:actor_num_simulation=400:zero_num_parallel_games=256"),
+    # Havannah at its default edge size 8 (a 15x15 network, 20 planes; minizero_amd.CONFIGS / DESCS): beside g15x64, the same board and tower with Gomoku's leaf
+    "havannah8x64": ("havannah8x64", None),
 }
 # ... and BASELINE configs[4]'s whole node (512 games) on ONE GPU — NOT the BASELINE shard (64 games per GPU): what the same kernels reach when the pool fills the chip
 EXTRA_CONFIGS["c5x512"] = ("c5", mz.CONFIGS["c5"].replace("zero_num_parallel_games=64", "zero_num_parallel_games=512"))
@@ -85,14 +87,14 @@ EXTRA_DESCS = {
     "h11x256": lambda: mz.make_desc("hex_11x11", 4, 11, 11, 256, 11, 11, 1, 1, 121),
     "nogo9x64": lambda: mz.make_desc("nogo_9x9", 18, 9, 9, 64, 9, 9, 1, 6, 82),
 }
-MOVES.update({"w9x128": 3, "w9x256": 3, "w19x64": 2, "c5x512": 30, "w9x128mz": 10, "l19x128": 1, "l13x96": 2, "w8x256oth": 30, "w3x256ttt": 100, "g15x64": 3, "g15x256": 2, "h11x64": 3, "h11x256": 2, "nogo9x64": 4})
-WARM.update({"w9x128": 1, "w9x256": 1, "w19x64": 1, "c5x512": 14, "l19x128": 1, "l13x96": 1, "w8x256oth": 3, "w3x256ttt": 20, "g15x64": 1, "g15x256": 1, "h11x64": 1, "h11x256": 1, "nogo9x64": 1})
+MOVES.update({"w9x128": 3, "w9x256": 3, "w19x64": 2, "c5x512": 30, "w9x128mz": 10, "l19x128": 1, "l13x96": 2, "w8x256oth": 30, "w3x256ttt": 100, "g15x64": 3, "g15x256": 2, "h11x64": 3, "h11x256": 2, "nogo9x64": 4, "havannah8x64": 3})
+WARM.update({"w9x128": 1, "w9x256": 1, "w19x64": 1, "c5x512": 14, "l19x128": 1, "l13x96": 1, "w8x256oth": 3, "w3x256ttt": 20, "g15x64": 1, "g15x256": 1, "h11x64": 1, "h11x256": 1, "nogo9x64": 1, "havannah8x64": 1})
 KERNEL.update({"w9x128mz": "sim_kernel_mz_wide<9,9,32,144,128>", "w9x128": "sim_kernel_wide<9,9,32,128,2>", "w9x256": "sim_kernel_wide<9,9,32,256,2>", "w19x64": "sim_kernel_wide<19,19,32,64,6>",
                "w8x256oth": "sim_kernel_wide<8,8,16,256,0>", "w3x256ttt": "sim_kernel_wide<3,3,16,256,-1>",
                "l19x128": "conv3x3_band (lock-step worker: per-layer kernels)", "l13x96": "conv3x3_band (lock-step worker: per-layer kernels)",
                "g15x64": "sim_kernel_wide<15,15,16,64,-2>", "g15x256": "conv3x3_band (lock-step worker: per-layer kernels, device rules leaf_kernel<-2>)",
                "h11x64": "sim_kernel_wide<11,11,16,64,-3>", "h11x256": "conv3x3_band (lock-step worker: per-layer kernels, device rules leaf_kernel<-3>)",
-               "nogo9x64": "sim_kernel<9,9,20,64,-4>"})
+               "nogo9x64": "sim_kernel<9,9,20,64,-4>", "havannah8x64": "sim_kernel_wide<15,15,32,64,-5>"})
 
 
 def _by_kernel(s0, s1, launches):

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Stand-alone cost of a device rules body per leaf: plays `moves` moves of 256 games in the lock-step mode (mz_sim_kernel=false), where every cycle is one launch of
-the game's leaf kernel (one wave per leaf: leaf_kernel<-3> for Hex, leaf_kernel<-2> for Gomoku, leaf_kernel<-4> for NoGo — go_dev.hip leaf_kernel<rules argument>), so that a kernel trace of the run holds one duration per cycle, in playing order.
+the game's leaf kernel (one wave per leaf: leaf_kernel<-3> for Hex, leaf_kernel<-2> for Gomoku, leaf_kernel<-4> for NoGo, leaf_kernel<-5> for Havannah — go_dev.hip leaf_kernel<rules argument>), so that a kernel trace of the run holds one duration per cycle, in playing order.
     rocprofv3 --kernel-trace --output-format csv -d DIR -- python tools/time_leaf_kernels.py run hex 100
     python tools/time_leaf_kernels.py report DIR 'leaf_kernel<-3>'
 NoGo: `run nogo 70` — a 9x9 game lasts 70 .. 79 moves, so the last third of the run is the late positions (long chains: the most flood rounds).
+Havannah: `run havannah 60` — edge size 8 on its 15x15 array; late positions have the large groups (the longest floods, and the ring test's complement flood).
 `report` splits the launches of the named kernel into the first, middle and last third of the run (early, middle and late positions) and prints the median and the
 mean duration of each."""
 import csv
@@ -14,7 +15,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-GAMES = {"hex": ("hex_11x11", 11, 4, 121), "gomoku": ("gomoku_15x15", 15, 4, 225), "nogo": ("nogo_9x9", 9, 18, 82)}  # name, board, planes, actions
+GAMES = {"hex": ("hex_11x11", 11, 4, 121), "gomoku": ("gomoku_15x15", 15, 4, 225), "nogo": ("nogo_9x9", 9, 18, 82),
+         "havannah": ("havannah8x8", 15, 20, 225)}  # name, board, planes, actions
 
 
 def run(game, moves, sims=16, games=256):
