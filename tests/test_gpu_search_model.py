@@ -16,23 +16,25 @@ HOST_ENV = ":mz_sim_kernel=false:mz_device_env=false"
 NO_ROUNDS = ":mz_sim_rounds_board=false"
 
 
-def worker_games(mz, oracle, conf, desc_args, w, games, moves, extra=""):
-    """moves + 1 whole searches, one call each (calls that end on a move's boundary keep the simulation kernel and the rounds in play)"""
+def worker_games(mz, oracle, conf, desc_args, w, games, moves, extra="", searches=None):
+    """moves + 1 whole searches (or `searches` of them), one call each (calls that end on a move's boundary keep the simulation kernel and the rounds in
+    play); the finished lines of the run are left in the statistics under "lines" """
     n = T.model_cfg(conf)[0].actor_num_simulation
     d = mz.make_desc(*desc_args[:10], vh=desc_args[10], dv=desc_args[11], type_name=desc_args[12])
     wk = mz.Worker(T.full_conf(conf, games) + extra, d, w)
     wk.command("start")
-    for _ in range(moves + 1):
+    for _ in range(moves + 1 if searches is None else searches):
         assert wk.run_cycles(n + 1) == n + 1
-    st = wk.stats()
-    out = T.games_of(wk.pop_lines(), wk.peek_records(games), games, moves)
+    st = dict(wk.stats())
+    st["lines"] = wk.pop_lines()
+    out = T.games_of(st["lines"], wk.peek_records(games), games, moves)
     wk.close()
     return out, st
 
 
-def run_case(mz, oracle, name, wseed, extra="", games=None):
-    conf, desc_args, _, moves, case_games, vgain = T.CASES[name]
-    got, st = worker_games(mz, oracle, conf, desc_args, T.case_weights(oracle, desc_args, wseed, vgain), games or case_games, moves, extra)
+def run_case(mz, oracle, name, wseed, extra="", games=None, searches=None):
+    conf, desc_args, _, moves, case_games, vgain = T.row(name)
+    got, st = worker_games(mz, oracle, conf, desc_args, T.case_weights(oracle, desc_args, wseed, vgain), games or case_games, moves, extra, searches)
     T.check_against(T.case_model(oracle, name, wseed), got)
     if T.is_atari(conf):
         T.check_atari_pool_shows_something(got)

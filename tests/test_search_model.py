@@ -1,6 +1,8 @@
 """The search model of tests/search_model.py (a third implementation, written from the reference's text) pinned by paper-and-pencil literals, then compared with
 the oracle's search as exact strings: action played, P tag, V tag, resignation, move by move.  The same table of configurations runs against the HIP worker in
-tests/test_gpu_search_model.py.  Nothing here compares with a tolerance."""
+tests/test_gpu_search_model.py.  A second table (GAME_CASES, GAME_NOISY) holds the rows of the games no oracle plays — Gomoku, Hex, NoGo, Havannah — which the
+model plays over tests/rule_envs.py: tests/test_search_model_games.py pins what they show, tests/test_gpu_search_model_games.py runs them against the HIP
+worker.  Nothing here compares with a tolerance."""
 import ctypes as C
 import re
 
@@ -10,6 +12,7 @@ import pytest
 from atari_synth import AtariSynth
 import hand_cases as H
 from helpers import sharpen
+import rule_envs
 import search_model as S
 
 f32 = np.float32
@@ -324,6 +327,81 @@ NOISY = {
 }
 NOISY_GAMES = 8
 
+# ---------------------------------------------------------------------------------------------
+# Gomoku, Hex, NoGo and Havannah: no oracle plays these games, so their rows are the model's alone — over tests/rule_envs.py — and run against the HIP
+# worker in tests/test_gpu_search_model_games.py.  Rows of the form of CASES, in a table of their own: test_model_equals_oracle keeps the rows it has.
+# ---------------------------------------------------------------------------------------------
+def _net(name, planes, side, actions):
+    """1 block x 32 channels, 16 value-hidden channels: the width the simulation-kernel instances of these boards are built for"""
+    return (name, planes, side, side, 32, side, side, 1, 1, actions, 16, 1, "alphazero")
+
+
+def _hex(n, swap=True): return f"env_game=hex:env_board_size={n}" + ("" if swap else ":env_hex_use_swap_rule=false"), _net(f"hex_{n}x{n}", 4, n, n * n)
+def _nogo(n): return f"env_game=nogo:env_board_size={n}", _net(f"nogo_{n}x{n}", 18, n, n * n + 1)
+def _hav(N): return f"env_game=havannah:env_board_size={N}", _net(f"havannah{N}x{N}", 20, 2 * N - 1, (2 * N - 1) ** 2)
+
+
+def _gomoku(n, rule="standard", five=True):
+    conf = f"env_game=gomoku:env_board_size={n}" + ("" if rule == "standard" else f":env_gomoku_rule={rule}") + ("" if five else ":env_gomoku_exactly_five_stones=false")
+    return conf, _net(f"gomoku_{'oo_' if rule == 'outer_open' else ''}{n}x{n}", 4, n, n * n)
+
+
+# the boards with a simulation-kernel instance (32 channels): every other board of these games plays lock-step on the default plan
+SIM_BOARDS = {("hex", 11), ("gomoku", 15), ("nogo", 9), ("havannah", 8), ("havannah", 4)}
+
+
+def has_sim_instance(conf):
+    game, n, _ = rule_envs.parse(full_conf(conf))
+    return (game, n) in SIM_BOARDS
+
+
+PUCT16, GUMBEL16, GUMBEL50 = ":actor_num_simulation=16", _gumbel(16, 16), _gumbel(50, 16)
+NO_RESIGN = ":actor_resign_threshold=-2"
+WHOLE = 400  # more moves than any of these boards has cells: a whole-game row ends where the game does
+
+# name -> (configuration, network, weight seeds, moves, games, gain on the value head).  The weight seeds are chosen on the CPU with the model alone: none
+# raises AmbiguousOrder (seed 1 does on Hex 11x11 under PUCT, on Gomoku 15x15 and on Havannah 8 under Gumbel), and together they show what
+# test_game_rows_show_what_they_are_for asks for.
+GAME_CASES = {}
+# a. the first three moves on every simulation-kernel instance.  Seeds with the swap taken: hex11 PUCT 2 and 3 (the same action three times: Black's
+# stone, White's swap, Black on the cell the swap left empty), hex11 Gumbel 5, hav8 PUCT 3, hav8 Gumbel 4, hav4 1; declined: the others.
+for _b, (_c, _d), _seeds in (("hex11", _hex(11), ((2, 3), (2, 5), (2,))), ("gomoku15", _gomoku(15), ((2,), (2,), (2,))), ("gomoku15oo", _gomoku(15, "outer_open"), ((2,), (3,), None)),
+                             ("nogo9", _nogo(9), ((1,), (2,), (2,))), ("hav8", _hav(8), ((2, 3), (2, 4), (3,))), ("hav4", _hav(4), ((1, 2), (1, 2), None))):
+    for _s, _search, _sd in zip(("puct_n16", "gumbel_n16", "gumbel_n50"), (PUCT16, GUMBEL16, GUMBEL50), _seeds):
+        if _sd:
+            GAME_CASES[f"{_b}_{_s}"] = (_c + _search, _d, _sd, 3, 4, None)
+# b. whole games through the simulation kernel, c. whole games on boards without an instance (lock-step), both without resignation
+for _b, (_c, _d), _seeds in (("hav4", _hav(4), ((2, 3), (2, 6))), ("nogo9", _nogo(9), ((2, 3), (2,))), ("hex11", _hex(11), ((2,), (2,))), ("gomoku15", _gomoku(15), ((2,), (2,))),
+                             ("hav8", _hav(8), ((9,), (8,))),  # (the model alone finishes these in 8 s and 2 s; seed 2 raises AmbiguousOrder on this board)
+                             ("hex4", _hex(4), ((1,), (1,))), ("hex4_noswap", _hex(4, False), ((2,), (1,))), ("hex5", _hex(5), ((4,), (2,))), ("hex5_noswap", _hex(5, False), ((1,), (4,))),
+                             ("nogo4", _nogo(4), ((4,), (2,))), ("gomoku5", _gomoku(5), ((1,), (1,))), ("gomoku6", _gomoku(6), ((1, 3), (2,))),
+                             ("gomoku6_freestyle", _gomoku(6, five=False), ((1,), (1,)))):
+    for _s, _search, _sd in zip(("puct", "gumbel"), (PUCT16, GUMBEL16), _seeds):
+        GAME_CASES[f"{_b}_game_{_s}"] = (_c + _search + NO_RESIGN, _d, _sd, WHOLE, 2, None)
+# d. the default resign threshold (-0.9) with the value head times 32: with seed 3 Black plays one move and White resigns, with seed 2 Black resigns at once
+GAME_CASES["hex11_puct_n16_resign"] = (_hex(11)[0] + PUCT16, _hex(11)[1], (2, 3), 3, 4, 32)
+WHOLE_GAMES = [name for name, c in GAME_CASES.items() if c[3] == WHOLE]
+# whole-game rows whose model takes more than about ten seconds on the CPU (DESIGN.md lists the seconds of every row)
+SLOW_GAMES = ("gomoku15_game_puct",)
+ALL_GAME_CASES = [pytest.param(name, s, marks=[pytest.mark.slow] if name in SLOW_GAMES else []) for name, c in GAME_CASES.items() for s in c[2]]
+
+
+# e. the noisy first move, rows of the form of NOISY.  Havannah 8: the root has 169 children, not 225, and the Dirichlet draws are one per legal child in child
+# order (noisy_model counts the legal actions of the root)
+GAME_NOISY = {
+    "hex11": (_hex(11)[0] + _gumbel(16, 16, True), _hex(11)[1], 2, "gumbel"),
+    "hav8_dirichlet": (_hav(8)[0] + ":actor_num_simulation=24" + DIRICHLET, _hav(8)[1], 2, "dirichlet"),
+}
+
+
+def row(name):
+    return CASES[name] if name in CASES else GAME_CASES[name]
+
+
+def noisy_row(name):
+    return NOISY[name] if name in NOISY else GAME_NOISY[name]
+
+
 MOVE = re.compile(r";([BW])\[(\d+)\]P\[([^\]]*)\]V\[([^\]]*)\]R\[([^\]]*)\]")
 SEED = re.compile(r"SD\[(-?\d+)\]")
 
@@ -363,6 +441,8 @@ def make_env(oracle, conf, env_seed=None):
     if kv["env_game"] == "atari":
         assert env_seed is not None, "an Atari-shaped game is defined by its seed"
         return AtariSynth(env_seed, int(kv["env_atari_episode_length"]))
+    if kv["env_game"] in rule_envs.GAMES:
+        return rule_envs.RuleEnv(full_conf(conf))  # no oracle for these games: the rules models of tests/, configured by the worker's own string
     return OracleEnvAdapter(oracle, ":".join(f"{k}={kv[k]}" for k in ("env_game", "env_board_size") if k in kv))
 
 
@@ -374,13 +454,16 @@ def parse_record(record, moves):
     return out
 
 
-def expected_from_model(oracle, conf, desc_args, wseed, moves, first_noise=None, weights=None, halvings=None, env_seed=None):
-    """what the model plays: ([(action, P, V, R)] of the moves played, resigned at the next search?, finished (terminal or resigned) within `moves`)"""
+def expected_from_model(oracle, conf, desc_args, wseed, moves, first_noise=None, weights=None, halvings=None, env_seed=None, trace=None, env=None):
+    """what the model plays: ([(action, P, V, R)] of the moves played, resigned at the next search?, finished (terminal or resigned) within `moves`);
+    `trace`, a dictionary, receives the environment as the game left it; `env` replaces the environment of the configuration"""
     cfg, muzero, _ = model_cfg(conf)
     od = oracle.make_desc(*desc_args[:10], vh=desc_args[10], dv=desc_args[11], type_name=desc_args[12])
     w = oracle.gen_weights(od, wseed) if weights is None else weights
-    env = make_env(oracle, conf, env_seed)
+    env = make_env(oracle, conf, env_seed) if env is None else env
     got = S.play(cfg, env, NetAdapter(oracle.OracleNet(od, w)), moves, muzero, first_noise)
+    if trace is not None:
+        trace["env"] = env
     resigned = bool(got) and got[-1]["resign"]
     played = [(g["action"], g["P"], g["V"], g["R"]) for g in got if not g["resign"]]
     return played, resigned, resigned or env.terminal()
@@ -425,15 +508,23 @@ _MODEL_CACHE = {}
 def model_of(oracle, name, wseed, env_seed=None):
     """the model's games are computed once and shared (the GPU file asks for the same ones)"""
     if (name, wseed, env_seed) not in _MODEL_CACHE:
-        conf, desc_args, _, moves, _, vgain = CASES[name]
+        conf, desc_args, _, moves, _, vgain = row(name)
+        trace = {}
         _MODEL_CACHE[name, wseed, env_seed] = expected_from_model(oracle, conf, desc_args, wseed, moves, weights=case_weights(oracle, desc_args, wseed, vgain),
-                                                                  env_seed=env_seed)
+                                                                  env_seed=env_seed, trace=trace)
+        _MODEL_CACHE["env", name, wseed, env_seed] = trace["env"]
     return _MODEL_CACHE[name, wseed, env_seed]
+
+
+def model_env_of(oracle, name, wseed):
+    """the environment as the model's game of a row left it (a RuleEnv for the rows of GAME_CASES: its final position and the terminal leaves of its searches)"""
+    model_of(oracle, name, wseed)
+    return _MODEL_CACHE["env", name, wseed, None]
 
 
 def case_model(oracle, name, wseed):
     """what check_against takes for a row: the one game all games of the pool play, or for an Atari-shaped row the game of each seed"""
-    if is_atari(CASES[name][0]):
+    if is_atari(row(name)[0]):
         return lambda sd: model_of(oracle, name, wseed, sd)
     return model_of(oracle, name, wseed)
 
@@ -499,7 +590,7 @@ def noisy_model(oracle, name, g, env_seed=None):
     seed an Atari-shaped game draws there.  The actors expand their first roots in index order in the second cycle, so game g takes draws [g * nc, (g + 1) * nc)
     of the noise stream, Gumbel or Dirichlet; test_noisy_first_move establishes it on the oracle by playing eight different first moves right."""
     if ("noisy", name, g, env_seed) not in _MODEL_CACHE:
-        conf, desc_args, wseed, kind = NOISY[name]
+        conf, desc_args, wseed, kind = noisy_row(name)
         cfg, _, kv = model_cfg(conf)
         assert (kind == "dirichlet") == cfg.actor_use_dirichlet_noise and (kind == "gumbel") == (kv.get("actor_use_gumbel_noise") == "true")
         nc = int(np.sum(make_env(oracle, conf, env_seed).legal()))
@@ -513,7 +604,7 @@ def check_noisy(oracle, name, games):
     assert len(games) == NOISY_GAMES
     first = set()
     for g, game in enumerate(games):
-        assert (game[2] is not None) == is_atari(NOISY[name][0])
+        assert (game[2] is not None) == is_atari(noisy_row(name)[0])
         model = noisy_model(oracle, name, g, game[2])
         check_against(model, [game])
         first.add(model[0][0][0])
