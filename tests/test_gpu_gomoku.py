@@ -233,7 +233,8 @@ def _selfplay_lines(mz, n, type_name, games, sims, cycles, seed, rule="standard"
 @pytest.mark.parametrize("type_name,n,rule", [("alphazero", 15, "outer_open"), ("muzero", 9, "standard")])
 def test_sampler_features_equal_the_host_engine(mz, type_name, n, rule):
     """DataLoader over self-play records: the planes the device replays for a sampled (game, position) are the host engine's planes of that position
-    under one of the 8 rotations; MuZero's unrolled action planes are one-hot (no pass action: past the end of a game a random point, gomoku.cpp:177-185)."""
+    under one of the 8 rotations; MuZero's unrolled action planes are one-hot (no pass action: past the end of a game a random point, gomoku.cpp:177-185).  Any rotation is accepted here; the policy, value and reward targets, the cell the
+    action plane marks and the one rotation they share with the planes are held to tests/loader_model.py in tests/test_gpu_loader_model.py."""
     lines = _selfplay_lines(mz, n, type_name, 6, 8, 9 * (n * n + 5), 21, rule)
     P = n * n
     lconf = f"{_conf(n, rule)}:nn_type_name={type_name}:learner_batch_size=64:learner_muzero_unrolling_step=3:program_seed=5"

@@ -274,7 +274,8 @@ def test_bf16x3_takes_a_path_that_exists(mz):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_sampler_features_equal_the_host_engine(mz):
     """DataLoader over finished self-play records (SZ = the edge size), one hand-written record with the swap among them: the planes the device replays
-    for a sampled (game, position) are the host engine's planes of that position — positions after the swap, with the cell in both planes, included."""
+    for a sampled (game, position) are the host engine's planes of that position — positions after the swap, with the cell in both planes, included.  Havannah has
+    no rotation: the planes are compared at rotation 0 only; the policy and value targets are held to tests/loader_model.py in tests/test_gpu_loader_model.py."""
     N, sims, games = 4, 8, 6
     E, P = 7, 49
     d = _desc(mz, N, 32, 1)

@@ -324,7 +324,8 @@ def test_muzero_and_gumbel_muzero_on_hex(mz):
 def test_sampler_features_equal_the_host_engine(mz, type_name, n):
     """DataLoader over self-play records, one of them with a forced swap (and, on 5x5, possibly P + 1 actions): the planes the device replays for a
     sampled (game, position) are the host engine's planes of that position — positions after the swap included; MuZero's unrolled action planes are
-    one-hot (no pass action: past the end of a game a random cell, hex.cpp:364-371)."""
+    one-hot (no pass action: past the end of a game a random cell, hex.cpp:364-371).  Hex has no rotation: the planes are compared at rotation 0 only; the policy, value and
+    reward targets and the cell the action plane marks are held to tests/loader_model.py in tests/test_gpu_loader_model.py."""
     sims, games = 8, 6
     d = _desc(mz, n, 32, 1, type_name)
     w = mz.generate_weights(d, 21)

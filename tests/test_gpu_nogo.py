@@ -309,7 +309,9 @@ def test_muzero_and_gumbel_muzero_on_nogo(mz):
 @pytest.mark.parametrize("type_name", ["alphazero", "muzero"])
 def test_sampler_features_equal_the_host_engine(mz, type_name):
     """DataLoader over finished self-play records: the planes the device replays for a sampled (game, position) are the host engine's planes of that
-    position under one of the eight rotations; MuZero's unrolled action planes are Go's (one-hot on the board, empty for the action past a game's end that lands on the pass slot)."""
+    position under one of the eight rotations; MuZero's unrolled action planes are Go's (one-hot on the board, empty for the action past a game's end that lands on the pass slot).
+    The policy, value and reward targets, the point the action plane marks and the one rotation they share with the planes are held to tests/loader_model.py in
+    tests/test_gpu_loader_model.py."""
     n, sims, games = 9, 8, 6
     d = _desc(mz, n, 8, 1, type_name)
     w = mz.generate_weights(d, 21)
