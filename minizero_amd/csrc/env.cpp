@@ -1423,27 +1423,28 @@ std::unique_ptr<GameEnv> createGameEnv(const EnvOptions& o)
     const GameKind k = gameFromName(o.game.c_str());
     if (k == kNoDeviceGame) { setError("unknown env_game '%s' (tictactoe | go | nogo | othello | gomoku | hex | havannah | atari)", o.game.c_str()); return nullptr; }
     const int n = o.board_size > 0 ? o.board_size : gameDefaultBoard(k);
+    static_assert(gameMaxBoard(kGo) <= kMaxN && gameMaxBoard(kGomoku) <= kMaxN && gameMaxBoard(kHex) <= kMaxN && networkBoard(kHavannah, gameMaxBoard(kHavannah)) <= kMaxN, "the table's boards fit the engines' arrays");
     switch (k) {
     case kTicTacToe: return std::make_unique<TicTacToe>();
     case kOthello:
-        if (n < 4 || n > 8 || n % 2) { setError("othello board size %d not supported (even, 4..8)", n); return nullptr; }
+        if (n < gameMinBoard(k) || n > gameMaxBoard(k) || n % 2) { setError("othello board size %d not supported (even, %d..%d)", n, gameMinBoard(k), gameMaxBoard(k)); return nullptr; }
         return std::make_unique<Othello>(n);
     case kGo:
-        if (n < 2 || n > kMaxN) { setError("go board size %d not supported (2..19)", n); return nullptr; }
+        if (n < gameMinBoard(k) || n > gameMaxBoard(k)) { setError("go board size %d not supported (%d..%d)", n, gameMinBoard(k), gameMaxBoard(k)); return nullptr; }
         if (o.go_ko_rule != "positional" && o.go_ko_rule != "situational") { setError("env_go_ko_rule '%s' not supported (positional | situational, ref go.cpp:47)", o.go_ko_rule.c_str()); return nullptr; }
         return std::make_unique<Go>(n, o.go_komi, o.go_ko_rule == "situational");
     case kNoGo: // ref nogo.h:12,22: 9x9; the smaller boards are for tests.  env_go_ko_rule is not read: nothing is captured, no position repeats
-        if (n < 2 || n > kNoGoMaxBoard) { setError("nogo board size %d not supported (2..%d)", n, kNoGoMaxBoard); return nullptr; }
+        if (n < gameMinBoard(k) || n > gameMaxBoard(k)) { setError("nogo board size %d not supported (%d..%d)", n, gameMinBoard(k), gameMaxBoard(k)); return nullptr; }
         return std::make_unique<NoGo>(n, o.go_komi);
     case kGomoku: // ref gomoku.h:13,21,44
-        if (n > kMaxN) { setError("gomoku board size %d not supported (up to 19)", n); return nullptr; }
+        if (n > gameMaxBoard(k)) { setError("gomoku board size %d not supported (up to %d)", n, gameMaxBoard(k)); return nullptr; }
         return std::make_unique<Gomoku>(n, o.gomoku_rule == "outer_open", o.gomoku_exactly_five);
     case kHex: // ref hex.h:12,63
-        if (n < 2 || n > kMaxN) { setError("hex board size %d not supported (2..19)", n); return nullptr; }
+        if (n < gameMinBoard(k) || n > gameMaxBoard(k)) { setError("hex board size %d not supported (%d..%d)", n, gameMinBoard(k), gameMaxBoard(k)); return nullptr; }
         return std::make_unique<Hex>(n, o.hex_use_swap_rule);
     case kHavannah: // ref havannah.h:41,74: edge size 8; the array of edge size 10 is 19 x 19, the widest the bitboards hold
-        if (n < gameMinBoard(kHavannah)) { setError("havannah board size %d not supported: the edge size is at least %d (ref havannah.h:41)", n, gameMinBoard(kHavannah)); return nullptr; }
-        if (n > kHavannahMaxBoard) { setError("havannah board size %d not supported: edge sizes up to %d (a %dx%d array) have an engine", n, kHavannahMaxBoard, networkBoard(kHavannah, kHavannahMaxBoard), networkBoard(kHavannah, kHavannahMaxBoard)); return nullptr; }
+        if (n < gameMinBoard(k)) { setError("havannah board size %d not supported: the edge size is at least %d (ref havannah.h:41)", n, gameMinBoard(k)); return nullptr; }
+        if (n > gameMaxBoard(k)) { setError("havannah board size %d not supported: edge sizes up to %d (a %dx%d array) have an engine", n, gameMaxBoard(k), networkBoard(k, gameMaxBoard(k)), networkBoard(k, gameMaxBoard(k))); return nullptr; }
         return std::make_unique<Havannah>(n, o.havannah_use_swap_rule);
     default: return nullptr;
     }

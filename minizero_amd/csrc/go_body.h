@@ -511,6 +511,98 @@ __device__ __forceinline__ void goPlanesPart(const GoDevView& v, int max_depth, 
     }
 }
 
+// ---- The frame of the two-bitboard leaf bodies (every game but Go).  A slot holds two bitboards of v.W words and two `meta` words; a leaf is its parent's slot
+// plus the last action of the path.  A body is: leafPlace, loadSlot, the game's rules (at depth >= 1: the move, then storeSlot), its legal mask, its planes
+// (storePlaneWord), storeLeafResult.  The boards stay in register arrays of a compile-time word count: every word index below is an unrolled constant.
+struct LeafPlace {
+    int len, depth;            // nodes on the path; the leaf's depth below the root (0: the leaf is the root)
+    int t, m;                  // the player to move at the leaf; the player who moved into it (3 - t; depth >= 1)
+    int src;                   // the slot the leaf's position starts from: its parent's (the root's slot 0 at depth 0)
+    size_t sb;                 // the game's first slot
+    const int* path;           // the path's nodes
+    const int* pact;           // the action into each of them
+    const int* hs;             // a node's slot
+    const GoRootSnapshot& S;
+    __device__ __forceinline__ int action() const { return pact[len - 1]; } // the action into the leaf (depth >= 1; read where it is used: not at a root)
+};
+__device__ __forceinline__ LeafPlace leafPlace(const GoDevView& v, const PoolView& pv, int g)
+{
+    const int len = pv.path_len[g], depth = len - 1;
+    const int* path = pv.path + size_t(g) * pv.max_depth;
+    const int* hs = pv.hslot + size_t(g) * pv.cap;
+    const GoRootSnapshot& S = v.snap[g];
+    const int t = (depth & 1) ? 3 - S.turn : S.turn;
+    return {len, depth, t, 3 - t, depth == 0 ? 0 : hs[path[len - 2]], size_t(g) * v.slots, path, pv.path_action + size_t(g) * pv.max_depth, hs, S};
+}
+
+__device__ __forceinline__ unsigned long long hexUniform(unsigned long long x) // a value every lane holds, moved to scalar registers
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
+    return (static_cast<unsigned long long>(hi) << 32) | lo;
+}
+
+// slot L.src: the boards' words past v.W are 0.  UNIFORM: the words go to scalar registers
+template <int NW, bool UNIFORM>
+__device__ __forceinline__ void loadSlot(const GoDevView& v, const LeafPlace& L, unsigned long long (&b0)[NW], unsigned long long (&b1)[NW], int& meta0, int& meta1)
+{
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        const bool in = NW == 1 || i < v.W; // (a board has a word)
+        const unsigned long long x0 = in ? v.stones[((L.sb + L.src) * 2 + 0) * v.W + i] : 0ull, x1 = in ? v.stones[((L.sb + L.src) * 2 + 1) * v.W + i] : 0ull;
+        b0[i] = UNIFORM ? hexUniform(x0) : x0;
+        b1[i] = UNIFORM ? hexUniform(x1) : x1;
+    }
+    meta0 = v.meta[(L.sb + L.src) * 2];
+    meta1 = v.meta[(L.sb + L.src) * 2 + 1];
+}
+
+// the leaf's position into its own slot (lane 0 calls it).  META = false: the game keeps nothing in `meta`
+template <int NW, bool META = true>
+__device__ __forceinline__ void storeSlot(const GoDevView& v, const LeafPlace& L, int slot, const unsigned long long (&b0)[NW], const unsigned long long (&b1)[NW], int meta0, int meta1)
+{
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        if (NW == 1 || i < v.W) {
+            v.stones[((L.sb + slot) * 2 + 0) * v.W + i] = b0[i];
+            v.stones[((L.sb + slot) * 2 + 1) * v.W + i] = b1[i];
+        }
+    }
+    if (META) {
+        v.meta[(L.sb + slot) * 2] = meta0;
+        v.meta[(L.sb + slot) * 2 + 1] = meta1;
+    }
+}
+
+// word i of a plane per lane: lane ch < planes holds plane ch's 64 bits and writes them as the plane's halves 2i and 2i + 1 (the last word may have one half only).
+// `out` = leafPlanes(v, g, planes), taken once by the body: inside the loop over the words every word would compute it again
+__device__ __forceinline__ uint32_t* leafPlanes(const GoDevView& v, int g, int planes) { return v.feat + size_t(g) * planes * v.W32; }
+__device__ __forceinline__ void storePlaneWord(const GoDevView& v, uint32_t* out, int lane, int planes, int i, unsigned long long word)
+{
+    if (lane < planes) {
+        if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(word); }
+        if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(word >> 32); }
+    }
+}
+// word i of the four planes of Othello, TicTacToe, Gomoku and Hex: own, opponent, black to move, white to move (`ones`: the points of the word on the board)
+__device__ __forceinline__ void storeToMovePlanes(const GoDevView& v, uint32_t* out, int lane, int t, int i, unsigned long long own, unsigned long long opp, unsigned long long ones)
+{
+    unsigned long long word = 0;
+    if (lane == 0) { word = own; }
+    if (lane == 1) { word = opp; }
+    if (lane == 2) { word = t == 1 ? ones : 0; }
+    if (lane == 3) { word = t == 2 ? ones : 0; }
+    storePlaneWord(v, out, lane, 4, i, word);
+}
+
+// what the search reads of the leaf (lane 0 calls it)
+__device__ __forceinline__ void storeLeafResult(const GoDevView& v, int g, int t, bool terminal, float eval)
+{
+    v.leaf_player[g] = t;
+    v.terminal[g] = terminal ? 1 : 0;
+    v.eval[g] = eval;
+}
+__device__ __forceinline__ float winnerEval(int winner) { return winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); } // black's point of view
+
 // ---- Othello (ref environment/othello/othello.cpp:61-140,195-255): the whole position is two 64-bit boards, so every lane carries
 // it and the rules are scalar bit arithmetic; only the rotated feature planes are built with ballots.  Slot layout: the `stones`
 // words of the Go slab hold the two boards, `meta` (moves played, trailing passes).
@@ -543,7 +635,7 @@ __device__ __forceinline__ unsigned long long othMoves(const OthMasks& k, unsign
 
 __device__ __forceinline__ void othLeafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane)
 {
-    const int P = v.P, n = v.n, MD = pv.max_depth;
+    const int P = v.P, n = v.n;
     OthMasks k;
     k.n = n;
     k.full = P == 64 ? ~0ull : ((1ull << P) - 1);
@@ -553,27 +645,20 @@ __device__ __forceinline__ void othLeafBody(const GoDevView& v, const PoolView& 
         k.not_left |= row & ~(1ull << (y * n));
         k.not_right |= row & ~(1ull << (y * n + n - 1));
     }
-    const int len = pv.path_len[g];
-    const int* path = pv.path + size_t(g) * MD;
-    const int* pact = pv.path_action + size_t(g) * MD;
-    const int depth = len - 1;
-    const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn;
-    const size_t sb = size_t(g) * v.slots;
-    const int* hs = pv.hslot + size_t(g) * pv.cap;
-    const int src = depth == 0 ? 0 : hs[path[len - 2]];
-    unsigned long long s[2] = {v.stones[((sb + src) * 2 + 0) * v.W], v.stones[((sb + src) * 2 + 1) * v.W]};
-    int nmoves = v.meta[(sb + src) * 2], passes = v.meta[(sb + src) * 2 + 1];
-    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
-    if (depth >= 1) {
-        const int a = pact[len - 1], m = 3 - t;
+    const LeafPlace L = leafPlace(v, pv, g);
+    const int t = L.t;
+    unsigned long long b[2][1]; // [black, white]
+    int nmoves, passes;
+    loadSlot<1, false>(v, L, b[0], b[1], nmoves, passes);
+    if (L.depth >= 1) {
+        const int a = L.action();
         ++nmoves;
         if (a >= P) {
             passes = passes + 1 > 2 ? 2 : passes + 1;
         } else {
             passes = 0;
-            unsigned long long& me = s[m - 1];
-            unsigned long long& op = s[2 - m];
+            unsigned long long& me = b[L.m - 1][0];
+            unsigned long long& op = b[2 - L.m][0];
             const unsigned long long placed = 1ull << a;
             unsigned long long flip = 0;
 #pragma unroll
@@ -585,13 +670,9 @@ __device__ __forceinline__ void othLeafBody(const GoDevView& v, const PoolView& 
             me |= placed | flip;
             op &= ~flip;
         }
-        if (lane == 0) {
-            v.stones[((sb + slot) * 2 + 0) * v.W] = s[0];
-            v.stones[((sb + slot) * 2 + 1) * v.W] = s[1];
-            v.meta[(sb + slot) * 2] = nmoves;
-            v.meta[(sb + slot) * 2 + 1] = passes;
-        }
+        if (lane == 0) { storeSlot<1>(v, L, slot, b[0], b[1], nmoves, passes); }
     }
+    const unsigned long long s[2] = {b[0][0], b[1][0]};
     const bool terminal = passes >= 2; // ref othello.cpp: two consecutive passes
     const unsigned long long mv = terminal ? 0ull : othMoves(k, s[t - 1], s[2 - t]);
     if (lane == 0) { // legal mask: the moves, or pass when there is none (ref othello.cpp:195-201)
@@ -604,55 +685,33 @@ __device__ __forceinline__ void othLeafBody(const GoDevView& v, const PoolView& 
         const uint16_t* map = v.inv + size_t(rot) * P;
         const int q = lane < P ? map[lane] : 0;
         const unsigned long long own = __ballot(lane < P && ((s[t - 1] >> q) & 1)), opp = __ballot(lane < P && ((s[2 - t] >> q) & 1));
-        const unsigned long long ones = __ballot(lane < P);
-        unsigned long long mine = 0;
-        if (lane == 0) { mine = own; }
-        if (lane == 1) { mine = opp; }
-        if (lane == 2) { mine = t == 1 ? ones : 0; }
-        if (lane == 3) { mine = t == 2 ? ones : 0; }
-        uint32_t* out = v.feat + size_t(g) * 4 * v.W32;
-        if (lane < 4) {
-            out[lane * v.W32] = static_cast<uint32_t>(mine);
-            if (v.W32 > 1) { out[lane * v.W32 + 1] = static_cast<uint32_t>(mine >> 32); }
-        }
+        storeToMovePlanes(v, leafPlanes(v, g, 4), lane, t, 0, own, opp, __ballot(lane < P));
     }
     float eval = 0.0f;
     if (terminal) { // ref othello.cpp:211-236: a winner only once neither side can move
         if (othMoves(k, s[0], s[1]) == 0 && othMoves(k, s[1], s[0]) == 0) {
-            const int b = __popcll(s[0]), w = __popcll(s[1]);
-            eval = b > w ? 1.0f : (b < w ? -1.0f : 0.0f);
+            const int nb = __popcll(s[0]), nw = __popcll(s[1]);
+            eval = nb > nw ? 1.0f : (nb < nw ? -1.0f : 0.0f);
         }
     }
-    if (lane == 0) {
-        v.leaf_player[g] = t;
-        v.terminal[g] = terminal ? 1 : 0;
-        v.eval[g] = eval;
-    }
+    if (lane == 0) { storeLeafResult(v, g, t, terminal, eval); }
 }
 
 // ---- TicTacToe (ref environment/tictactoe/tictactoe.cpp:19-97): two 9-bit boards per slot; the planes are Othello's (own, opponent,
 // black to move, white to move); no pass, terminal = a complete line or a full board.
 __device__ __forceinline__ void tttLeafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane)
 {
-    const int P = 9, MD = pv.max_depth;
-    const int len = pv.path_len[g];
-    const int* path = pv.path + size_t(g) * MD;
-    const int* pact = pv.path_action + size_t(g) * MD;
-    const int depth = len - 1;
-    const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn;
-    const size_t sb = size_t(g) * v.slots;
-    const int* hs = pv.hslot + size_t(g) * pv.cap;
-    const int src = depth == 0 ? 0 : hs[path[len - 2]];
-    unsigned s[2] = {static_cast<unsigned>(v.stones[((sb + src) * 2 + 0) * v.W]), static_cast<unsigned>(v.stones[((sb + src) * 2 + 1) * v.W])};
-    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
-    if (depth >= 1) {
-        s[2 - t] |= 1u << pact[len - 1]; // moved by the other player
-        if (lane == 0) {
-            v.stones[((sb + slot) * 2 + 0) * v.W] = s[0];
-            v.stones[((sb + slot) * 2 + 1) * v.W] = s[1];
-        }
+    const int P = 9;
+    const LeafPlace L = leafPlace(v, pv, g);
+    const int t = L.t;
+    unsigned long long b[2][1]; // [black, white]
+    int unused0, unused1;       // (nothing is kept in `meta`)
+    loadSlot<1, false>(v, L, b[0], b[1], unused0, unused1);
+    if (L.depth >= 1) {
+        b[L.m - 1][0] |= 1ull << L.action();
+        if (lane == 0) { storeSlot<1, false>(v, L, slot, b[0], b[1], 0, 0); }
     }
+    const unsigned s[2] = {static_cast<unsigned>(b[0][0]), static_cast<unsigned>(b[1][0])};
     int winner = 0;
     {
         const unsigned lines[8] = {0007, 0070, 0700, 0111, 0222, 0444, 0421, 0124};
@@ -667,19 +726,9 @@ __device__ __forceinline__ void tttLeafBody(const GoDevView& v, const PoolView& 
     {
         const uint16_t* map = v.inv + size_t(rot) * P;
         const int q = lane < P ? map[lane] : 0;
-        const unsigned own = static_cast<unsigned>(__ballot(lane < P && ((s[t - 1] >> q) & 1)));
-        const unsigned opp = static_cast<unsigned>(__ballot(lane < P && ((s[2 - t] >> q) & 1)));
-        uint32_t* out = v.feat + size_t(g) * 4 * v.W32;
-        if (lane == 0) { out[0] = own; }
-        if (lane == 1) { out[v.W32] = opp; }
-        if (lane == 2) { out[2 * v.W32] = t == 1 ? 0777u : 0u; }
-        if (lane == 3) { out[3 * v.W32] = t == 2 ? 0777u : 0u; }
+        storeToMovePlanes(v, leafPlanes(v, g, 4), lane, t, 0, __ballot(lane < P && ((s[t - 1] >> q) & 1)), __ballot(lane < P && ((s[2 - t] >> q) & 1)), 0777ull);
     }
-    if (lane == 0) {
-        v.leaf_player[g] = t;
-        v.terminal[g] = terminal ? 1 : 0;
-        v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f);
-    }
+    if (lane == 0) { storeLeafResult(v, g, t, terminal, winnerEval(winner)); }
 }
 
 // ---- Gomoku (ref environment/gomoku/gomoku.cpp:23-105,140-162): two bitboards of up to kGoMaxW words per slot, `meta` (moves played, the winner).  The
@@ -697,26 +746,14 @@ __device__ __forceinline__ bool gmkStone(const unsigned long long (&b)[kGoMaxW],
 
 __device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane)
 {
-    const int P = v.P, n = v.n, W = v.W, MD = pv.max_depth;
-    const int len = pv.path_len[g];
-    const int* path = pv.path + size_t(g) * MD;
-    const int* pact = pv.path_action + size_t(g) * MD;
-    const int depth = len - 1;
-    const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn, rule = S.ruleBits();
-    const size_t sb = size_t(g) * v.slots;
-    const int* hs = pv.hslot + size_t(g) * pv.cap;
-    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    const int P = v.P, n = v.n, W = v.W;
+    const LeafPlace L = leafPlace(v, pv, g);
+    const int t = L.t, rule = L.S.ruleBits();
     unsigned long long blk[kGoMaxW], wht[kGoMaxW];
-#pragma unroll
-    for (int i = 0; i < kGoMaxW; ++i) {
-        blk[i] = i < W ? v.stones[((sb + src) * 2 + 0) * W + i] : 0ull;
-        wht[i] = i < W ? v.stones[((sb + src) * 2 + 1) * W + i] : 0ull;
-    }
-    int nmoves = v.meta[(sb + src) * 2], winner = v.meta[(sb + src) * 2 + 1];
-    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
-    if (depth >= 1) {
-        const int a = pact[len - 1], m = 3 - t; // moved by the other player
+    int nmoves, winner;
+    loadSlot<kGoMaxW, false>(v, L, blk, wht, nmoves, winner);
+    if (L.depth >= 1) {
+        const int a = L.action(), m = L.m;
         ++nmoves;
         unsigned long long mine[kGoMaxW];
 #pragma unroll
@@ -734,17 +771,7 @@ __device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& 
         }
         const bool five = (rule & kGmkExactlyFive) ? run == 5 : run >= 5;
         winner = __ballot(lane < 4 && five) != 0 ? m : 0; // ref gomoku.cpp:29: the winner is replaced on every move
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < kGoMaxW; ++i) {
-                if (i < W) {
-                    v.stones[((sb + slot) * 2 + 0) * W + i] = blk[i];
-                    v.stones[((sb + slot) * 2 + 1) * W + i] = wht[i];
-                }
-            }
-            v.meta[(sb + slot) * 2] = nmoves;
-            v.meta[(sb + slot) * 2 + 1] = winner;
-        }
+        if (lane == 0) { storeSlot<kGoMaxW>(v, L, slot, blk, wht, nmoves, winner); }
     }
     int stones = 0;
 #pragma unroll
@@ -752,7 +779,7 @@ __device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& 
     const bool terminal = winner != 0 || stones == P; // ref gomoku.cpp:60-63
     const bool first_oo = (rule & kGmkOuterOpen) && nmoves == 0;
     const uint16_t* map = v.inv + size_t(rot) * P;
-    uint32_t* out = v.feat + size_t(g) * 4 * v.W32;
+    uint32_t* out = leafPlanes(v, g, 4);
 #pragma unroll
     for (int i = 0; i < kGoMaxW; ++i) {
         if (i >= W) { continue; }
@@ -771,22 +798,9 @@ __device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& 
         // planes (ref gomoku.cpp:75-98): own, opponent, black to move, white to move — under the cycle's rotation
         const int q = p < P ? map[p] : 0;
         const bool b = gmkStone(blk, q), w = gmkStone(wht, q);
-        const unsigned long long own = __ballot(p < P && (t == 1 ? b : w)), opp = __ballot(p < P && (t == 1 ? w : b)), ones = __ballot(p < P);
-        unsigned long long word = 0;
-        if (lane == 0) { word = own; }
-        if (lane == 1) { word = opp; }
-        if (lane == 2) { word = t == 1 ? ones : 0; }
-        if (lane == 3) { word = t == 2 ? ones : 0; }
-        if (lane < 4) {
-            if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(word); }
-            if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(word >> 32); }
-        }
+        storeToMovePlanes(v, out, lane, t, i, __ballot(p < P && (t == 1 ? b : w)), __ballot(p < P && (t == 1 ? w : b)), __ballot(p < P));
     }
-    if (lane == 0) {
-        v.leaf_player[g] = t;
-        v.terminal[g] = terminal ? 1 : 0;
-        v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); // ref gomoku.cpp:65-73
-    }
+    if (lane == 0) { storeLeafResult(v, g, t, terminal, winnerEval(winner)); } // ref gomoku.cpp:65-73
 }
 
 // ---- Hex (ref environment/hex/hex.cpp:22-141,307-362): the slot layout of Gomoku — two bitboards of up to kGoMaxW words, `meta` (actions played, the winner).
@@ -794,12 +808,6 @@ __device__ __forceinline__ void gmkLeafBody(const GoDevView& v, const PoolView& 
 // position is wave-uniform, so the win test is a wave-uniform flood: the set reached from the new stone is dilated by the six shifts (multi-word shifts with
 // column masks, every word index static), masked with the mover's stones, until a round adds nothing; then it is tested against the mover's two edge masks.
 // NW = the words the board needs (2 up to 11x11, else kGoMaxW), so that the default board does not shift four empty words.
-__device__ __forceinline__ unsigned long long hexUniform(unsigned long long x) // a value every lane holds, moved to scalar registers
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x)), hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
-    return (static_cast<unsigned long long>(hi) << 32) | lo;
-}
-
 // bit p of a board: the word is gathered with masked ORs (not gmkWord's select chain, which the compiler turns into an indexed load from a scratch copy)
 __device__ __forceinline__ bool hexStone(const unsigned long long (&b)[kGoMaxW], int p)
 {
@@ -855,26 +863,14 @@ __device__ __forceinline__ bool hexConnects(const unsigned long long (&stones)[k
 
 __device__ __forceinline__ void hexLeafBody(const GoDevView& v, const PoolView& pv, int /*rot: Hex has no symmetries, hex.cpp:128*/, int slot, int g, int lane)
 {
-    const int P = v.P, n = v.n, W = v.W, MD = pv.max_depth;
-    const int len = pv.path_len[g];
-    const int* path = pv.path + size_t(g) * MD;
-    const int* pact = pv.path_action + size_t(g) * MD;
-    const int depth = len - 1;
-    const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn, rule = S.ruleBits();
-    const size_t sb = size_t(g) * v.slots;
-    const int* hs = pv.hslot + size_t(g) * pv.cap;
-    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    const int P = v.P, n = v.n, W = v.W;
+    const LeafPlace L = leafPlace(v, pv, g);
+    const int t = L.t, rule = L.S.ruleBits();
     unsigned long long blk[kGoMaxW], wht[kGoMaxW];
-#pragma unroll
-    for (int i = 0; i < kGoMaxW; ++i) {
-        blk[i] = i < W ? v.stones[((sb + src) * 2 + 0) * W + i] : 0ull;
-        wht[i] = i < W ? v.stones[((sb + src) * 2 + 1) * W + i] : 0ull;
-    }
-    int nact = v.meta[(sb + src) * 2], winner = v.meta[(sb + src) * 2 + 1];
-    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
-    if (depth >= 1) {
-        const int a = pact[len - 1], m = 3 - t; // moved by the other player
+    int nact, winner;
+    loadSlot<kGoMaxW, false>(v, L, blk, wht, nact, winner);
+    if (L.depth >= 1) {
+        const int a = L.action(), m = L.m;
         // the swap (hex.cpp:28-47), recognised from the position alone: rule on, one action played, the chosen cell occupied — the stone there goes, the mover's
         // lands on its reflection (row, col) -> (n - 1 - col, n - 1 - row)
         const bool swap = (rule & kHexSwap) && nact == 1 && (hexStone(blk, a) || hexStone(wht, a));
@@ -894,21 +890,11 @@ __device__ __forceinline__ void hexLeafBody(const GoDevView& v, const PoolView& 
             const bool won = W <= 2 ? hexConnects<2>(mine, p, m, n, P, lane) : hexConnects<kGoMaxW>(mine, p, m, n, P, lane);
             if (won) { winner = m; }
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < kGoMaxW; ++i) {
-                if (i < W) {
-                    v.stones[((sb + slot) * 2 + 0) * W + i] = blk[i];
-                    v.stones[((sb + slot) * 2 + 1) * W + i] = wht[i];
-                }
-            }
-            v.meta[(sb + slot) * 2] = nact;
-            v.meta[(sb + slot) * 2 + 1] = winner;
-        }
+        if (lane == 0) { storeSlot<kGoMaxW>(v, L, slot, blk, wht, nact, winner); }
     }
     const bool terminal = winner != 0; // ref hex.cpp:101-104: there is no draw
     const bool any_cell = (rule & kHexSwap) && nact == 1; // hex.cpp:97: every cell is legal on the second action
-    uint32_t* out = v.feat + size_t(g) * 4 * v.W32;
+    uint32_t* out = leafPlanes(v, g, 4);
 #pragma unroll
     for (int i = 0; i < kGoMaxW; ++i) {
         if (i >= W) { continue; }
@@ -917,22 +903,9 @@ __device__ __forceinline__ void hexLeafBody(const GoDevView& v, const PoolView& 
         const unsigned long long lw = __ballot(p < P && (any_cell || !(b || w)));
         if (lane == 0) { v.legal[size_t(g) * v.LW + i] = lw; }
         // planes (ref hex.cpp:118-141): own, opponent, black to move, white to move
-        const unsigned long long own = __ballot(p < P && (t == 1 ? b : w)), opp = __ballot(p < P && (t == 1 ? w : b)), ones = __ballot(p < P);
-        unsigned long long word = 0;
-        if (lane == 0) { word = own; }
-        if (lane == 1) { word = opp; }
-        if (lane == 2) { word = t == 1 ? ones : 0; }
-        if (lane == 3) { word = t == 2 ? ones : 0; }
-        if (lane < 4) {
-            if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(word); }
-            if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(word >> 32); }
-        }
+        storeToMovePlanes(v, out, lane, t, i, __ballot(p < P && (t == 1 ? b : w)), __ballot(p < P && (t == 1 ? w : b)), __ballot(p < P));
     }
-    if (lane == 0) {
-        v.leaf_player[g] = t;
-        v.terminal[g] = terminal ? 1 : 0;
-        v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); // ref hex.cpp:106-116
-    }
+    if (lane == 0) { storeLeafResult(v, g, t, terminal, winnerEval(winner)); } // ref hex.cpp:106-116
 }
 
 // ---- NoGo (ref nogo.h:25-76; a rules variant of Go, game_kind.h kNoGo): boards up to 9x9, so a position is two bitboards of two words, and the slot layout is
@@ -959,26 +932,17 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src)
 
 __device__ __forceinline__ void nogoLeafBody(const GoDevView& v, const PoolView& pv, int rot, int slot, int g, int lane)
 {
-    const int P = v.P, n = v.n, W = v.W, MD = pv.max_depth; // W <= 2 (GoDevice::init: boards up to kNoGoMaxBoard)
-    const int len = pv.path_len[g];
-    const int* path = pv.path + size_t(g) * MD;
-    const int* pact = pv.path_action + size_t(g) * MD;
-    const int depth = len - 1;
-    const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn, root_hist_len = S.hist_len;
-    const size_t sb = size_t(g) * v.slots;
-    const int* hs = pv.hslot + size_t(g) * pv.cap;
-    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    const int P = v.P, n = v.n, W = v.W; // W <= 2 (GoDevice::init: boards up to gameMaxBoard(kNoGo))
+    const LeafPlace L = leafPlace(v, pv, g);
+    const GoRootSnapshot& S = L.S;
+    const int t = L.t, depth = L.depth, len = L.len, root_hist_len = S.hist_len;
+    const size_t sb = L.sb;
+    const int *path = L.path, *hs = L.hs;
     unsigned long long st[2][2]; // [colour][word]
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        st[0][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 0) * W + i]) : 0ull;
-        st[1][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 1) * W + i]) : 0ull;
-    }
-    int nmoves = v.meta[(sb + src) * 2];
-    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
+    int nmoves, unused;          // (the second `meta` word is written 0 and never read)
+    loadSlot<2, true>(v, L, st[0], st[1], nmoves, unused);
     if (depth >= 1) { // GoEnv::act of a move that captures nothing (ref go.cpp:132-190): the stone is placed
-        const int a = pact[len - 1], m = 3 - t; // moved by the other player
+        const int a = L.action(), m = L.m;
         ++nmoves;
 #pragma unroll
         for (int i = 0; i < 2; ++i) { // (selects, never a dynamic register index)
@@ -986,17 +950,7 @@ __device__ __forceinline__ void nogoLeafBody(const GoDevView& v, const PoolView&
             st[0][i] |= m == 1 ? bit : 0ull;
             st[1][i] |= m == 2 ? bit : 0ull;
         }
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if (i < W) {
-                    v.stones[((sb + slot) * 2 + 0) * W + i] = st[0][i];
-                    v.stones[((sb + slot) * 2 + 1) * W + i] = st[1][i];
-                }
-            }
-            v.meta[(sb + slot) * 2] = nmoves;
-            v.meta[(sb + slot) * 2 + 1] = 0;
-        }
+        if (lane == 0) { storeSlot<2>(v, L, slot, st[0], st[1], nmoves, 0); }
     }
     NoGoMasks k;
     k.n = n;
@@ -1053,7 +1007,7 @@ __device__ __forceinline__ void nogoLeafBody(const GoDevView& v, const PoolView&
             }
         }
         const uint16_t* map = v.inv + size_t(rot) * P;
-        uint32_t* out = v.feat + size_t(g) * 18 * v.W32;
+        uint32_t* out = leafPlanes(v, g, 18);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if (i >= W) { continue; }
@@ -1068,17 +1022,10 @@ __device__ __forceinline__ void nogoLeafBody(const GoDevView& v, const PoolView&
             }
             if (lane == 16) { mine = t == 1 ? k.full[i] : 0; }
             if (lane == 17) { mine = t == 2 ? k.full[i] : 0; }
-            if (lane < 18) {
-                if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(mine); }
-                if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(mine >> 32); }
-            }
+            storePlaneWord(v, out, lane, 18, i, mine);
         }
     }
-    if (lane == 0) {
-        v.leaf_player[g] = t;
-        v.terminal[g] = terminal ? 1 : 0;
-        v.eval[g] = t == 2 ? 1.0f : -1.0f; // ref nogo.h:68-76: the player not to move
-    }
+    if (lane == 0) { storeLeafResult(v, g, t, terminal, t == 2 ? 1.0f : -1.0f); } // ref nogo.h:68-76: the player not to move
 }
 
 // ---- Havannah (ref havannah.cpp:38-231,272-496; a game past the rows, game_kind.h kHavannah): the view's board is the E x E array (E = 2N - 1 for edge
@@ -1190,25 +1137,18 @@ __device__ __forceinline__ bool havWins(const HavGeo<NW>& k, const unsigned long
 template <int NW>
 __device__ __forceinline__ void havLeafBodyT(const GoDevView& v, const PoolView& pv, int slot, int g, int lane)
 {
-    const int P = v.P, E = v.n, W = v.W, MD = pv.max_depth; // W <= NW
-    const int len = pv.path_len[g];
-    const int* path = pv.path + size_t(g) * MD;
-    const int* pact = pv.path_action + size_t(g) * MD;
-    const int depth = len - 1;
-    const GoRootSnapshot& S = v.snap[g];
-    const int root_turn = S.turn, root_hist_len = S.hist_len;
+    const int P = v.P, E = v.n, W = v.W; // W <= NW
+    const LeafPlace L = leafPlace(v, pv, g);
+    const GoRootSnapshot& S = L.S;
+    const int t = L.t, depth = L.depth, len = L.len, root_hist_len = S.hist_len;
     const bool rule = (S.hash & kHavSwap) != 0;
-    const size_t sb = size_t(g) * v.slots;
-    const int* hs = pv.hslot + size_t(g) * pv.cap;
-    const int src = depth == 0 ? 0 : hs[path[len - 2]];
+    const size_t sb = L.sb;
+    const int *path = L.path, *hs = L.hs;
     unsigned long long fb[2][NW]; // [black, white][word]: the feature bitboards
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        fb[0][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 0) * W + i]) : 0ull;
-        fb[1][i] = i < W ? hexUniform(v.stones[((sb + src) * 2 + 1) * W + i]) : 0ull;
-    }
-    int nact = __builtin_amdgcn_readfirstlane(v.meta[(sb + src) * 2]), winner = __builtin_amdgcn_readfirstlane(v.meta[(sb + src) * 2 + 1]);
-    const int t = (depth & 1) ? 3 - root_turn : root_turn; // the player to move at the leaf
+    int nact, winner;
+    loadSlot<NW, true>(v, L, fb[0], fb[1], nact, winner);
+    nact = __builtin_amdgcn_readfirstlane(nact);
+    winner = __builtin_amdgcn_readfirstlane(winner);
     HavGeo<NW> k;
     k.E = E;
     k.N = (E + 1) / 2;
@@ -1225,7 +1165,7 @@ __device__ __forceinline__ void havLeafBodyT(const GoDevView& v, const PoolView&
         k.board[i] = __ballot(in && r + c >= k.N - 1 && r + c <= 3 * k.N - 3); // havannah.cpp:321-327
     }
     if (depth >= 1) { // havannah.cpp:107-151
-        const int a = __builtin_amdgcn_readfirstlane(pact[len - 1]), m = 3 - t; // moved by the other player
+        const int a = __builtin_amdgcn_readfirstlane(L.action()), m = L.m;
         ++nact;
         unsigned long long mine[NW];
 #pragma unroll
@@ -1236,17 +1176,7 @@ __device__ __forceinline__ void havLeafBodyT(const GoDevView& v, const PoolView&
             mine[i] = m == 1 ? fb[0][i] & ~fb[1][i] : fb[1][i];
         }
         if (winner == 0 && havWins<NW>(k, mine, a)) { winner = m; } // a winner never goes away (and the floods are skipped)
-        if (lane == 0) {
-#pragma unroll
-            for (int i = 0; i < NW; ++i) {
-                if (i < W) {
-                    v.stones[((sb + slot) * 2 + 0) * W + i] = fb[0][i];
-                    v.stones[((sb + slot) * 2 + 1) * W + i] = fb[1][i];
-                }
-            }
-            v.meta[(sb + slot) * 2] = nact;
-            v.meta[(sb + slot) * 2 + 1] = winner;
-        }
+        if (lane == 0) { storeSlot<NW>(v, L, slot, fb[0], fb[1], nact, winner); }
     }
     int stones = 0, cells = 0;
 #pragma unroll
@@ -1257,7 +1187,7 @@ __device__ __forceinline__ void havLeafBodyT(const GoDevView& v, const PoolView&
     // the identity, so a plane's word is the history word itself), lanes 16 .. 19 the board, swappable, black to move, white to move
     const int avail = root_hist_len + depth;
     const int kk = lane >> 1, colour = (lane & 1) == 0 ? t - 1 : 2 - t;
-    uint32_t* out = v.feat + size_t(g) * 20 * v.W32;
+    uint32_t* out = leafPlanes(v, g, 20);
 #pragma unroll
     for (int i = 0; i < NW; ++i) {
         if (i >= W) { continue; }
@@ -1274,16 +1204,9 @@ __device__ __forceinline__ void havLeafBodyT(const GoDevView& v, const PoolView&
         if (lane == 17) { word = swappable ? k.full[i] : 0ull; }
         if (lane == 18) { word = t == 1 ? k.full[i] : 0ull; }
         if (lane == 19) { word = t == 2 ? k.full[i] : 0ull; }
-        if (lane < 20) {
-            if (2 * i < v.W32) { out[lane * v.W32 + 2 * i] = static_cast<uint32_t>(word); }
-            if (2 * i + 1 < v.W32) { out[lane * v.W32 + 2 * i + 1] = static_cast<uint32_t>(word >> 32); }
-        }
+        storePlaneWord(v, out, lane, 20, i, word);
     }
-    if (lane == 0) {
-        v.leaf_player[g] = t;
-        v.terminal[g] = terminal ? 1 : 0;
-        v.eval[g] = winner == 1 ? 1.0f : (winner == 2 ? -1.0f : 0.0f); // ref havannah.cpp:186-194
-    }
+    if (lane == 0) { storeLeafResult(v, g, t, terminal, winnerEval(winner)); } // ref havannah.cpp:186-194
 }
 
 __device__ __forceinline__ void havLeafBody(const GoDevView& v, const PoolView& pv, int /*rot: no symmetries, havannah.h:71*/, int slot, int g, int lane)

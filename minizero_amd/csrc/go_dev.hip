@@ -65,9 +65,9 @@ int GoDevice::init(int device, int games, int board_n, float komi, int action_si
     if (!isDeviceGame(kind_arg)) { setError("GoDevice: unknown kind %d", kind_arg); return MZ_ERR_ARG; }
     const GameKind kind = static_cast<GameKind>(kind_arg);
     if (kind == kOthello && board_n > gameMaxBoard(kOthello)) { setError("GoDevice: Othello boards up to 8x8"); return MZ_ERR_ARG; }
-    if (kind == kNoGo && board_n > kNoGoMaxBoard) { setError("GoDevice: NoGo boards up to %dx%d", kNoGoMaxBoard, kNoGoMaxBoard); return MZ_ERR_ARG; } // (nogoLeafBody: two words per bitboard)
-    if (kind == kHavannah && (board_n % 2 == 0 || board_n < networkBoard(kHavannah, gameMinBoard(kHavannah)) || board_n > networkBoard(kHavannah, kHavannahMaxBoard))) { // (board_n: the array's side 2N - 1)
-        setError("GoDevice: Havannah arrays of 7x7 .. 19x19 (edge sizes %d .. %d)", gameMinBoard(kHavannah), kHavannahMaxBoard);
+    if (kind == kNoGo && board_n > gameMaxBoard(kNoGo)) { setError("GoDevice: NoGo boards up to %dx%d", gameMaxBoard(kNoGo), gameMaxBoard(kNoGo)); return MZ_ERR_ARG; } // (nogoLeafBody: two words per bitboard)
+    if (kind == kHavannah && (board_n % 2 == 0 || board_n < networkBoard(kHavannah, gameMinBoard(kHavannah)) || board_n > networkBoard(kHavannah, gameMaxBoard(kHavannah)))) { // (board_n: the array's side 2N - 1)
+        setError("GoDevice: Havannah arrays of 7x7 .. 19x19 (edge sizes %d .. %d)", gameMinBoard(kHavannah), gameMaxBoard(kHavannah));
         return MZ_ERR_ARG;
     }
     if (kind == kTicTacToe && (board_n != 3 || action_size != 9)) { setError("GoDevice: TicTacToe is 3x3 with 9 actions"); return MZ_ERR_ARG; }

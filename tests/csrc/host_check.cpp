@@ -302,8 +302,8 @@ static int gamesMain()
             o.board_size = n;
             std::unique_ptr<mz::GameEnv> e = mz::createGameEnv(o);
             if (!e) { fprintf(stderr, "games: %s %dx%d: %s\n", mz::gameName(k), n, n, mz_last_error()); return 1; }
-            const int P = n * n;
-            GAMES_CHECK(e->boardSize() == n)
+            const int side = mz::networkBoard(k, n), P = side * side; // (Havannah's engine reports the array: game_kind.h networkBoard)
+            GAMES_CHECK(e->boardSize() == side)
             GAMES_CHECK(e->policySize() == P + (mz::gameHasPass(k) ? 1 : 0))
             GAMES_CHECK(e->numInputChannels() == mz::gameChannels(k))
             GAMES_CHECK(e->deviceKind() == k && e->hasDeviceTwin())
@@ -313,7 +313,9 @@ static int gamesMain()
             case 1: want = 0; break;             // Othello
             case 2: want = -1; break;            // TicTacToe
             case 3: want = -2; break;            // Gomoku
-            default: want = -3; break;           // Hex
+            case 4: want = -3; break;            // Hex
+            case 5: want = -4; break;            // NoGo
+            default: want = -5; break;           // Havannah
             }
             GAMES_CHECK(mz::rulesArg(k, n) == want)
             ++engines;
@@ -323,13 +325,15 @@ static int gamesMain()
             mz::EnvOptions o;
             o.game = mz::gameName(k);
             std::unique_ptr<mz::GameEnv> e = mz::createGameEnv(o);
-            GAMES_CHECK(e && e->boardSize() == mz::gameDefaultBoard(k))
+            GAMES_CHECK(e && e->boardSize() == mz::networkBoard(k, mz::gameDefaultBoard(k)))
         }
     }
 #undef GAMES_CHECK
     if (mz::gameHasPass(mz::kGo) != true || mz::gameHasPass(mz::kOthello) != true || mz::gameHasPass(mz::kTicTacToe) || mz::gameHasPass(mz::kGomoku) || mz::gameHasPass(mz::kHex) ||
         mz::gameChannels(mz::kGo) != 18 || mz::gameChannels(mz::kOthello) != 4 || mz::gameMaxBoard(mz::kOthello) != 8 || mz::gameMaxBoard(mz::kTicTacToe) != 3 ||
-        mz::gameMaxBoard(mz::kGo) != 19 || mz::gameMaxBoard(mz::kGomoku) != 19 || mz::gameMaxBoard(mz::kHex) != 19) {
+        mz::gameMaxBoard(mz::kGo) != 19 || mz::gameMaxBoard(mz::kGomoku) != 19 || mz::gameMaxBoard(mz::kHex) != 19 ||
+        mz::gameChannels(mz::kNoGo) != 18 || mz::gameHasPass(mz::kNoGo) != true || mz::gameMaxBoard(mz::kNoGo) != 9 ||
+        mz::gameChannels(mz::kHavannah) != 20 || mz::gameHasPass(mz::kHavannah) || mz::gameMaxBoard(mz::kHavannah) != 10 || mz::networkBoard(mz::kHavannah, 8) != 15) {
         fprintf(stderr, "games: a fact of the table changed\n");
         return 1;
     }

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gomoku_rules as R
+from game_paths import GUMBEL, run_paths
 
 pytestmark = pytest.mark.gpu
 
@@ -54,10 +55,13 @@ def _random_game(mz, conf, rng):
 
 
 @pytest.mark.parametrize("n,rule,five,games", [(15, r, f, 6) for r, f in RULES] + [(19, "standard", True, 3), (19, "outer_open", False, 2),
-                                                                                (5, "standard", True, 10), (5, "outer_open", False, 10)])
+                                                                                (5, "standard", True, 10), (5, "outer_open", False, 10),
+                                                                                (8, "standard", True, 3), (9, "outer_open", False, 3)])
 def test_device_engine_matches_host_engine(mz, n, rule, five, games):
     """Random whole games; the device replays the tail move by move from roots at several depths (root_prefix 0 .. the last move, so that the winning
-    or board-filling stone is a device move): planes under random rotations, legal mask, terminal flag, result and player to move after every move."""
+    or board-filling stone is a device move): planes under random rotations, legal mask, terminal flag, result and player to move after every move.
+    The boards cover the boundaries of the planes' words: 8x8 is one full 64-bit word, 9x9 two words of which the second has one 32-bit half only (5x5:
+    the same in the first word), 15x15 four words, 19x19 the most a bitboard holds."""
     rng = np.random.default_rng(100 * n + 10 * RULES.index((rule, five)))
     conf = _conf(n, rule, five)
     outcomes = set()
@@ -121,33 +125,6 @@ def _desc(mz, n, c, blocks, type_name="alphazero"):
     return mz.make_desc(f"gomoku_{n}x{n}", 4, n, n, c, n, n, 1, blocks, n * n, vh=32, dv=1, type_name=type_name)
 
 
-PATHS = {"sim": "", "lockstep_device": ":mz_sim_kernel=false", "lockstep_host": ":mz_device_env=false"}
-
-
-def _run_paths(mz, conf, d, w, games, cycles, paths=("sim", "lockstep_device", "lockstep_host"), expect_sim=True):
-    out = {}
-    for path in paths:
-        wk = mz.Worker(conf + PATHS[path], d, w)
-        wk.command("start")
-        assert wk.run_cycles(cycles) == cycles
-        st = wk.stats()
-        if path == "sim" and expect_sim:
-            assert st["sim_launches"] > 0 and st["sim_cycles"] > cycles // 2, ("the per-game simulation kernel did not run", st)
-        else:
-            assert st["sim_launches"] == 0, (path, st)
-        if path != "lockstep_host":
-            assert st["ms_env"] == 0, (path, "the device rules were not resident", st)
-        else:
-            assert st["ms_env"] > 0, st
-        out[path] = (wk.pop_lines(), wk.peek_records(games))
-        wk.close()
-    first = out[paths[0]]
-    for path in paths[1:]:
-        assert out[path][0] == first[0], f"{path}: finished records differ from {paths[0]}'s"
-        assert out[path][1] == first[1], f"{path}: records as they stand differ from {paths[0]}'s"
-    return first
-
-
 def _check_records(lines, n, rule, five):
     name = f"gomoku_{'oo_' if rule == 'outer_open' else ''}{n}x{n}"
     for line in lines:
@@ -165,7 +142,7 @@ def _check_records(lines, n, rule, five):
 CASES = [  # (c, blocks, extra configuration, rule, five, seed)
     (32, 2, "", "standard", True, 1),
     (64, 1, "", "standard", True, 2),
-    (32, 1, ":actor_use_dirichlet_noise=false:actor_use_gumbel=true:actor_use_gumbel_noise=true:actor_gumbel_sample_size=8", "standard", True, 3),
+    (32, 1, GUMBEL, "standard", True, 3),
     (32, 1, "", "outer_open", True, 4),
     (32, 1, "", "standard", False, 5),
 ]
@@ -180,7 +157,7 @@ def test_records_equal_across_the_three_paths(mz, c, blocks, extra, rule, five, 
     w = mz.generate_weights(d, seed)
     conf = f"{_conf(n, rule, five)}:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed={seed}:nn_file_name=x.pt:zero_num_threads=2{extra}"
     cycles = (sims + 1) * 230  # longer than any game on 225 points
-    lines, recs = _run_paths(mz, conf, d, w, games, cycles)
+    lines, recs = run_paths(mz, conf, d, w, games, cycles)
     assert len(lines) >= games
     _check_records(lines, n, rule, five)
 
@@ -192,7 +169,7 @@ def test_default_network_takes_the_lock_step_path_with_device_rules(mz):
     d = _desc(mz, n, 256, 1)
     w = mz.generate_weights(d, 7)
     conf = f"{_conf()}:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed=7:nn_file_name=x.pt:zero_num_threads=2"
-    _, recs = _run_paths(mz, conf, d, w, games, 2 * (sims + 1), paths=("sim", "lockstep_host"), expect_sim=False)
+    _, recs = run_paths(mz, conf, d, w, games, 2 * (sims + 1), paths=("sim", "lockstep_host"), expect_sim=False)
     assert all(";B[" in r for r in recs)
 
 

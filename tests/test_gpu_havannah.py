@@ -3,23 +3,20 @@
 finished record against the pure-Python rules model (tests/havannah_rules.py: there is no oracle for this game), the terminal leaves that skip the
 network, the learner-side sampler's device replay and its refusals, and the `-mode sp` executable.  ref environment/havannah/havannah.{h,cpp}.
 Edge size N plays on the E x E array, E = 2N - 1: N = 4 is one word per bitboard (7x7), N = 5 two (9x9), N = 8 four (15x15), N = 10 six (19x19)."""
-import json
 import os
 import re
 import subprocess
-import sys
 import threading
 
 import numpy as np
 import pytest
 
 import havannah_rules as R
+from game_paths import GUMBEL, NO_RESIGN, child, run_paths
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NO_RESIGN = ":actor_resign_threshold=-2"
-GUMBEL = ":actor_use_dirichlet_noise=false:actor_use_gumbel=true:actor_use_gumbel_noise=true:actor_gumbel_sample_size=8"
 
 
 def _conf(N=8, swap=True):
@@ -117,36 +114,6 @@ def _desc(mz, N, c, blocks, type_name="alphazero"):
     return mz.make_desc(f"havannah{N}x{N}", 20, E, E, c, E, E, 1, blocks, E * E, vh=32, dv=1, type_name=type_name)
 
 
-PATHS = {"sim": "", "lockstep_device": ":mz_sim_kernel=false", "lockstep_host": ":mz_device_env=false"}
-
-
-def _check_path_stats(st, path, cycles, expect_sim=True):
-    if path == "sim" and expect_sim:
-        assert st["sim_launches"] > 0 and st["sim_cycles"] > cycles // 2, ("the per-game simulation kernel did not run", st)
-    else:
-        assert st["sim_launches"] == 0, (path, st)
-    if path != "lockstep_host":
-        assert st["ms_env"] == 0, (path, "the device rules were not resident", st)
-    else:
-        assert st["ms_env"] > 0, st
-
-
-def _run_paths(mz, conf, d, w, games, cycles, paths=("sim", "lockstep_device", "lockstep_host"), expect_sim=True):
-    out = {}
-    for path in paths:
-        wk = mz.Worker(conf + PATHS[path], d, w)
-        wk.command("start")
-        assert wk.run_cycles(cycles) == cycles
-        _check_path_stats(wk.stats(), path, cycles, expect_sim)
-        out[path] = (wk.pop_lines(), wk.peek_records(games))
-        wk.close()
-    first = out[paths[0]]
-    for path in paths[1:]:
-        assert out[path][0] == first[0], f"{path}: finished records differ from {paths[0]}'s"
-        assert out[path][1] == first[1], f"{path}: records as they stand differ from {paths[0]}'s"
-    return first
-
-
 def _check_records(lines, N, swap=True):
     """Every record replays legally on the model with the right result, name and SZ; returns how the games ended."""
     ends = []
@@ -172,7 +139,7 @@ def test_records_equal_across_the_three_paths_whole_games(mz, extra, seed):
     w = mz.generate_weights(d, seed)
     conf = f"{_conf(N)}:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed={seed}:nn_file_name=x.pt:zero_num_threads=2{NO_RESIGN}{extra}"
     cycles = (sims + 1) * 38
-    lines, recs = _run_paths(mz, conf, d, w, games, cycles)
+    lines, recs = run_paths(mz, conf, d, w, games, cycles)
     assert len(lines) >= games
     ends = _check_records(lines, N)
     print(f"{len(lines)} records, ended by {sorted(set(ends))}")
@@ -185,7 +152,7 @@ def test_records_equal_across_the_three_paths_default_board(mz, extra, seed):
     d = _desc(mz, N, 32, 1)
     w = mz.generate_weights(d, seed)
     conf = f"{_conf(N)}:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed={seed}:nn_file_name=x.pt:zero_num_threads=2{NO_RESIGN}{extra}"
-    lines, recs = _run_paths(mz, conf, d, w, games, 3 * (sims + 1))
+    lines, recs = run_paths(mz, conf, d, w, games, 3 * (sims + 1))
     assert all(r.count(";B[") >= 1 and r.count(";W[") >= 1 for r in recs), recs[0][:300]
 
 
@@ -196,40 +163,9 @@ def test_other_shapes_play_lock_step_on_the_device_rules(mz):
     d = _desc(mz, N, 32, 1)
     w = mz.generate_weights(d, 5)
     conf = f"{_conf(N)}:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed=5:nn_file_name=x.pt:zero_num_threads=2{NO_RESIGN}"
-    lines, recs = _run_paths(mz, conf, d, w, games, (sims + 1) * 62, paths=("sim", "lockstep_host"), expect_sim=False)
+    lines, recs = run_paths(mz, conf, d, w, games, (sims + 1) * 62, paths=("sim", "lockstep_host"), expect_sim=False)
     assert len(lines) >= games
     _check_records(lines, N)
-
-
-CHILD = r"""
-import json, sys
-sys.path.insert(0, sys.argv[1])
-import minizero_amd as mz
-conf, args, wseed, cycles = json.loads(sys.argv[2])
-d = mz.make_desc(*args[:10], vh=args[10], dv=args[11], type_name=args[12])
-wk = mz.Worker(conf, d, mz.generate_weights(d, wseed))
-wk.command("start")
-assert wk.run_cycles(cycles) == cycles
-st = wk.stats()
-out = {"lines": wk.pop_lines(), "records": wk.peek_records(int(sys.argv[3])), "sim_launches": st["sim_launches"]}
-wk.close()
-print("RESULT " + json.dumps(out), flush=True)
-"""
-
-
-def _child(conf, args, wseed, cycles, games, no_spec):
-    env = dict(os.environ, MZ_SIM_PROF="1")
-    env.pop("MZ_NO_SPEC", None)
-    if no_spec:
-        env["MZ_NO_SPEC"] = str(no_spec)
-    r = subprocess.run([sys.executable, "-c", CHILD, ROOT, json.dumps([conf, list(args), wseed, cycles]), str(games)], env=env, capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, f"worker process failed ({r.returncode}):\n{r.stdout[-2000:]}\n{r.stderr[-4000:]}"
-    out = json.loads(next(l for l in r.stdout.splitlines() if l.startswith("RESULT "))[7:])
-    m = re.search(r"network skipped in (\d+) of (\d+) simulations", r.stderr)
-    assert m, "no terminal-leaf line in the MZ_SIM_PROF dump:\n" + r.stderr[-4000:]
-    out["skipped"], out["sims"] = int(m.group(1)), int(m.group(2))
-    return out
 
 
 def test_terminal_leaves_skip_the_network(mz):
@@ -239,8 +175,8 @@ def test_terminal_leaves_skip_the_network(mz):
     args = ("havannah4x4", 20, 7, 7, 32, 7, 7, 1, 1, 49, 16, 1, "alphazero")
     conf = f"{_conf(4)}:actor_num_simulation={sims}:zero_num_parallel_games={games}:actor_use_dirichlet_noise=false:program_seed=11:nn_file_name=x.pt:zero_num_threads=2{NO_RESIGN}"
     cycles = (sims + 1) * 38
-    skip = _child(conf, args, 3, cycles, games, 0)
-    full = _child(conf, args, 3, cycles, games, 16)
+    skip = child(conf, args, 3, cycles, games, 0)
+    full = child(conf, args, 3, cycles, games, 16)
     print(f"network skipped in {skip['skipped']} of {skip['sims']} simulations; with MZ_NO_SPEC=16 in {full['skipped']} of {full['sims']}")
     for r in (skip, full):
         assert r["sim_launches"] > 0 and r["sims"] == cycles * games

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import hex_rules as R
+from game_paths import GUMBEL, PATHS, run_paths
 
 pytestmark = pytest.mark.gpu
 
@@ -57,7 +58,8 @@ def _random_game(mz, conf, rng, take_swap):
     return actions, env.eval_score()
 
 
-@pytest.mark.parametrize("n,swap,games", [(11, True, 9), (11, False, 6), (19, True, 3), (19, False, 3), (5, True, 12), (5, False, 9), (3, True, 9), (3, False, 6)])
+@pytest.mark.parametrize("n,swap,games", [(11, True, 9), (11, False, 6), (19, True, 3), (19, False, 3), (5, True, 12), (5, False, 9), (3, True, 9), (3, False, 6),
+                                          (8, False, 6), (9, True, 6)])  # 8x8: one full 64-bit word of planes; 9x9: the second word has one 32-bit half only
 def test_device_engine_matches_host_engine(mz, n, swap, games):
     """Random whole games; the device replays the tail action by action from roots at several depths (root_prefix 0 .. the last move, so that the
     winning stone is a device move): planes under random rotation arguments, legal mask, terminal flag, result and player to move after every
@@ -156,36 +158,6 @@ def _desc(mz, n, c, blocks, type_name="alphazero"):
     return mz.make_desc(f"hex_{n}x{n}", 4, n, n, c, n, n, 1, blocks, n * n, vh=32, dv=1, type_name=type_name)
 
 
-PATHS = {"sim": "", "lockstep_device": ":mz_sim_kernel=false", "lockstep_host": ":mz_device_env=false"}
-
-
-def _check_path_stats(st, path, cycles, expect_sim=True):
-    if path == "sim" and expect_sim:
-        assert st["sim_launches"] > 0 and st["sim_cycles"] > cycles // 2, ("the per-game simulation kernel did not run", st)
-    else:
-        assert st["sim_launches"] == 0, (path, st)
-    if path != "lockstep_host":
-        assert st["ms_env"] == 0, (path, "the device rules were not resident", st)
-    else:
-        assert st["ms_env"] > 0, st
-
-
-def _run_paths(mz, conf, d, w, games, cycles, paths=("sim", "lockstep_device", "lockstep_host"), expect_sim=True):
-    out = {}
-    for path in paths:
-        wk = mz.Worker(conf + PATHS[path], d, w)
-        wk.command("start")
-        assert wk.run_cycles(cycles) == cycles
-        _check_path_stats(wk.stats(), path, cycles, expect_sim)
-        out[path] = (wk.pop_lines(), wk.peek_records(games))
-        wk.close()
-    first = out[paths[0]]
-    for path in paths[1:]:
-        assert out[path][0] == first[0], f"{path}: finished records differ from {paths[0]}'s"
-        assert out[path][1] == first[1], f"{path}: records as they stand differ from {paths[0]}'s"
-    return first
-
-
 def _check_records(lines, n, swap):
     """Every record replays legally on the model with the right result and name; returns how many of them hold a swap (B[k];W[k])."""
     swaps = 0
@@ -203,7 +175,7 @@ def _check_records(lines, n, swap):
 CASES = [  # (c, blocks, extra configuration, swap, seed)
     (32, 2, "", True, 1),
     (64, 1, "", True, 2),
-    (32, 1, ":actor_use_dirichlet_noise=false:actor_use_gumbel=true:actor_use_gumbel_noise=true:actor_gumbel_sample_size=8", True, 3),
+    (32, 1, GUMBEL, True, 3),
     (32, 1, "", False, 4),
 ]
 
@@ -218,7 +190,7 @@ def test_records_equal_across_the_three_paths(mz, c, blocks, extra, swap, seed):
     w = mz.generate_weights(d, seed)
     conf = f"{_conf(n, swap)}:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed={seed}:nn_file_name=x.pt:zero_num_threads=2{extra}"
     cycles = (sims + 1) * 125  # longer than any game: 122 actions at most
-    lines, recs = _run_paths(mz, conf, d, w, games, cycles)
+    lines, recs = run_paths(mz, conf, d, w, games, cycles)
     assert len(lines) >= games
     swaps = _check_records(lines, n, swap)
     print(f"{len(lines)} records, {swaps} with a swap")
@@ -300,10 +272,9 @@ def test_default_network_path(mz):
 def test_muzero_and_gumbel_muzero_on_hex(mz):
     """MuZero and Gumbel MuZero (the host engine at the root only): finished records replay legally; the two MuZero paths agree."""
     n, sims, games = 7, 8, 6
-    gumbel = ":actor_use_dirichlet_noise=false:actor_use_gumbel=true:actor_use_gumbel_noise=true:actor_gumbel_sample_size=8"
     d = _desc(mz, n, 32, 1, "muzero")
     w = mz.generate_weights(d, 11)
-    for variant in ("", gumbel):
+    for variant in ("", GUMBEL):
         conf = f"{_conf(n)}:nn_type_name=muzero:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed=11:nn_file_name=x.pt:zero_num_threads=2{variant}"
         out = []
         for extra in ("", ":mz_sim_kernel=false"):

@@ -177,9 +177,11 @@ def test_sharp_searches_equal_the_oracle(mz, oracle, name, variant):
 @pytest.mark.parametrize("game", ["hex", "gomoku"])
 def test_sharp_searches_without_an_oracle(mz, game):
     """Hex 11x11 and Gomoku 15x15 (1 block x 32 channels, sim_kernel_wide) have no oracle: at gain (1024, 8) the three execution paths must write the same lines
-    and records, and every finished record must replay legally on the rules model with the right result (the helpers of test_gpu_hex.py / test_gpu_gomoku.py)."""
+    and records, and every finished record must replay legally on the rules model with the right result (the helpers of game_paths.py, test_gpu_hex.py and
+    test_gpu_gomoku.py)."""
     import test_gpu_gomoku as TG
     import test_gpu_hex as TH
+    from game_paths import run_paths
     sims, games, seed = 16, 8, 1
     if game == "hex":
         n, d, conf = 11, TH._desc(mz, 11, 32, 1), TH._conf(11, True)
@@ -188,7 +190,7 @@ def test_sharp_searches_without_an_oracle(mz, game):
     w = sharpen(d, mz.generate_weights(d, seed), 1024, 8)
     conf = f"{conf}:actor_num_simulation={sims}:zero_num_parallel_games={games}:program_seed={seed}:nn_file_name=x.pt:zero_num_threads=2"
     cycles = (sims + 1) * (125 if game == "hex" else 230)  # longer than any game
-    lines, recs = (TH if game == "hex" else TG)._run_paths(mz, conf, d, w, games, cycles)
+    lines, recs = run_paths(mz, conf, d, w, games, cycles)
     assert len(lines) >= games
     if game == "hex":
         TH._check_records(lines, n, True)

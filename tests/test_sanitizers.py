@@ -152,7 +152,7 @@ def test_parsers_under_asan_ubsan(mz, oracle, binaries, tmp_path):
 def test_game_table_matches_the_host_engines(binaries):
     """every row of minizero_amd/csrc/game_kind.h against the engine it describes (smallest, default, largest board): policy size, planes, device kind, the
     literal rules arguments of the kernels; the Atari-shaped engine reports no device game"""
-    assert "games ok: 15 engines of 5 games" in run(binaries["asan"], "games")
+    assert "games ok: 21 engines of 7 games" in run(binaries["asan"], "games")
 
 
 @pytest.mark.parametrize("seed", range(10))
