@@ -86,7 +86,9 @@ struct WorkerConfig {
     // (mz_worker_search_action / mz_worker_act / mz_worker_reset_search): the per-actor stepping of BaseActor / ZeroActor::think()
     bool mz_manual_step = false;
     // not a reference key: arithmetic of the residual tower — "f32" (default: bit-exact against the oracle, records identical to the reference)
-    // or "bf16x3" (opt-in: split-bf16 operands on the 16-bit MFMA, outputs within 1e-3, records not bit-identical; net_bf16_body.h, net_bf16_wide_body.h)
+    // or "bf16x3" (opt-in: split-bf16 operands on the 16-bit MFMA, outputs within 1e-3, records not bit-identical; net_bf16_body.h, net_bf16_wide_body.h).
+    // Built for AlphaZero networks of 64 hidden channels on 9x9 / 8x8 / 11x11 / 15x15 boards (Go, Othello, Hex, Gomoku, Havannah edge size 8) and of 128 / 256
+    // on 9x9 boards; every other network is refused at init (Net::setPrecision)
     std::string mz_nn_precision = "f32";
     int mz_zero_copy = 3; // bit 0: kernels read their inputs from pinned host memory; bit 1: kernels write their outputs there
 

@@ -106,7 +106,7 @@ public:
     // num_simulation: the kernels keep per-search tables / the path in LDS; searches too long for 160 KB use the lock-step kernels
     bool hasSimKernel(int board_n, int env_kind = kGo, int num_simulation = 0) const; // env_kind: GameKind, as stored in GoDevView::kind
     // ... on the one-tile tower (sim_wide.inc, sim_wide_a.hip): Go with 128 / 256 hidden channels or on 7x7 / 13x13 / 19x19 boards; at the network's precision
-    // (bf16x3: sim_kernel_wide_bf16, sim_wide_bf16.inc — 9x9 Go with 128 / 256 hidden channels)
+    // (bf16x3: sim_kernel_wide_bf16, sim_wide_bf16.inc — 9x9 Go with 128 / 256 hidden channels; Gomoku 15x15, Hex 11x11 and Havannah 15x15 with 64)
     bool hasSimKernelWide(int board_n, int env_kind, int num_simulation) const;
     bool simWidePlan(int board_n, int env_kind, int num_simulation, const HeadParams& hp, int channels, int W32, size_t leaf_bytes, size_t scratch_bytes, int* lf, size_t* lds,
                      size_t* tile_bytes_out) const;
@@ -151,10 +151,16 @@ public:
     void makeAtariHeadParams(AtariHeadParams* out) const; // net_atari.hip
     // opt-in 16-bit-input tower (net_bf16_body.h; net_bf16_wide_body.h): 0 = f32 (default, bit-exact against the oracle), 1 = bf16x3 (split bf16 operands on
     // v_mfma_f32_16x16x32_bf16, f32 accumulation; outputs within 1e-3 of the f32 path, records not bit-identical to the reference).  Built for AlphaZero networks
-    // of 64 hidden channels on 9x9 / 8x8 boards and of 128 / 256 hidden channels on 9x9 boards (bf16Supported); every other shape is refused.
+    // of 64 hidden channels on 9x9 / 8x8 / 11x11 / 15x15 boards and of 128 / 256 hidden channels on 9x9 boards (bf16Supported); every other shape — 19x19 x 64
+    // among them — is refused.
     int setPrecision(int mode);
     int precision() const { return precision_; }
     bool bf16Supported() const;
+    bool bf16TwoTile() const              // the shapes of the two-tile body (net_bf16_body.h); every other supported shape runs the one-tile body
+    {
+        const int H = desc_.hidden_channel_height, W = desc_.hidden_channel_width;
+        return desc_.num_hidden_channels == 64 && ((H == 9 && W == 9) || (H == 8 && W == 8));
+    }
     int timeForward(int B, int iters, float* ms_total, float* ms_conv, double* conv_flops);
     int timeTowerConv(int B, int iters, float* ms_per_launch, double* flops_per_launch, double* bytes_per_launch);
 
@@ -183,7 +189,7 @@ private:
     bool makeTowerArgsBf16(TowerArgsBf16* out) const;
     int packBf16(const std::vector<float>& packed);
     int launchTowerBf16(const float* d_feat, float** out, int B, bool in_bits);
-    int launchTowerBf16Wide(const TowerArgsBf16& ta, const unsigned* bits, float* gx, float* gt, float* out, int B); // net_bf16_wide.hip: 128 / 256 channels
+    int launchTowerBf16Wide(const TowerArgsBf16& ta, const unsigned* bits, float* gx, float* gt, float* out, int B); // net_bf16_wide.hip: the one-tile body's shapes
     int precision_ = 0;
     DevBuf<uint4> wfrag_;                 // bf16 hi / lo A-fragments of the representation trunk (built at load when the shape is supported)
     std::vector<unsigned> wfrag_off_;     // per layer, in 16-byte units

@@ -210,8 +210,9 @@ bool Net::bf16Supported() const
 {
     const int H = desc_.hidden_channel_height, W = desc_.hidden_channel_width, C = desc_.num_hidden_channels;
     if (desc_.type != 0 || repr_.size() < 3 || repr_.size() > 48 || (repr_.size() % 2) != 1 || repr_[0].cin > 32) { return false; }
-    if (C == 64) { return (H == 9 && W == 9) || (H == 8 && W == 8); } // the two-tile body (net_bf16_body.h)
-    return (C == 128 || C == 256) && H == 9 && W == 9;                // the one-tile body (net_bf16_wide_body.h)
+    if (bf16TwoTile()) { return true; }                                  // the two-tile body (net_bf16_body.h)
+    if (C == 64) { return H == W && (H == 11 || H == 15); }              // the one-tile body (net_bf16_wide_body.h): two pixel groups
+    return (C == 128 || C == 256) && H == 9 && W == 9;                   // ... all pixel tiles on every wave
 }
 
 int Net::packBf16(const std::vector<float>& packed)
@@ -254,8 +255,8 @@ int Net::setPrecision(int mode)
 {
     if (mode != 0 && mode != 1) { setError("precision %d unknown (0 = f32, 1 = bf16x3)", mode); return MZ_ERR_ARG; }
     if (mode == 1 && !bf16Supported()) {
-        setError("mz_nn_precision=bf16x3 is built for AlphaZero networks with 64 hidden channels on 9x9 / 8x8 boards and with 128 / 256 hidden channels on 9x9 boards "
-                 "(at most 32 input planes); this network (%s, %dx%d x %d channels) keeps the f32 tower",
+        setError("mz_nn_precision=bf16x3 is built for AlphaZero networks with 64 hidden channels on 9x9 / 8x8 / 11x11 / 15x15 boards and with 128 / 256 hidden channels on 9x9 "
+                 "boards (at most 32 input planes); this network (%s, %dx%d x %d channels) keeps the f32 tower",
                  desc_.type == 0 ? "alphazero" : "muzero", desc_.hidden_channel_height, desc_.hidden_channel_width, desc_.num_hidden_channels);
         return MZ_ERR_ARG;
     }
@@ -287,7 +288,7 @@ int Net::launchTowerBf16(const float* d_feat, float** out, int B, bool in_bits)
         MZ_HIP(hipGetLastError());
         bits = bits_in_.p;
     }
-    if (ta.C != 64) { *out = act_[2].p; return launchTowerBf16Wide(ta, bits, act_[0].p, act_[1].p, act_[2].p, B); } // (x of the blocks in act_[0] / act_[1])
+    if (!bf16TwoTile()) { *out = act_[2].p; return launchTowerBf16Wide(ta, bits, act_[0].p, act_[1].p, act_[2].p, B); } // (x of the blocks in act_[0] / act_[1])
     *out = act_[0].p;
     if (H == 9 && W == 9) { return launchTowerBf16T<9, 9>(ta, wfrag_.p, params_.p, bits, act_[0].p, B, stream_); }
     return launchTowerBf16T<8, 8>(ta, wfrag_.p, params_.p, bits, act_[0].p, B, stream_);

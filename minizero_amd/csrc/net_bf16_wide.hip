@@ -1,5 +1,5 @@
-// The one-tile bf16x3 tower (net_bf16_wide_body.h) as a stand-alone launch: 9x9 AlphaZero networks with 128 / 256 hidden channels under
-// `mz_nn_precision=bf16x3` — mz_net_forward_az and the lock-step worker.  gfx950, -ffp-contract=off.
+// The one-tile bf16x3 tower (net_bf16_wide_body.h) as a stand-alone launch: AlphaZero networks with 128 / 256 hidden channels on 9x9 boards and with 64 on
+// 11x11 / 15x15 boards under `mz_nn_precision=bf16x3` — mz_net_forward_az and the lock-step worker.  gfx950, -ffp-contract=off.
 #include "net.h"
 #include "net_bf16_wide_body.h"
 
@@ -30,6 +30,8 @@ int Net::launchTowerBf16Wide(const TowerArgsBf16& ta, const unsigned* bits, floa
     const int H = desc_.hidden_channel_height, W = desc_.hidden_channel_width, C = desc_.num_hidden_channels;
     if (H == 9 && W == 9 && C == 128) { return launchTowerBf16WideT<9, 9, 128>(ta, wfrag_.p, params_.p, bits, gx, gt, out, B, stream_); }
     if (H == 9 && W == 9 && C == 256) { return launchTowerBf16WideT<9, 9, 256>(ta, wfrag_.p, params_.p, bits, gx, gt, out, B, stream_); }
+    if (H == 11 && W == 11 && C == 64) { return launchTowerBf16WideT<11, 11, 64>(ta, wfrag_.p, params_.p, bits, gx, gt, out, B, stream_); }
+    if (H == 15 && W == 15 && C == 64) { return launchTowerBf16WideT<15, 15, 64>(ta, wfrag_.p, params_.p, bits, gx, gt, out, B, stream_); }
     setError("bf16x3 tower: no one-tile instance for %dx%d x %d channels", H, W, C);
     return MZ_ERR_STATE;
 }

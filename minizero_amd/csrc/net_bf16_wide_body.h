@@ -1,4 +1,4 @@
-// The opt-in bf16x3 tower (`mz_nn_precision=bf16x3`) for 128 and 256 hidden channels: the arithmetic of net_bf16_body.h — every f32 value v carried as
+// The opt-in bf16x3 tower (`mz_nn_precision=bf16x3`) for 128 and 256 hidden channels (9x9) and for 64 hidden channels on 11x11 / 15x15 boards: the arithmetic of net_bf16_body.h — every f32 value v carried as
 // hi = bf16(v), lo = bf16(v - hi), a product as three v_mfma_f32_16x16x32_bf16 (hi * lo, lo * hi, hi * hi) into one f32 accumulator, bias + skip + ReLU in
 // f32, the stem's 0 / 1 planes as hi alone — on the data flow of the one-tile f32 tower (net_wide_body.h): the 64-channel body's four LDS buffers (x and t,
 // each as hi and lo) would be 128 KB at 128 channels and 256 KB at 256.
@@ -13,6 +13,10 @@
 //   * A fragments ([tap][oc-tile][k-block][hi, lo][lane] x 8, bf16_split.h) travel D steps ahead of their MFMAs in a register ring, the next layer's first D
 //     steps are fetched before the barrier; B fragments one step ahead in a pinned order (net_bf16_body.h).  The tap loop is a real loop (a 256-channel
 //     layer unrolled would be 2600 MFMAs of code).
+//   * 64 channels (11x11, 15x15: boards whose four buffers of net_bf16_body.h would not leave the simulation kernel its blocks) are 4 oc-tiles for 8 waves:
+//     wave w owns oc-tile w & 3 and one of TWO PIXEL GROUPS (w >> 2), the split of the f32 one-tile tower (net_wide_body.h WideGeo: WO = 4, WP = 2) — 11x11:
+//     4 + 4 pixel tiles; 15x15: 8 + 7, the last one the corner tile (225 = 14 * 16 + 1).  An output still belongs to the same lane in every layer.  With
+//     KB = 2 k-blocks per tap the ring's D = 4 steps are two taps: the tap loop goes round the ring once per pair of taps, and tap 8 is taken alone.
 // gfx950, -ffp-contract=off.
 #pragma once
 #include "net_bf16_body.h"
@@ -36,36 +40,41 @@ struct Bf16WideGeo {
     using TM = TileMap<H, W>;
     static constexpr int BW = W, P = H * W, PW = W + 2, NPOS = (H + 2) * (W + 2), NPOS16 = (NPOS + 16) / 16 * 16; // at least one spare position (the dump slot)
     static constexpr int CH = C / 8, KB = C / 32, OT = C / 16;
-    static constexpr int NOT = OT / 8;         // oc-tiles per wave
-    static constexpr int NT = TM::PT;          // pixel tiles per wave: all of them
+    static constexpr int WO = OT < 8 ? OT : 8, WP = 8 / WO; // waves side by side over the oc-tiles / pixel groups (128, 256 channels: 8 / 1; 64 channels: 4 / 2)
+    static constexpr int NOT = OT / WO;        // oc-tiles per wave
+    static constexpr int PT = TM::PT;
+    static constexpr int groupTiles(int wp) { return PT / WP + (wp < PT % WP ? 1 : 0); } // pixel tiles of group wp: consecutive ones, the corner tile in the last group
+    static constexpr int NT = groupTiles(0);   // pixel tiles per wave, at most (WP == 1: all of them)
     static constexpr bool kCorner = TM::kCorner;
     static constexpr int D = NOT >= 2 ? 2 : 4; // steps the A fragments travel ahead (two oc-tiles per wave: 16 registers per step)
     static constexpr int kBufBytes = NPOS16 * C * 2; // one buffer (hi or lo)
     static constexpr int kDump = NPOS16 - 1;
     static constexpr int CS = (NPOS + 1 + 3) & ~3;   // plane stride of the last layer's f32 planes (one spare float: the dump slot)
     static constexpr int kTileBytes = 2 * kBufBytes > C * CS * 4 ? 2 * kBufBytes : C * CS * 4;
-    // x in global memory: accumulator tile (i, j) of wave w as one float4 per lane; the pixel tiles below NTH in the first block, the others in the second
+    // x in global memory: accumulator tile (i, j) of wave w as one float4 per lane; the wave's pixel tiles below NTH in the first block, the others in the second
     static constexpr int NTH = (NT + 1) / 2;
-    static_assert(C % 128 == 0 && NOT * NT <= 12, "one-tile bf16 tower: 128 or 256 hidden channels, at most 12 accumulator tiles per wave");
-    static_assert(KB % D == 0, "the ring's slot of a step is its k-block's");
-    static_assert(16 * NTH <= P, "the per-lane order of x must fit a [C][P] block");
+    static_assert((C == 64 || C % 128 == 0) && NOT * NT <= 12, "one-tile bf16 tower: 64, 128 or 256 hidden channels, at most 12 accumulator tiles per wave");
+    static_assert(WP == 1 || (WP == 2 && groupTiles(1) >= 2), "one or two pixel groups, each with two halves of B fragments");
+    static_assert(KB % D == 0 || 2 * KB == D, "the ring's slot of a step is its k-block's, or (two taps per round) its tap's parity and its k-block's");
+    static_assert(8 * NOT * NTH * 64 * 4 <= C * P, "the per-lane order of x must fit a [C][P] block");
     static_assert(kTileBytes <= 160 * 1024, "the tile must fit the LDS");
 };
 template <int CH>
 __device__ __forceinline__ int actByteW(int pos, int chunk) { return (((pos >> 4) * CH + chunk) * 16 + (pos & 15)) * 16; }
 
-// One conv3x3 layer (KB k-blocks per tap: C / 32, or 1 for the stem, which has no lo input) for the NOT oc-tiles from ot0 and all pixel tiles.
+// One conv3x3 layer (KB k-blocks per tap: C / 32, or 1 for the stem, which has no lo input) for the NOT oc-tiles from ot0 and the wave's NT pixel tiles (px; all
+// of them, or those of its pixel group; CORNER: the last one is the corner tile).
 //   gskip / gkeep: this wave's part of x in global memory (see above), read as the skip values / written for a later layer; nullptr: neither
 //   out_f32: last layer of the simulation kernel, f32 padded planes over the tile; gout: last layer of the stand-alone launch, f32 NCHW
 //   next_wf: the fragments of the layer that follows (C / 32 k-blocks per tap): its first D steps are left in the ring
-template <class G, int KB, bool HAS_LO>
+template <class G, int NT, bool CORNER, int KB, bool HAS_LO>
 __device__ __forceinline__ void wideLayerBf16(LdsByte* tile, GlbF32x4* gskip0, GlbF32x4* gskip1, GlbF32x4* gkeep0, GlbF32x4* gkeep1, bool out_f32, float* __restrict__ gout,
                                               GlbCU32x4* wf, GlbCU32x4* next_wf, GlbCF32x4* bias, int lane, int ot0,
-                                              const PixSetBf16<G::NT>& px, bool have_first, u32x4 (&ring)[G::D][G::NOT][2])
+                                              const PixSetBf16<NT>& px, bool have_first, u32x4 (&ring)[G::D][G::NOT][2])
 {
-    constexpr int NT = G::NT, NOT = G::NOT, D = G::D, OT = G::OT, PW = G::PW, CH = G::CH, KBN = G::KB, NTH = G::NTH;
-    constexpr bool CORNER = G::kCorner;
-    static_assert(KB == 1 || KB % D == 0, "stem or tower layer");
+    constexpr int NOT = G::NOT, D = G::D, OT = G::OT, PW = G::PW, CH = G::CH, KBN = G::KB, NTH = G::NTH;
+    static_assert(KB == 1 || KB == KBN, "stem or tower layer");
+    static_assert(NT <= G::NT && NT - NTH <= NTH, "the wave's part of x: NTH tiles in each block");
     const int kg = lane >> 4;
     const LdsByte* in_hi = tile;
     const LdsByte* in_lo = tile + G::kBufBytes;
@@ -156,7 +165,7 @@ __device__ __forceinline__ void wideLayerBf16(LdsByte* tile, GlbF32x4* gskip0, G
 #pragma unroll
                 for (int i = 0; i < NOT; ++i) { a[i][0] = ring[s % D][i][0]; a[i][1] = ring[s % D][i][1]; }
                 if (s + D < 9) { loadA(ring[s % D], wme + size_t(s + D) * OT * 128, KB); }  // this slot's fragments are in `a` now
-                else if (nme) { loadA(ring[s % D], nme + (s + D - 9) * 128, KBN); }          // the next layer's step s + D - 9 (tap 0)
+                else if (nme) { loadA(ring[s % D], nme + (size_t((s + D - 9) / KBN) * OT * KBN + (s + D - 9) % KBN) * 128, KBN); } // the next layer's step s + D - 9 (its tap, its k-block)
             };
             if (cornerTapInside(s)) { step(std::true_type{}, (s / 3) * PW + s % 3, 0, (sn / 3) * PW + sn % 3, 0, fetch); }
             else { step(std::false_type{}, (s / 3) * PW + s % 3, 0, (sn / 3) * PW + sn % 3, 0, fetch); }
@@ -173,6 +182,41 @@ __device__ __forceinline__ void wideLayerBf16(LdsByte* tile, GlbF32x4* gskip0, G
 #pragma unroll
                 for (int k = 0; k < NOT; ++k) { ring[i][k][0] = tmp[i][k][0]; ring[i][k][1] = tmp[i][k][1]; }
             }
+        }
+    } else if constexpr (KB % D != 0) {
+        // Fewer k-blocks than ring slots (64 channels: KB = 2, D = 4): the ring holds TWO taps.  Step (t, kb) is in slot (t & 1) * KB + kb, which then takes
+        // step (t + 2, kb) — of this layer, of the next one (its tap t + 2 - 9), or, without one, this tap's own again (harmless).  The loop takes the taps in
+        // pairs, so that a slot is a constant, and tap 8 alone; behind it the next layer's step i is in slot (9 * KB + i) % D, as behind the stem.
+        static_assert(2 * KB == D && NOT == 1, "two taps per round of the ring");
+        auto tapSteps = [&](auto odd, int t) {
+            constexpr int S0 = decltype(odd)::value ? KB : 0;
+            const int tn = t < 8 ? t + 1 : 8;
+            const int tapoff = (t / 3) * PW + (t % 3), ntapoff = (tn / 3) * PW + (tn % 3);
+            GlbCU32x4* ahead = t + 2 < 9 ? wme + size_t(t + 2) * OT * KB * 128 : (nme ? nme + size_t(t + 2 - 9) * OT * KB * 128 : wme + size_t(t) * OT * KB * 128);
+            auto steps = [&](auto inside) {
+#pragma unroll
+                for (int kb = 0; kb < KB; ++kb) {
+                    auto fetch = [&](u32x4 (&a)[NOT][2]) {
+                        a[0][0] = ring[S0 + kb][0][0]; a[0][1] = ring[S0 + kb][0][1];
+                        loadA(ring[S0 + kb], ahead + kb * 128, KB);
+                    };
+                    if (kb + 1 < KB) { step(inside, tapoff, kb, tapoff, kb + 1, fetch); } else { step(inside, tapoff, kb, ntapoff, 0, fetch); }
+                }
+            };
+            if (!CORNER || cornerTapInside(t)) { steps(std::true_type{}); } else { steps(std::false_type{}); }
+        };
+#pragma unroll 1
+        for (int t = 0; t < 8; t += 2) {
+            tapSteps(std::false_type{}, t);
+            tapSteps(std::true_type{}, t + 1);
+        }
+        tapSteps(std::false_type{}, 8);
+        if (nme) {
+            u32x4 tmp[D][2];
+#pragma unroll
+            for (int i = 0; i < D; ++i) { tmp[i][0] = ring[(9 * KB + i) % D][0][0]; tmp[i][1] = ring[(9 * KB + i) % D][0][1]; }
+#pragma unroll
+            for (int i = 0; i < D; ++i) { ring[i][0][0] = tmp[i][0]; ring[i][0][1] = tmp[i][1]; }
         }
     } else {
         // one tap: its KB steps; step kb's fragments are in ring slot kb % D, which then takes step kb + D — of this tap, of the next one, or (behind tap 8)
@@ -256,6 +300,37 @@ __device__ __forceinline__ void wideLayerBf16(LdsByte* tile, GlbF32x4* gskip0, G
     }
 }
 
+// All layers for the NOT oc-tiles from ot0 and the NT pixel tiles from tile0 (CORNER: the last of them is the corner tile) on wave `wave`
+template <class G, int H, int W, int NT, bool CORNER>
+__device__ __forceinline__ void towerRunBf16Wide(LdsByte* lt, const uint4* __restrict__ wfrag, const float* __restrict__ params, const TowerArgsBf16& ta, float* __restrict__ gx,
+                                                 float* __restrict__ gt, bool out_f32, float* __restrict__ gout, int lane, int wave, int ot0, int tile0)
+{
+    constexpr int PW = G::PW;
+    PixSetBf16<NT> px;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        px.q[j] = kTileMap<H, W>.q[(tile0 + j) * 16 + (lane & 15)];
+        const int q = px.q[j] < 0 ? 0 : px.q[j];
+        px.src[j] = (q / W) * PW + (q % W);
+        px.dst[j] = px.q[j] < 0 ? G::kDump : (q / W + 1) * PW + (q % W) + 1;
+    }
+    GlbF32x4* k0 = (GlbF32x4*)gx + size_t(wave) * G::NOT * G::NTH * 64; // the wave's part of x
+    GlbF32x4* k1 = (GlbF32x4*)gt + size_t(wave) * G::NOT * G::NTH * 64;
+    GlbCU32x4* wfr = (GlbCU32x4*)wfrag;
+    GlbCF32x4* par4 = (GlbCF32x4*)params; // (bias offsets are multiples of 4 floats: the blob's arrays are 16-byte aligned)
+    u32x4 ring[G::D][G::NOT][2];
+    // stem: planes -> x (kept for the first block's skip)
+    wideLayerBf16<G, NT, CORNER, 1, false>(lt, nullptr, nullptr, k0, k1, false, nullptr, wfr + ta.w_off[0], wfr + ta.w_off[1], par4 + ta.b_off[0] / 4, lane, ot0, px, false, ring);
+    __syncthreads();
+#pragma unroll 1
+    for (int l = 1; l < ta.nlayers; ++l) { // residual blocks: t = relu(conv1(x)); x = relu(conv2(t) + x)
+        const bool second = ((l - 1) & 1) != 0, last = l + 1 == ta.nlayers, keep = second && !last;
+        wideLayerBf16<G, NT, CORNER, G::KB, true>(lt, second ? k0 : nullptr, second ? k1 : nullptr, keep ? k0 : nullptr, keep ? k1 : nullptr, last && out_f32, last ? gout : nullptr,
+                                                  wfr + ta.w_off[l], last ? nullptr : wfr + ta.w_off[l + 1], par4 + ta.b_off[l] / 4, lane, ot0, px, true, ring);
+        __syncthreads();
+    }
+}
+
 // The body for sample `b`, run by all 512 threads of a workgroup: input = bit-packed planes (cin0 <= 32 channels).  `tile` = Bf16WideGeo::kTileBytes of LDS;
 // gx, gt = this workgroup's two blocks of C x P floats in global memory.  out != nullptr: the last activations as f32 NCHW to out + b * C * P; else they stay
 // in the tile as f32 padded planes (channel stride Bf16WideGeo::CS, row stride W + 2), whose pointer is returned.
@@ -264,7 +339,7 @@ __device__ __forceinline__ float* towerBodyBf16Wide(const unsigned* __restrict__
                                                     const TowerArgsBf16& ta, float* __restrict__ gx, float* __restrict__ gt, float* __restrict__ out, int b, int tid, char* tile)
 {
     using G = Bf16WideGeo<H, W, C>;
-    constexpr int P = G::P, PW = G::PW, W32 = (P + 31) / 32, NT = G::NT;
+    constexpr int P = G::P, PW = G::PW, W32 = (P + 31) / 32;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     LdsByte* lt = (LdsByte*)tile;
     for (int i = tid; i < 2 * G::kBufBytes / 16; i += 512) { ((__attribute__((address_space(3))) u32x4*)lt)[i] = u32x4{0, 0, 0, 0}; }
@@ -280,30 +355,13 @@ __device__ __forceinline__ float* towerBodyBf16Wide(const unsigned* __restrict__
         }
     }
     __syncthreads();
-    PixSetBf16<NT> px;
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        px.q[j] = kTileMap<H, W>.q[j * 16 + (lane & 15)];
-        const int q = px.q[j] < 0 ? 0 : px.q[j];
-        px.src[j] = (q / W) * PW + (q % W);
-        px.dst[j] = px.q[j] < 0 ? G::kDump : (q / W + 1) * PW + (q % W) + 1;
-    }
-    const int ot0 = wave * G::NOT;
-    GlbF32x4* k0 = (GlbF32x4*)gx + size_t(wave) * G::NOT * G::NTH * 64;
-    GlbF32x4* k1 = (GlbF32x4*)gt + size_t(wave) * G::NOT * G::NTH * 64;
-    GlbCU32x4* wfr = (GlbCU32x4*)wfrag;
-    GlbCF32x4* par4 = (GlbCF32x4*)params; // (bias offsets are multiples of 4 floats: the blob's arrays are 16-byte aligned)
     float* gout = out ? out + size_t(b) * C * P : nullptr;
-    u32x4 ring[G::D][G::NOT][2];
-    // stem: planes -> x (kept for the first block's skip)
-    wideLayerBf16<G, 1, false>(lt, nullptr, nullptr, k0, k1, false, nullptr, wfr + ta.w_off[0], wfr + ta.w_off[1], par4 + ta.b_off[0] / 4, lane, ot0, px, false, ring);
-    __syncthreads();
-#pragma unroll 1
-    for (int l = 1; l < ta.nlayers; ++l) { // residual blocks: t = relu(conv1(x)); x = relu(conv2(t) + x)
-        const bool second = ((l - 1) & 1) != 0, last = l + 1 == ta.nlayers, keep = second && !last;
-        wideLayerBf16<G, G::KB, true>(lt, second ? k0 : nullptr, second ? k1 : nullptr, keep ? k0 : nullptr, keep ? k1 : nullptr, last && !out, last ? gout : nullptr,
-                                      wfr + ta.w_off[l], last ? nullptr : wfr + ta.w_off[l + 1], par4 + ta.b_off[l] / 4, lane, ot0, px, true, ring);
-        __syncthreads();
+    if constexpr (G::WP == 1) { // wave w: the NOT oc-tiles from w * NOT, all pixel tiles
+        towerRunBf16Wide<G, H, W, G::NT, G::kCorner>(lt, wfrag, params, ta, gx, gt, !out, gout, lane, wave, wave * G::NOT, 0);
+    } else { // wave w: oc-tile w % WO, pixel group w / WO (the same number of barriers on either side)
+        const int ot0 = (wave % G::WO) * G::NOT;
+        if (wave < G::WO) { towerRunBf16Wide<G, H, W, G::groupTiles(0), false>(lt, wfrag, params, ta, gx, gt, !out, gout, lane, wave, ot0, 0); }
+        else { towerRunBf16Wide<G, H, W, G::groupTiles(1), G::kCorner>(lt, wfrag, params, ta, gx, gt, !out, gout, lane, wave, ot0, G::groupTiles(0)); }
     }
     return reinterpret_cast<float*>(tile);
 }

@@ -151,7 +151,7 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
 }
 
 // The parts, listed once: part n is simWideLaunchPart<n>, defined by the translation unit built with MZ_SIM_WIDE_PART == n and tried in this order (sim_wide_a.hip)
-#define MZ_SIM_WIDE_PARTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9)
+#define MZ_SIM_WIDE_PARTS(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12)
 #define MZ_SIM_WIDE_FN(n) simWideLaunchPart##n
 #define MZ_SIM_WIDE_SIG(n)                                                                                                                                                    \
     bool MZ_SIM_WIDE_FN(n)(int H, int W, int c0q, int C, int cpl, int prec, const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds, \
@@ -159,7 +159,7 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
 #define MZ_SIM_WIDE_SIG_OF(n) MZ_SIM_WIDE_SIG(n) // (expands MZ_SIM_WIDE_PART before it is pasted)
 
 // instances by part: (H, W, input channels of the stem padded to 16, hidden channels, the rules argument: game_kind.h rulesArg); prec: Net::precision() — the
-// parts of sim_kernel_wide hold the f32 tower's instances, parts 6 and 7 (sim_wide_bf16.inc) those of sim_kernel_wide_bf16
+// parts of sim_kernel_wide hold the f32 tower's instances, parts 6, 7 and 10 to 12 (sim_wide_bf16.inc) those of sim_kernel_wide_bf16
 #if MZ_SIM_WIDE_PART == 0
 #define MZ_SIM_WIDE_PART_CASES(X) X(9, 9, 32, 128, 2) X(9, 9, 32, 32, 2) X(7, 7, 32, 128, 1) X(13, 13, 32, 64, 3)
 #elif MZ_SIM_WIDE_PART == 1
@@ -176,7 +176,7 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
 #define MZ_SIM_WIDE_PART_CASES(X) X(9, 9, 32, 256, kRulesNoGo) X(9, 9, 32, 128, kRulesNoGo) X(9, 9, 32, 32, kRulesNoGo)
 #elif MZ_SIM_WIDE_PART == 9 // Havannah (a game past the rows: game_kind.h): edge size 8 on its 15x15 array with 64 channels (measured) and 32, edge size 4 (7x7) with 32 (tests); 20 planes pad to 32
 #define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 32, 64, kRulesHavannah) X(15, 15, 32, 32, kRulesHavannah) X(7, 7, 32, 32, kRulesHavannah)
-#elif MZ_SIM_WIDE_PART == 6 || MZ_SIM_WIDE_PART == 7 // the bf16x3 tower: sim_wide_bf16.inc defines the kernel, its instances and the part's function
+#elif MZ_SIM_WIDE_PART == 6 || MZ_SIM_WIDE_PART == 7 || (MZ_SIM_WIDE_PART >= 10 && MZ_SIM_WIDE_PART <= 12) // the bf16x3 tower: sim_wide_bf16.inc defines the kernel, its instances and the part's function
 #else
 #error "MZ_SIM_WIDE_PART: not one of MZ_SIM_WIDE_PARTS"
 #endif

@@ -1,6 +1,6 @@
-// sim_kernel_wide_bf16 — sim_kernel_wide (sim_wide.inc) with the opt-in bf16x3 tower of net_bf16_wide_body.h: 9x9 Go AlphaZero with 128 / 256 hidden channels
-// under `mz_nn_precision=bf16x3`.  Every tree phase is the one sim_kernel and sim_kernel_wide run; the LDS plan is sim_kernel_wide's (lf; Net::simWidePlan) around
-// another tile: the tower's hi / lo buffers (64 KB at 128 channels, 128 KB at 256), over which the last layer leaves the f32 planes the heads read.  The tower
+// sim_kernel_wide_bf16 — sim_kernel_wide (sim_wide.inc) with the opt-in bf16x3 tower of net_bf16_wide_body.h: 9x9 Go AlphaZero with 128 / 256 hidden channels,
+// Gomoku 15x15, Hex 11x11 and Havannah 15x15 with 64 under `mz_nn_precision=bf16x3`.  Every tree phase is the one sim_kernel and sim_kernel_wide run; the LDS plan is sim_kernel_wide's (lf; Net::simWidePlan) around
+// another tile: the tower's hi / lo buffers (64 KB at 128 channels, 128 KB at 256; 44 KB at 11x11 x 64 and 76 KB at 15x15 x 64, the f32 tiles' sizes), over which the last layer leaves the f32 planes the heads read.  The tower
 // body is the stand-alone launch's (net_bf16_wide.hip) — same code, same order, same bits: the lock-step mode on the bf16x3 tower writes the same records.
 // A kernel of its own, not a template parameter of sim_kernel_wide: the f32 kernels keep their names and their code.
 #include "sim_wide.inc"
@@ -53,20 +53,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     }
     float* next = xchg + ((simXchgWordsDev(a->gv.A, a->gv.channels, a->gv.W32) + 1) & ~1);
     const uint64_t* seen_lds = nullptr;
-    if (lf & 2) {
-        uint64_t* sw = reinterpret_cast<uint64_t*>(next);
-        for (int i = tid; i < kGoSeenCap; i += 512) { sw[i] = a->gv.snap[g].seen[i]; }
-        __syncthreads();
-        seen_lds = sw;
-        next = reinterpret_cast<float*>(sw + kGoSeenCap);
+    if constexpr (CPL > 0) { // (the superko table and the leaf's block are Go's)
+        if (lf & 2) {
+            uint64_t* sw = reinterpret_cast<uint64_t*>(next);
+            for (int i = tid; i < kGoSeenCap; i += 512) { sw[i] = a->gv.snap[g].seen[i]; }
+            __syncthreads();
+            seen_lds = sw;
+            next = reinterpret_cast<float*>(sw + kGoSeenCap);
+        }
     }
     uint64_t* leaf_smem = nullptr;
-    if ((lf & 4) && !(a->no_spec & 8)) {
-        leaf_smem = reinterpret_cast<uint64_t*>(next);
-        uint64_t* zk = leaf_smem + goLeafKeyWord(a->gv.Ppad, a->gv.W, a->pv.max_depth); // the block's copy of the Zobrist keys (go_body.h)
-        for (int i = tid; i < 2 * a->gv.P; i += 512) { zk[i] = a->gv.key[i]; }
-        __syncthreads();
-        next = reinterpret_cast<float*>(zk + 2 * a->gv.P); // (goLeafSmemBytes: the body's arrays, then the keys)
+    if constexpr (CPL > 0) {
+        if ((lf & 4) && !(a->no_spec & 8)) {
+            leaf_smem = reinterpret_cast<uint64_t*>(next);
+            uint64_t* zk = leaf_smem + goLeafKeyWord(a->gv.Ppad, a->gv.W, a->pv.max_depth); // the block's copy of the Zobrist keys (go_body.h)
+            for (int i = tid; i < 2 * a->gv.P; i += 512) { zk[i] = a->gv.key[i]; }
+            __syncthreads();
+            next = reinterpret_cast<float*>(zk + 2 * a->gv.P); // (goLeafSmemBytes: the body's arrays, then the keys)
+        }
     }
     float* const hscr = next; // the heads' scratch: (PC * P + P + VH + A + 16) floats
     unsigned long long* prof = a->prof ? a->prof + size_t(g) * 8 : nullptr;
@@ -88,9 +92,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         }
         __syncthreads();
         const bool term = simLeafTerminal(a, xchg); // a terminal leaf: no planes, tower and heads; the same barriers for every wave either way
-        if (!term) {
-            simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
-            __syncthreads();
+        if constexpr (CPL > 0) { // (the other games' leaf bodies write their planes themselves: sim_wide.inc)
+            if (!term) {
+                simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
+                __syncthreads();
+            }
         }
         if (prof) { t1 = wall_clock64(); }
         const float* xt = nullptr;
