@@ -163,10 +163,44 @@ static_assert((kSpecWays & (kSpecWays - 1)) == 0 && kSpecWays >= 2 && kSpecWays 
 constexpr int kHelpSegs = 3;                                    // helper waves / segments of kLv levels behind the first
 constexpr int kHelpHdr = 16;                                    // [0] serial of the simulation the block belongs to, [2] entry node, [3] levels accepted, [4..9] header of the last chosen node + the node
 constexpr int kHelpSeg = kHelpHdr + 4 * kLv;                    // + per accepted level: chosen node, its action, first_child, num_children
-constexpr int kSpecHelp = kSpecWays * kSpecWay + 8;
-constexpr int kSpecWords = kSpecHelp + kHelpSegs * kHelpSeg;    // the paths + [kSpecWays * kSpecWay] = the next one to replace; [+1] passes, [+3] walks that found their path, [+5] levels taken, [+6] the way of the last walk, [+7] levels taken over from helpers; the helpers' blocks
+// behind the kSpecWays paths: eight words of the walk's state and counters, then the helpers' blocks
+enum : int {
+    kSpecNext = kSpecWays * kSpecWay, // the way to replace next
+    kSpecPasses = kSpecNext + 1,      // passes of the speculation
+    kSpecFound = kSpecNext + 3,       // walks that found their path
+    kSpecLevels = kSpecNext + 5,      // levels taken
+    kSpecLastWay = kSpecNext + 6,     // the way of the last walk
+    kSpecHelped = kSpecNext + 7,      // levels taken over from helpers
+    kSpecHelp = kSpecNext + 8,        // the helpers' blocks
+};
+constexpr int kSpecWords = kSpecHelp + kHelpSegs * kHelpSeg;
 constexpr int kSpecNode = 4, kSpecFc = 4 + kSpecCap, kSpecNc = 4 + 2 * kSpecCap;
 struct SpecMem { LdsI32* w; LdsCFloat* bias; LdsCDbl* sqrt; }; // w == nullptr: no speculation
+
+// The speculation memory as a kernel stages it, behind its reciprocal table (rcp_n doubles at rcp_w): the sqrt and bias tables (rcp_n - 2 entries each), then the
+// kSpecWords words.  specStage lays the three out, copies the tables and clears the paths' lengths, the eight words behind them and the helpers' serials.  No
+// barrier in here: the kernel's own barrier stands between this and the first walk.  (sim_kernel, sim_kernel_mz and sim_kernel_mz_cluster spell the same layout out:
+// at their register limit the inlined helper makes the compiler allocate them another way.)
+struct SpecStage {
+    double* sqrt_w;
+    float* bias_w;
+    int* spec_w;
+    __device__ __forceinline__ SpecMem mem(bool walk) const { return SpecMem{walk ? (LdsI32*)spec_w : nullptr, (LdsCFloat*)bias_w, (LdsCDbl*)sqrt_w}; } // walk == false: the tables alone
+    __device__ __forceinline__ float* end() const { return reinterpret_cast<float*>(spec_w + kSpecWords); }
+};
+template <class View>
+__device__ __forceinline__ SpecStage specStage(const View& pv, double* rcp_w, int rcp_n, int tid)
+{
+    const int tab_n = rcp_n - 2;
+    double* sqrt_w = rcp_w + rcp_n;
+    float* bias_w = reinterpret_cast<float*>(sqrt_w + tab_n);
+    int* spec_w = reinterpret_cast<int*>(bias_w + tab_n + (tab_n & 1));
+    for (int i = tid; i < tab_n; i += 512) { sqrt_w[i] = pv.sqrt_tab[i]; bias_w[i] = pv.bias_tab[i]; }
+    if (tid < kSpecWays) { spec_w[tid * kSpecWay] = 0; }
+    if (tid < 8) { spec_w[kSpecNext + tid] = 0; }
+    if (tid < kHelpSegs) { spec_w[kSpecHelp + tid * kHelpSeg] = 0; }
+    return SpecStage{sqrt_w, bias_w, spec_w};
+}
 
 // The walk beside the previous simulation's expand (JOIN, the value-first order of sim_az_body.h): the backup is done, the expand may still run.  Of what the walk
 // reads, the expand only writes the second half of the record of ITS leaf (first_child, num_children, players) and the children behind it, so the walk waits where it
@@ -202,13 +236,13 @@ __device__ __forceinline__ void selectBody(const PoolView& v, const int* __restr
             int way;
             if (m != 0) {
                 way = static_cast<int>(__builtin_ctzll(m));
-                if (lane == 0) { sm.w[kSpecWays * kSpecWay + 3] += 1; }
+                if (lane == 0) { sm.w[kSpecFound] += 1; }
             } else {
-                way = __builtin_amdgcn_readfirstlane(sm.w[kSpecWays * kSpecWay]) & (kSpecWays - 1);
-                if (lane == 0) { sm.w[kSpecWays * kSpecWay] = way + 1; sm.w[way * kSpecWay] = 0; }
+                way = __builtin_amdgcn_readfirstlane(sm.w[kSpecNext]) & (kSpecWays - 1);
+                if (lane == 0) { sm.w[kSpecNext] = way + 1; sm.w[way * kSpecWay] = 0; }
             }
             spec = sm.w + way * kSpecWay;
-            if (lane == 0) { sm.w[kSpecWays * kSpecWay + 6] = way; } // (the helpers of the NEXT walk follow this path)
+            if (lane == 0) { sm.w[kSpecLastWay] = way; } // (the helpers of the NEXT walk follow this path)
         }
         if (spec && lane == 0 && d < kSpecCap) {
             spec[kSpecNode + d] = n;
@@ -320,7 +354,7 @@ __device__ __forceinline__ void selectBody(const PoolView& v, const int* __restr
                             cur.players = __builtin_amdgcn_readfirstlane(h[8]);
                             node = __builtin_amdgcn_readfirstlane(h[9]);
                             depth += hadv;
-                            if (lane == 0) { sm.w[kSpecWays * kSpecWay + 7] += hadv; }
+                            if (lane == 0) { sm.w[kSpecHelped] += hadv; }
                             continue;
                         }
                     }
@@ -426,7 +460,7 @@ __device__ __forceinline__ void selectBody(const PoolView& v, const int* __restr
                             node = laneI(chosen, l);
                             depth += adv;
                         }
-                        if (lane == 0) { sm.w[kSpecWays * kSpecWay + 1] += 1; sm.w[kSpecWays * kSpecWay + 5] += adv; }
+                        if (lane == 0) { sm.w[kSpecPasses] += 1; sm.w[kSpecLevels] += adv; }
                         if (adv > 0) { continue; }
                     }
                 }
@@ -615,7 +649,7 @@ __device__ __forceinline__ void selectSpecHelper(const PoolView& v, int g, int l
 {
     if (!sm.w || v.atari_init_q || v.value_rescale || seg < 1 || seg > kHelpSegs) { return; }
     LdsI32* out = sm.w + kSpecHelp + (seg - 1) * kHelpSeg;
-    const int way = __builtin_amdgcn_readfirstlane(sm.w[kSpecWays * kSpecWay + 6]) & (kSpecWays - 1);
+    const int way = __builtin_amdgcn_readfirstlane(sm.w[kSpecLastWay]) & (kSpecWays - 1);
     LdsI32* spec = sm.w + way * kSpecWay;
     const int plen = __builtin_amdgcn_readfirstlane(spec[0]);
     const int L0 = 1 + seg * kLv, depth = L0 + 1; // the entry node's level / the path index of the first chosen node

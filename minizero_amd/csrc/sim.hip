@@ -18,7 +18,8 @@ __global__ __launch_bounds__(512) void sim_kernel_mz(const SimArgs* __restrict__
     const int rcp_n = a->rcp_n;
     for (int i = tid; i < rcp_n; i += 512) { rcp_w[i] = a->pv.rcp_tab[i]; }
     LdsCDouble* rcp_lds = (LdsCDouble*)rcp_w; // (one barrier for everything the launch keeps in LDS, below: three in a row cost every launch ~2 us, and a move of BASELINE configs[4] has thirteen)
-    // path-speculation memory of the walk (pool_body.h): LDS copies of the sqrt / bias tables + the remembered paths
+    // path-speculation memory of the walk (pool_body.h): LDS copies of the sqrt / bias tables + the remembered paths.  specStage's layout spelled out: with the
+    // helper inlined here the 12 / 8-channel instance, at its 256 registers, allocates them another way and spills 16 bytes more
     const int tab_n = rcp_n - 2;
     double* sqrt_w = rcp_w + rcp_n;
     float* bias_w = reinterpret_cast<float*>(sqrt_w + tab_n);
@@ -26,7 +27,7 @@ __global__ __launch_bounds__(512) void sim_kernel_mz(const SimArgs* __restrict__
     for (int i = tid; i < tab_n; i += 512) { sqrt_w[i] = a->pv.sqrt_tab[i]; bias_w[i] = a->pv.bias_tab[i]; }
     if (!a->atari) { // (muzero_atari walks without path speculation: its memory holds the path block and the Gumbel state filled below, before the same barrier)
         if (tid < kSpecWays) { spec_w[tid * kSpecWay] = 0; }
-        if (tid < 8) { spec_w[kSpecWays * kSpecWay + tid] = 0; }
+        if (tid < 8) { spec_w[kSpecNext + tid] = 0; }
         if (tid < kHelpSegs) { spec_w[kSpecHelp + tid * kHelpSeg] = 0; }
     }
     SpecMem spec{((a->no_spec & 1) || a->atari) ? nullptr : (LdsI32*)spec_w, (LdsCFloat*)bias_w, (LdsCDbl*)sqrt_w};
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(512) void sim_kernel_mz(const SimArgs* __restrict__
         __syncthreads();
         if (prof && tid == 0 && !given) {
             const unsigned long long t4 = wall_clock64();
-            prof[0] += t1 - t0; prof[1] += t2 - t1; prof[2] += t3 - t2; prof[3] += t4 - t3; prof[4] += 1;
+            simProfSim(prof, t0, t1, t2, t3, t4);
         }
     }
     if (lds_path && tid == 0) { a->pv.num_nodes[g] = lds_path[2 * a->pv.max_depth + 1]; }

@@ -532,6 +532,22 @@ __device__ __forceinline__ void simProfExit(unsigned long long* tail)
     atomicAdd(tail + 3, t);
     atomicAdd(tail + 5, 1ull);
 }
+// One simulation into the game's counters: [0] select + leaf, [1] tower, [2] heads, [3] cand + expand ticks, [4] simulations | (<< 32) those whose network
+// evaluation was skipped.  term: a terminal leaf — its second half, alone where the heads would be, counts as leaf time: "tower" and "heads" only hold
+// simulations that ran them
+__device__ __forceinline__ void simProfSim(unsigned long long* prof, unsigned long long t0, unsigned long long t1, unsigned long long t2, unsigned long long t3, unsigned long long t4,
+                                           bool term = false)
+{
+    prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
+    prof[4] += 1 + (static_cast<unsigned long long>(term) << 32);
+}
+// The end of a launch: the walk's speculation counters (pool_body.h) into [7] = passes << 40 | levels taken << 20 | walks that found their path, and
+// [6] += levels taken over from the helper waves << 40 (the low bits hold the path lengths)
+__device__ __forceinline__ void simProfSpec(unsigned long long* prof, const int* spec_w)
+{
+    prof[7] += (static_cast<unsigned long long>(spec_w[kSpecPasses]) << 40) | (static_cast<unsigned long long>(spec_w[kSpecLevels]) << 20) | spec_w[kSpecFound];
+    prof[6] += static_cast<unsigned long long>(spec_w[kSpecHelped]) << 40;
+}
 
 // 8x8 boards: three tower tiles are 80 KB of LDS, so TWO games share a CU (16 waves) if the kernel stays within 128 VGPRs: one game's
 // tree phases and barrier bubbles are filled by the other's tower
@@ -883,13 +899,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
     const int path_words = 2 * a->pv.max_depth + 2;
     float* xchg = reinterpret_cast<float*>(rcp_w + a->rcp_n) + path_words;
     if constexpr (WPE == 2) {
+        // (pool_body.h specStage's layout, spelled out: with the helper inlined the compiler allocates this kernel's registers, which are at their limit, another
+        //  way — the same counts, 799 other lines in the 9x9 x 64 instance — and this is the kernel bench.py measures)
         const int tab_n = a->rcp_n - 2;
         double* sqrt_w = rcp_w + a->rcp_n;
         float* bias_w = reinterpret_cast<float*>(sqrt_w + tab_n);
         spec_w = reinterpret_cast<int*>(bias_w + tab_n + (tab_n & 1));
         for (int i = tid; i < tab_n; i += 512) { sqrt_w[i] = a->pv.sqrt_tab[i]; bias_w[i] = a->pv.bias_tab[i]; }
         if (tid < kSpecWays) { spec_w[tid * kSpecWay] = 0; }
-        if (tid < 8) { spec_w[kSpecWays * kSpecWay + tid] = 0; }
+        if (tid < 8) { spec_w[kSpecNext + tid] = 0; }
         if (tid < kHelpSegs) { spec_w[kSpecHelp + tid * kHelpSeg] = 0; }
         __syncthreads();
         spec = SpecMem{(a->no_spec & 1) ? nullptr : (LdsI32*)spec_w, (LdsCFloat*)bias_w, (LdsCDbl*)sqrt_w};
@@ -1075,8 +1093,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
                     vfPublish((LdsI32*)s_help + kVfBackup, s + 1, lane);
                     if (prof && tid == 0) {
                         t4 = wall_clock64(); // ("cand+expand": what is exposed between the heads and the next walk)
-                        prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
-                        prof[4] += 1 + (static_cast<unsigned long long>(term) << 32);
+                        simProfSim(prof, t0, t1, t2, t3, t4, term);
                         if (pair && !lent && !term) { pair_n += 1; pair_t += t2 - t1; }
                         if (quad && !term) { quad_n += 1; quad_t += t2 - t1; }
                         if (lent && !term) { lent_n += 1; lent_t += t2 - t1; }
@@ -1119,9 +1136,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         __syncthreads();
         if (prof && tid == 0) {
             t4 = wall_clock64();
-            // (a terminal leaf's second half, alone where the heads would be, counts as leaf time: "tower" and "heads" only hold simulations that ran them)
-            prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
-            prof[4] += 1 + (static_cast<unsigned long long>(term) << 32); // simulations | those whose network evaluation was skipped
+            simProfSim(prof, t0, t1, t2, t3, t4, term);
             if (pair && !term) { pair_n += 1; pair_t += t2 - t1; }
             if (quad && !term) { quad_n += 1; quad_t += t2 - t1; }
             if constexpr (kAhead) { if (heads_w && !term) { ahead_n += 1; } }
@@ -1152,10 +1167,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(simWavesPer
         if (pair_n) { atomicAdd(a->prof + size_t(games) * 8 + 13, pair_n); atomicAdd(a->prof + size_t(games) * 8 + 14, pair_t); }
         if (quad_n) { atomicAdd(a->prof + size_t(games) * 8 + 21, quad_n); atomicAdd(a->prof + size_t(games) * 8 + 22, quad_t); atomicAdd(a->prof + size_t(games) * 8 + 23, pair_n ? 1ull : 0ull); }
     }
-    if (prof && tid == 0 && spec_w) {
-        prof[7] += (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 1]) << 40) | (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 5]) << 20) | spec_w[kSpecWays * kSpecWay + 3];
-        prof[6] += static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 7]) << 40; // levels taken over from the helper waves (the low bits hold the path lengths)
-    }
+    if (prof && tid == 0 && spec_w) { simProfSpec(prof, spec_w); }
     if constexpr (kHelp) {
         // this game is done and its results are written: the CU helps the stragglers of its XCD with their towers instead of idling to the end of the launch
         if (help_on) {

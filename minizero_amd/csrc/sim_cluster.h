@@ -432,7 +432,7 @@ __global__ __launch_bounds__(512) void sim_kernel_mz_cluster(const SimArgs* __re
     __shared__ int s_abort, s_cmd[4], s_cand_k; // s_cmd: parent slot, action, leaf evaluated ahead (simPreProbe)
     double* rcp_w = reinterpret_cast<double*>(tiles + kTileFloats);
     const int rcp_n = a->rcp_n;
-    const int tab_n = rcp_n - 2;
+    const int tab_n = rcp_n - 2; // (pool_body.h specStage's layout; not the helper: only the owner copies the tables, and it walks without path speculation, so nothing is cleared)
     double* sqrt_w = rcp_w + rcp_n;
     float* bias_w = reinterpret_cast<float*>(sqrt_w + tab_n);
     int* spec_w = reinterpret_cast<int*>(bias_w + tab_n + (tab_n & 1));
@@ -577,7 +577,7 @@ __global__ __launch_bounds__(512) void sim_kernel_mz_cluster(const SimArgs* __re
         MZ_HPROF(13);
         if (prof && tid == 0) {
             const unsigned long long t4 = wall_clock64();
-            prof[0] += t1 - t0; prof[1] += t2 - t1; prof[2] += t3 - t2; prof[3] += t4 - t3; prof[4] += 1;
+            simProfSim(prof, t0, t1, t2, t3, t4);
         }
     }
 }

@@ -1,12 +1,18 @@
-// sim_kernel_wide — the per-game simulation kernel (sim_az_body.h sim_kernel: one workgroup per game runs whole simulations — walk, Go leaf, tower, heads,
-// candidates, expand + backup) on the ONE-TILE tower of net_wide_body.h, for the AlphaZero shapes whose two activation tiles do not fit the LDS:
-// 128 / 256 hidden channels (the reference's default network: 1 block x 256 channels, config/configuration.cpp:70-72) and 7x7 / 13x13 / 19x19 Go
-// (go_unit.h:11).  Every phase function is the one sim_kernel runs (same bits); what differs is where things live:
+// sim_kernel_wide, sim_kernel_wide_bf16 — the per-game simulation kernel (sim_az_body.h sim_kernel: one workgroup per game runs whole simulations — walk, leaf,
+// tower, heads, candidates, expand + backup) on a ONE-TILE tower, for the AlphaZero shapes whose two activation tiles do not fit the LDS: 128 / 256 hidden channels
+// (the reference's default network: 1 block x 256 channels, config/configuration.cpp:70-72), 7x7 / 13x13 / 19x19 Go (go_unit.h:11) and the board games' 11x11 and
+// 15x15 boards.  Every phase function is the one sim_kernel runs (same bits); what differs is where things live:
 //   LDS: [ the tower's tile — the tree phases' scratch while no tower runs ] [ reciprocal table ] [ sqrt / bias tables + path-speculation memory: if they fit ]
 //        [ the simulation's path | the phases' hand-over block ] [ root superko table: if it fits ] [ the leaf's block beside the heads: if it fits ] [ heads scratch ]
 //   global: the tower's two per-game activation blocks (SimArgs::act, act2; L2-resident).
 // The heads cannot take their scratch from a tile here (the only tile holds the activations they read): it is a block of its own.
-// Compiled in parts (sim_wide_a.hip ...: MZ_SIM_WIDE_PART selects the instances) so that make builds them side by side.
+// One frame (simWideFrame) is the body of both kernels; a tower policy says what differs between them — the tile's size, the strides the heads read with and the
+// tower function, which stays a function of its own with its own register budget:
+//   WideTowerF32   the f32 tower of net_wide_body.h: the tile is wideTileFloats floats
+//   WideTowerBf16  (sim_wide_bf16.inc) the opt-in bf16x3 tower of net_bf16_wide_body.h: the tile holds the tower's hi / lo buffers (64 KB at 128 channels, 128 KB at
+//                  256; 44 KB at 11x11 x 64 and 76 KB at 15x15 x 64, the f32 tiles' sizes), over which the last layer leaves the f32 planes the heads read
+// Two __global__ functions, not one with the policy as a parameter: the kernels keep their names.
+// Compiled in parts (sim_wide_a.hip ...: each defines MZ_SIM_WIDE_PART, its number, and MZ_SIM_WIDE_CASES, its instances) so that make builds them side by side.
 #include "sim_az_body.h"
 #include "net_wide_body.h"
 
@@ -22,19 +28,24 @@ __device__ __noinline__ const float* simTowerWide(CSimArgs* __restrict__ a, int 
                                          tile, true);
 }
 
+template <int H, int W, int CIN0Q, int C>
+struct WideTowerF32 {
+    static constexpr int kPrec = 0; // Net::precision()
+    static constexpr int kTileFloats = int(wideTileFloats<H, W, C>(CIN0Q));
+    static constexpr int CS = WideGeo<H, W, C>::CS, PW = WideGeo<H, W, C>::PW;
+    static __device__ __forceinline__ const float* run(CSimArgs* __restrict__ a, int g, int tid, float* tile, float* xchg) { return simTowerWide<H, W, CIN0Q, C>(a, g, tid, tile, xchg); }
+};
+
 // lf: bit 0 = path speculation of the walk (+ its LDS tables), bit 1 = the root's superko table in LDS, bit 2 = the second half of the Go leaf beside the heads
-template <int H, int W, int CIN0Q, int C, int CPL>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) void sim_kernel_wide(const SimArgs* __restrict__ a_, const uint8_t* __restrict__ rot_tab, int sim0,
-                                                                                                  int nsims, int host_start, int lf)
+template <int H, int W, int CPL, class Tower>
+__device__ __forceinline__ void simWideFrame(const SimArgs* a_, const uint8_t* rot_tab, int sim0, int nsims, int host_start, int lf)
 {
-    using G = WideGeo<H, W, C>;
     CSimArgs* a = (CSimArgs*)a_;
     extern __shared__ __attribute__((aligned(16))) float tiles[];
     const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int games = gridDim.x;
     constexpr int WPE = 2;
-    constexpr int kTileFloats = int(wideTileFloats<H, W, C>(CIN0Q));
-    double* rcp_w = reinterpret_cast<double*>(tiles + kTileFloats);
+    double* rcp_w = reinterpret_cast<double*>(tiles + Tower::kTileFloats);
     for (int i = tid; i < a->rcp_n; i += 512) { rcp_w[i] = a->pv.rcp_tab[i]; }
     __syncthreads();
     LdsCDouble* rcp_lds = (LdsCDouble*)rcp_w;
@@ -43,21 +54,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     const int path_words = 2 * a->pv.max_depth + 2;
     float* xchg = reinterpret_cast<float*>(rcp_w + a->rcp_n) + path_words;
     if (lf & 1) {
-        const int tab_n = a->rcp_n - 2;
-        double* sqrt_w = rcp_w + a->rcp_n;
-        float* bias_w = reinterpret_cast<float*>(sqrt_w + tab_n);
-        spec_w = reinterpret_cast<int*>(bias_w + tab_n + (tab_n & 1));
-        for (int i = tid; i < tab_n; i += 512) { sqrt_w[i] = a->pv.sqrt_tab[i]; bias_w[i] = a->pv.bias_tab[i]; }
-        if (tid < kSpecWays) { spec_w[tid * kSpecWay] = 0; }
-        if (tid < 8) { spec_w[kSpecWays * kSpecWay + tid] = 0; }
-        if (tid < kHelpSegs) { spec_w[kSpecHelp + tid * kHelpSeg] = 0; }
+        const SpecStage st = specStage(a->pv, rcp_w, a->rcp_n, tid);
         __syncthreads();
-        spec = SpecMem{(a->no_spec & 1) ? nullptr : (LdsI32*)spec_w, (LdsCFloat*)bias_w, (LdsCDbl*)sqrt_w};
-        xchg = reinterpret_cast<float*>(spec_w + kSpecWords) + path_words;
+        spec_w = st.spec_w;
+        spec = st.mem(!(a->no_spec & 1));
+        xchg = st.end() + path_words;
     }
     float* next = xchg + ((simXchgWordsDev(a->gv.A, a->gv.channels, a->gv.W32) + 1) & ~1);
     const uint64_t* seen_lds = nullptr;
-    if constexpr (CPL > 0) {
+    if constexpr (CPL > 0) { // (the superko table and the leaf's block are Go's)
         if (lf & 2) {
             uint64_t* sw = reinterpret_cast<uint64_t*>(next);
             for (int i = tid; i < kGoSeenCap; i += 512) { sw[i] = a->gv.snap[g].seen[i]; }
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         }
         __syncthreads();
         const bool term = simLeafTerminal(a, xchg); // a terminal leaf: no planes, tower and heads (sim_az_body.h sim_kernel); the same barriers for every wave either way
-        if constexpr (CPL > 0) {
+        if constexpr (CPL > 0) { // (the other games' leaf bodies write their planes themselves)
             if (!term) {
                 simLeafPlanes<CPL>(a, rot, g, wave, lane, leaf_smem ? leaf_smem : reinterpret_cast<const uint64_t*>(tiles), xchg);
                 __syncthreads();
@@ -104,11 +109,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         }
         if (prof) { t1 = wall_clock64(); }
         const float* xt = nullptr;
-        if (!term) { xt = simTowerWide<H, W, CIN0Q, C>(a, g, tid, tiles, xchg); } // its own function: its own register budget
+        if (!term) { xt = Tower::run(a, g, tid, tiles, xchg); }
         __syncthreads();
         if (prof) { t2 = wall_clock64(); }
         if (leaf_smem && wave >= 6) { simLeafRest<CPL>(a, rot, slot, g, lane, xchg, seen_lds, leaf_smem, 7 - wave); }
-        else if (!term) { simHeads<WPE, (H * W + 1 > 128), true>(a, g, tid, hscr, xt, G::CS, G::PW, xchg); }
+        else if (!term) { simHeads<WPE, (H * W + 1 > 128), true>(a, g, tid, hscr, xt, Tower::CS, Tower::PW, xchg); }
         else if (leaf_smem) { __syncthreads(); __syncthreads(); } // (the two barriers of the leaf's second half on waves 6 and 7)
         __syncthreads();
         if (prof) { t3 = wall_clock64(); }
@@ -128,24 +133,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
         __syncthreads();
         if (prof && tid == 0) {
             t4 = wall_clock64();
-            // (a terminal leaf's second half, alone where the heads would be, counts as leaf time: "tower" and "heads" only hold simulations that ran them)
-            prof[0] += t1 - t0 + (term ? t3 - t1 : 0); prof[1] += term ? 0 : t2 - t1; prof[2] += term ? 0 : t3 - t2; prof[3] += t4 - t3;
-            prof[4] += 1 + (static_cast<unsigned long long>(term) << 32); // simulations | those whose network evaluation was skipped
+            simProfSim(prof, t0, t1, t2, t3, t4, term);
         }
     }
     if (tid == 0) { a->pv.num_nodes[g] = *node_count; }
     if (prof && tid == 0) { simProfExit(a->prof + size_t(games) * 8); }
-    if (prof && tid == 0 && spec_w) {
-        prof[7] += (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 1]) << 40) | (static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 5]) << 20) | spec_w[kSpecWays * kSpecWay + 3];
-        prof[6] += static_cast<unsigned long long>(spec_w[kSpecWays * kSpecWay + 7]) << 40;
-    }
+    if (prof && tid == 0 && spec_w) { simProfSpec(prof, spec_w); }
 }
 
 template <int H, int W, int CIN0Q, int C, int CPL>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) void sim_kernel_wide(const SimArgs* __restrict__ a_, const uint8_t* __restrict__ rot_tab, int sim0,
+                                                                                                  int nsims, int host_start, int lf)
+{
+    simWideFrame<H, W, CPL, WideTowerF32<H, W, CIN0Q, C>>(a_, rot_tab, sim0, nsims, host_start, lf);
+}
+
+} // namespace mz
+
+#include "sim_wide_bf16.inc" // WideTowerBf16, sim_kernel_wide_bf16: here, because they need the frame above and the part function below needs them (templates: an f32 part instantiates none)
+
+namespace mz {
+
+template <auto Kernel> // sim_kernel_wide<...> or sim_kernel_wide_bf16<...>
 static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot, int sim0, int nsims, int host_start, int lf, size_t lds, hipStream_t s)
 {
-    MZ_LDS_ATTR((sim_kernel_wide<H, W, CIN0Q, C, CPL>), lds);
-    hipLaunchKernelGGL((sim_kernel_wide<H, W, CIN0Q, C, CPL>), dim3(games), dim3(512), lds, s, d_args, d_rot, sim0, nsims, host_start, lf);
+    MZ_LDS_ATTR(Kernel, lds);
+    hipLaunchKernelGGL(Kernel, dim3(games), dim3(512), lds, s, d_args, d_rot, sim0, nsims, host_start, lf);
     MZ_HIP(hipGetLastError());
     return MZ_OK;
 }
@@ -158,45 +171,27 @@ static int launchSimWideT(const SimArgs* d_args, int games, const uint8_t* d_rot
                            hipStream_t s, size_t* tile_bytes, int* rc, int* spec_words)
 #define MZ_SIM_WIDE_SIG_OF(n) MZ_SIM_WIDE_SIG(n) // (expands MZ_SIM_WIDE_PART before it is pasted)
 
-// instances by part: (H, W, input channels of the stem padded to 16, hidden channels, the rules argument: game_kind.h rulesArg); prec: Net::precision() — the
-// parts of sim_kernel_wide hold the f32 tower's instances, parts 6, 7 and 10 to 12 (sim_wide_bf16.inc) those of sim_kernel_wide_bf16
-#if MZ_SIM_WIDE_PART == 0
-#define MZ_SIM_WIDE_PART_CASES(X) X(9, 9, 32, 128, 2) X(9, 9, 32, 32, 2) X(7, 7, 32, 128, 1) X(13, 13, 32, 64, 3)
-#elif MZ_SIM_WIDE_PART == 1
-#define MZ_SIM_WIDE_PART_CASES(X) X(7, 7, 32, 32, 1) X(7, 7, 32, 64, 1) X(7, 7, 32, 256, 1)
-#elif MZ_SIM_WIDE_PART == 2 // (built with MZ_SPEC_WAYS = 4: the shapes whose tile leaves too little LDS for sixteen remembered paths)
-#define MZ_SIM_WIDE_PART_CASES(X) X(19, 19, 32, 64, 6) X(19, 19, 32, 32, 6) X(13, 13, 32, 128, 3) X(9, 9, 32, 256, 2)
-#elif MZ_SIM_WIDE_PART == 3 // Othello and TicTacToe at the reference's default width: the same phase functions as sim_kernel's
-#define MZ_SIM_WIDE_PART_CASES(X) X(8, 8, 16, 128, kRulesOthello) X(8, 8, 16, 256, kRulesOthello) X(3, 3, 16, 128, kRulesTicTacToe) X(3, 3, 16, 256, kRulesTicTacToe)
-#elif MZ_SIM_WIDE_PART == 4 // Gomoku on its default 15x15 board: 64 channels (measured), 32 (tests)
-#define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 16, 64, kRulesGomoku) X(15, 15, 16, 32, kRulesGomoku)
-#elif MZ_SIM_WIDE_PART == 5 // Hex on its default 11x11 board: 64 channels (measured), 32 (tests), 128
-#define MZ_SIM_WIDE_PART_CASES(X) X(11, 11, 16, 64, kRulesHex) X(11, 11, 16, 32, kRulesHex) X(11, 11, 16, 128, kRulesHex)
-#elif MZ_SIM_WIDE_PART == 8 // NoGo (a rules variant of Go: game_kind.h) on Go's 9x9 networks: 256 channels (the reference's default network), 128, 32 (tests); MZ_SPEC_WAYS = 4
-#define MZ_SIM_WIDE_PART_CASES(X) X(9, 9, 32, 256, kRulesNoGo) X(9, 9, 32, 128, kRulesNoGo) X(9, 9, 32, 32, kRulesNoGo)
-#elif MZ_SIM_WIDE_PART == 9 // Havannah (a game past the rows: game_kind.h): edge size 8 on its 15x15 array with 64 channels (measured) and 32, edge size 4 (7x7) with 32 (tests); 20 planes pad to 32
-#define MZ_SIM_WIDE_PART_CASES(X) X(15, 15, 32, 64, kRulesHavannah) X(15, 15, 32, 32, kRulesHavannah) X(7, 7, 32, 32, kRulesHavannah)
-#elif MZ_SIM_WIDE_PART == 6 || MZ_SIM_WIDE_PART == 7 || (MZ_SIM_WIDE_PART >= 10 && MZ_SIM_WIDE_PART <= 12) // the bf16x3 tower: sim_wide_bf16.inc defines the kernel, its instances and the part's function
-#else
-#error "MZ_SIM_WIDE_PART: not one of MZ_SIM_WIDE_PARTS"
-#endif
+// A part's instances, MZ_SIM_WIDE_CASES(X) of its .hip: X(tower, H, W, input channels of the stem padded to 16, hidden channels, the rules argument: game_kind.h
+// rulesArg); tower: f32 or bf16, the instance of Net::precision() 0 or 1
+#define MZ_SIM_WIDE_TOWER_f32 WideTowerF32
+#define MZ_SIM_WIDE_TOWER_bf16 WideTowerBf16
+#define MZ_SIM_WIDE_KERNEL_f32 sim_kernel_wide
+#define MZ_SIM_WIDE_KERNEL_bf16 sim_kernel_wide_bf16
 
 // true: this part holds the instance (launched when d_args != nullptr; d_args == nullptr: a query, *tile_bytes = the LDS bytes of the tower's tile, *spec_words = the
 // words of the walk's speculation memory as this translation unit was built)
-#ifdef MZ_SIM_WIDE_PART_CASES
 MZ_SIM_WIDE_SIG_OF(MZ_SIM_WIDE_PART)
 {
-#define MZ_SIM_WIDE_ONE(h, w, cin0q, c, cp)                                                                                                        \
-    if (H == h && W == w && c0q == cin0q && C == c && cpl == cp && prec == 0) {                                                                    \
-        if (tile_bytes) { *tile_bytes = wideTileFloats<h, w, c>(cin0q) * sizeof(float); }                                                          \
+#define MZ_SIM_WIDE_ONE(t, h, w, cin0q, c, cp)                                                                                                     \
+    if (H == h && W == w && c0q == cin0q && C == c && cpl == cp && prec == MZ_SIM_WIDE_TOWER_##t<h, w, cin0q, c>::kPrec) {                         \
+        if (tile_bytes) { *tile_bytes = MZ_SIM_WIDE_TOWER_##t<h, w, cin0q, c>::kTileFloats * sizeof(float); }                                      \
         if (spec_words) { *spec_words = kSpecWords; } /* of THIS translation unit (MZ_SPEC_WAYS) */                                                \
-        if (d_args) { *rc = launchSimWideT<h, w, cin0q, c, cp>(d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s); }                       \
+        if (d_args) { *rc = launchSimWideT<&MZ_SIM_WIDE_KERNEL_##t<h, w, cin0q, c, cp>>(d_args, games, d_rot, sim0, nsims, host_start, lf, lds, s); } \
         return true;                                                                                                                               \
     }
-    MZ_SIM_WIDE_PART_CASES(MZ_SIM_WIDE_ONE)
+    MZ_SIM_WIDE_CASES(MZ_SIM_WIDE_ONE)
 #undef MZ_SIM_WIDE_ONE
     return false;
 }
-#endif
 
 } // namespace mz

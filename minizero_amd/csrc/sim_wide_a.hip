@@ -1,5 +1,6 @@
 // instances of the wide simulation kernel, part 0 (sim_wide.inc) + the host side of all parts
 #define MZ_SIM_WIDE_PART 0
+#define MZ_SIM_WIDE_CASES(X) X(f32, 9, 9, 32, 128, 2) X(f32, 9, 9, 32, 32, 2) X(f32, 7, 7, 32, 128, 1) X(f32, 13, 13, 32, 64, 3)
 #include "sim_wide.inc"
 
 namespace mz {

@@ -29,16 +29,9 @@ __global__ __launch_bounds__(512) void sim_kernel_mz_wide(const SimArgs* __restr
     SpecMem spec{nullptr, nullptr, nullptr};
     float* hscr = reinterpret_cast<float*>(rcp_w + rcp_n);
     if (lf & 1) { // path-speculation memory of the walk (pool_body.h): LDS copies of the sqrt / bias tables + the remembered paths
-        const int tab_n = rcp_n - 2;
-        double* sqrt_w = rcp_w + rcp_n;
-        float* bias_w = reinterpret_cast<float*>(sqrt_w + tab_n);
-        int* spec_w = reinterpret_cast<int*>(bias_w + tab_n + (tab_n & 1));
-        for (int i = tid; i < tab_n; i += 512) { sqrt_w[i] = a->pv.sqrt_tab[i]; bias_w[i] = a->pv.bias_tab[i]; }
-        if (tid < kSpecWays) { spec_w[tid * kSpecWay] = 0; }
-        if (tid < 8) { spec_w[kSpecWays * kSpecWay + tid] = 0; }
-        if (tid < kHelpSegs) { spec_w[kSpecHelp + tid * kHelpSeg] = 0; }
-        spec = SpecMem{(a->no_spec & 1) ? nullptr : (LdsI32*)spec_w, (LdsCFloat*)bias_w, (LdsCDbl*)sqrt_w};
-        hscr = reinterpret_cast<float*>(spec_w + kSpecWords);
+        const SpecStage st = specStage(a->pv, rcp_w, rcp_n, tid);
+        spec = st.mem(!(a->no_spec & 1));
+        hscr = st.end();
     }
     const PoolView v = ldc(&a->pv);
     __syncthreads();
@@ -83,7 +76,7 @@ __global__ __launch_bounds__(512) void sim_kernel_mz_wide(const SimArgs* __restr
         __syncthreads();
         if (prof && tid == 0) {
             const unsigned long long t4 = wall_clock64();
-            prof[0] += t1 - t0; prof[1] += t2 - t1; prof[2] += t3 - t2; prof[3] += t4 - t3; prof[4] += 1;
+            simProfSim(prof, t0, t1, t2, t3, t4);
         }
     }
 }
