@@ -11,8 +11,11 @@
 //   * afterNNEvaluation(output) does not consume `output`: the evaluation happens on the device inside the library, one
 //     beforeNNEvaluation / afterNNEvaluation pair still = one simulation; getNNEvaluationBatchIndex() is 0 while one is in flight, -1 otherwise;
 //   * think() runs the search as library calls of whole launches: actor_mcts_think_time_limit IS honoured (the clock is looked at between library calls of 1-64 cycles, a quarter of what still fits the limit, and the
-//     decision is then taken from the simulations run so far, zero_actor.cpp:40-45), actor_mcts_think_batch_size and the virtual loss of ZeroActor::step
-//     (ref zero_actor.cpp:128-157) are not — the self-play path (ActorGroup) never uses them;
+//     decision is then taken from the simulations run so far, zero_actor.cpp:40-45).  actor_mcts_think_batch_size = B IS honoured, 1 <= B <= 64: with B > 1 a
+//     library cycle is one ZeroActor::step (ref zero_actor.cpp:128-157) — B selections under virtual loss, one forward over the leaves that are queries, expand +
+//     backup per query — so think()'s chunks of cycles are chunks of steps and the time limit falls between two steps.  B > 1 is served for AlphaZero networks
+//     with a PUCT root on the device rules (all seven board games); a MuZero network, actor_use_gumbel=true, mz_device_env=false, actor_mcts_value_rescale=true
+//     or B > 64 is refused by name when the actor is created.  B = 1 (the default) is the one-simulation-per-cycle search, unchanged;
 //   * setNetwork(network) runs the actor ON the caller's network (mz_worker_create_shared): no second copy of the weights, a later
 //     network->loadModel(...) is what the next search uses;
 //   * getEnvironment() is an `Environment` over the library's rules engine with the members the actor's callers use (isTerminal, getTurn, setTurn,

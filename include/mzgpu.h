@@ -271,6 +271,11 @@ typedef struct mz_worker_stats {
     uint64_t pre_pair_launches;  /* ... of which: on pairs of workgroups per leaf (mz_sim_round_pairs, sim_pre_pair_kernel_mz; counted per network) */
 } mz_worker_stats;
 int mz_worker_get_stats(mz_worker* w, mz_worker_stats* out);
+/* Batched think (actor_mcts_think_batch_size = B > 1 under mz_manual_step=true; 1 <= B <= 64, AlphaZero networks, PUCT root, device rules): one cycle of
+   mz_worker_run_cycles is then one STEP of every game whose search is not done — B selections under virtual loss, one forward over the leaves that are
+   queries, expand + backup per query (ref actor/zero_actor.cpp:129-157).  Counters since the worker was created, summed over its games: steps, walks
+   (selections) and queries (walks whose leaf carried no virtual loss: the leaves evaluated).  All three stay 0 with B = 1. */
+int mz_worker_think_stats(mz_worker* w, uint64_t* steps, uint64_t* walks, uint64_t* queries);
 mz_net* mz_worker_net(mz_worker* w);
 
 /* ------------------------------------------------------------------------------------------

@@ -1,0 +1,51 @@
+// Batched think (actor_mcts_think_batch_size = B > 1 under mz_manual_step): one STEP of a game's search is B selections under virtual loss, one forward over
+// the leaves that are queries, then expand + backup per query in batch order (ref actor/zero_actor.cpp:129-157, mcts.h:33-47, mcts.cpp:40-61,181-217).
+// A step of every game of a lane is five launches on the lane's stream and one small read-back; no workgroup waits for another.
+//   think_select_kernel          one wave per game, its walks one after the other: the order is the semantics
+//   think_leaf_kernel<CPL>       one wave per (game, walk): leafBody<CPL> of go_body.h for the queries
+//   (Net::forwardAZ over games * B samples)
+//   think_cand_kernel            one wave per (game, walk): azCandBody for the queries
+//   think_expand_backup_kernel   one wave per game: expandBackupBody per query in batch order, the virtual loss of the query's path removed after each
+// The node records keep their layout: the virtual loss is an array of its own beside them, allocated here.
+#pragma once
+#include "go_dev.h"
+#include "pool.h"
+
+namespace mz {
+
+class Net;
+constexpr int kThinkMaxBatch = 64;
+
+struct ThinkView {
+    int B, n, tab_n;            // walks per step, actor_num_simulation, entries of the two tables
+    float* vl;                  // [games][cap] virtual loss per node (mcts.h:59)
+    int *path, *path_action;    // [games][B][max_depth]
+    int *path_len, *query, *slot; // [games][B]: length of the walk, 1 = the walk is a query, the position slot of a query's leaf
+    const uint8_t* rot;         // [games][B] feature rotation drawn for the walk
+    int* status;                // [games][4]: root visits after the step, walks of the step, queries of the step, root child on the last query's path if it completed the search (else -1)
+    const float* bias_tab;      // [tab_n] PUCT bias for N = 0 .. n + B (N counts virtual losses: the pool's tables end at n)
+    const double* sqrt_tab;     // [tab_n]
+    // per (game, walk) outputs of the leaves and candidate lists, laid out as GoDevView / the pool's staging lay them out per game
+    uint32_t* feat;
+    uint64_t* legal;
+    int *leaf_player, *terminal;
+    float* eval;
+    int *cand_count, *cand_action, *cand_player;
+    float *cand_policy, *cand_logit, *value, *reward;
+};
+
+// The device half behind an interface: the worker (host code, also built without any device code by the host-only test programs) reaches it through
+// createThinkDevice(), which think.hip defines; where that unit is not linked the symbol is null and the worker refuses a batch size above 1.
+class ThinkDevice {
+public:
+    virtual ~ThinkDevice() = default;
+    virtual int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg) = 0;
+    virtual int clearAsync() = 0;                             // a new search: no virtual loss anywhere
+    virtual uint8_t* hostRot() = 0;                           // [games][B], uploaded by stepAsync
+    // one step of every game: select, leaves, forward, candidates, expand + backup, then the status words on their way to hostStatus()
+    virtual int stepAsync(Pool& pool, const GoDevView& gv, Net& net) = 0;
+    virtual const int* hostStatus() const = 0;                // valid after the stream has been waited for
+};
+ThinkDevice* createThinkDevice() __attribute__((weak));
+
+} // namespace mz

@@ -1,0 +1,192 @@
+// gfx950 kernels of the batched think (think.h).  One wave64 per game for the ordered parts (selection under virtual loss; expand + backup in batch order), one
+// wave64 per (game, walk) for the parts that are independent per query (leaf position + planes, candidate list).  Built like pool.hip: -ffp-contract=off, the
+// reference's formulas as written.  The leaf and candidate bodies are go_body.h's own, reached through views whose per-game arrays are offset so that the body's
+// index `g` lands on the (game, walk) entry: the bodies and their existing instantiations stay as they are.
+#include "think_body.h"
+#include "go_body.h"
+#include "net.h"
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+namespace mz {
+
+namespace {
+
+__global__ __launch_bounds__(64) void think_select_kernel(PoolView pv, ThinkView tv, int* __restrict__ err) { thinkSelectBody(pv, tv, blockIdx.x, threadIdx.x, err); }
+
+// the views of (game g, walk q - g * B): what the bodies index by game and is kept per walk moves by q - g entries
+__device__ __forceinline__ PoolView walkPool(PoolView pv, const ThinkView& tv, int g, int q)
+{
+    const ptrdiff_t d = q - g;
+    pv.path_len = tv.path_len + d;
+    pv.path = tv.path + d * pv.max_depth;
+    pv.path_action = tv.path_action + d * pv.max_depth;
+    pv.host_path_len = nullptr;
+    pv.host_path_action = nullptr;
+    return pv;
+}
+
+template <int CPL>
+__global__ __launch_bounds__(64) void think_leaf_kernel(GoDevView v, PoolView pv, ThinkView tv)
+{
+    extern __shared__ uint64_t smem[];
+    const int q = blockIdx.x, g = q / tv.B;
+    if (tv.query[q] == 0) { return; }
+    const ptrdiff_t d = q - g;
+    v.feat = tv.feat + d * v.channels * v.W32;
+    v.legal = tv.legal + d * v.LW;
+    v.leaf_player = tv.leaf_player + d;
+    v.terminal = tv.terminal + d;
+    v.eval = tv.eval + d;
+    leafBody<CPL>(v, walkPool(pv, tv, g, q), tv.rot[q], tv.slot[q], g, threadIdx.x, smem);
+}
+
+// the candidate body reads nothing that is kept per game: the (game, walk) index is its `g`
+__global__ __launch_bounds__(64) void think_cand_kernel(GoDevView v, ThinkView tv, const float* __restrict__ policy, const float* __restrict__ logit,
+                                                        const float* __restrict__ value, int* __restrict__ err)
+{
+    extern __shared__ uint64_t smem[];
+    const int q = blockIdx.x;
+    if (tv.query[q] == 0) { return; }
+    v.legal = tv.legal; v.leaf_player = tv.leaf_player; v.terminal = tv.terminal; v.eval = tv.eval;
+    azCandBody(v, policy, logit, value, tv.rot[q], tv.cand_count, tv.cand_action, tv.cand_policy, tv.cand_logit, tv.cand_player, tv.value, tv.reward, err, q,
+               threadIdx.x, smem);
+}
+
+// afterNNEvaluation per query in batch order (zero_actor.cpp:149-156): expand + backup, then the leaf's virtual loss comes off every node of the path — that
+// also clears what the duplicates of this query added (a path to a node is unique)
+__global__ __launch_bounds__(64) void think_expand_backup_kernel(PoolView pv, ThinkView tv, int* __restrict__ err)
+{
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const size_t base = size_t(g) * pv.cap;
+    float* vls = tv.vl + base;
+    const int bs = tv.status[g * 4 + 1];
+    int last = -1;
+    for (int b = 0; b < bs && b < tv.B; ++b) {
+        const int q = g * tv.B + b;
+        if (tv.query[q] == 0) { continue; }
+        const ptrdiff_t d = q - g;
+        thinkWaveSync(); // what the query before this one wrote
+        expandBackupBody(walkPool(pv, tv, g, q), tv.cand_count + d, tv.cand_action + d * pv.A, tv.cand_policy + d * pv.A, tv.cand_logit + d * pv.A, tv.cand_player + d,
+                         tv.value + d, tv.reward + d, tv.slot[q], err, g, lane, nullptr);
+        const int len = tv.path_len[q];
+        const int* path = tv.path + size_t(q) * pv.max_depth;
+        const float lv = len > 0 ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(vls[path[len - 1]]))) : 0.0f; // getVirtualLoss() of the leaf (:154), read before any of it comes off
+        for (int k = lane; k < len; k += 64) { vls[path[k]] -= lv; }
+        last = q;
+    }
+    thinkWaveSync();
+    if (lane == 0) {
+        const int count = static_cast<int>(pv.rec[base].count);
+        tv.status[g * 4 + 0] = count;
+        // the query that completed the search: handleSearchDone() ran while its path still carried one virtual loss (:96 before :154) — the host puts it back for the decision
+        int child = -1;
+        if (last >= 0 && count == tv.n + 1) { child = tv.path_len[last] >= 2 ? tv.path[size_t(last) * pv.max_depth + 1] - pv.rec[base].first_child : -1; }
+        tv.status[g * 4 + 3] = (last >= 0 && count == tv.n + 1) ? child : -2;
+    }
+}
+
+} // namespace
+
+class ThinkDeviceImpl final : public ThinkDevice {
+public:
+    int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg) override;
+    int clearAsync() override;
+    uint8_t* hostRot() override { return h_rot_.p; }
+    int stepAsync(Pool& pool, const GoDevView& gv, Net& net) override;
+    const int* hostStatus() const override { return h_status_.p; }
+
+private:
+    ThinkView v_{};
+    int device_ = 0, games_ = 0;
+    hipStream_t stream_ = nullptr;
+    DevBuf<float> vl_, bias_tab_, eval_, cand_f_, out_; // out_: the heads' outputs per (game, walk): policy, logit [Q][A], value [Q]
+    DevBuf<double> sqrt_tab_;
+    DevBuf<int> walk_i_, status_, leaf_i_, cand_i_;
+    DevBuf<uint8_t> d_rot_;
+    PinBuf<uint8_t> h_rot_;
+    PinBuf<int> h_status_;
+    DevBuf<uint32_t> feat_;
+    DevBuf<uint64_t> legal_;
+};
+
+ThinkDevice* createThinkDevice() { return new ThinkDeviceImpl(); }
+
+#define TALLOC(buf, k) \
+    if (!(buf).alloc(k)) { setError("think: allocation of %zu elements failed (%s)", size_t(k), #buf); return MZ_ERR_DEVICE; }
+
+int ThinkDeviceImpl::init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg)
+{
+    if (B < 2 || B > kThinkMaxBatch) { setError("think: batch size %d out of range", B); return MZ_ERR_ARG; }
+    device_ = device;
+    stream_ = stream;
+    MZ_HIP(hipSetDevice(device));
+    const PoolView& pv = pool.v_;
+    const size_t G = pv.games, Q = G * B, MD = pv.max_depth, A = pv.A;
+    games_ = pv.games;
+    ThinkView& t = v_;
+    t.B = B; t.n = cfg.num_simulation; t.tab_n = cfg.num_simulation + B + 2;
+    TALLOC(vl_, G * pv.cap); TALLOC(walk_i_, 2 * Q * MD + 3 * Q); TALLOC(status_, 4 * G); TALLOC(h_status_, 4 * G);
+    TALLOC(d_rot_, Q); TALLOC(h_rot_, Q);
+    TALLOC(bias_tab_, t.tab_n); TALLOC(sqrt_tab_, t.tab_n);
+    TALLOC(feat_, Q * gv.channels * gv.W32); TALLOC(legal_, Q * gv.LW); TALLOC(leaf_i_, 2 * Q); TALLOC(eval_, Q);
+    TALLOC(cand_i_, 2 * Q + Q * A); TALLOC(cand_f_, 2 * Q + 2 * Q * A); TALLOC(out_, 2 * Q * A + Q);
+    t.vl = vl_.p;
+    t.path = walk_i_.p; t.path_action = walk_i_.p + Q * MD; t.path_len = walk_i_.p + 2 * Q * MD; t.query = t.path_len + Q; t.slot = t.query + Q;
+    t.rot = d_rot_.p;
+    t.status = status_.p;
+    t.feat = feat_.p; t.legal = legal_.p; t.leaf_player = leaf_i_.p; t.terminal = leaf_i_.p + Q; t.eval = eval_.p;
+    t.cand_count = cand_i_.p; t.cand_player = cand_i_.p + Q; t.cand_action = cand_i_.p + 2 * Q;
+    t.value = cand_f_.p; t.reward = cand_f_.p + Q; t.cand_policy = cand_f_.p + 2 * Q; t.cand_logit = cand_f_.p + 2 * Q + Q * A;
+    // PUCT tables as Pool::init builds them (ref mcts.cpp:57-58), for N up to n + B
+    std::vector<float> bias(t.tab_n);
+    std::vector<double> sq(t.tab_n);
+    for (int N = 0; N < t.tab_n; ++N) {
+        const float ratio = (1 + N + cfg.puct_base) / cfg.puct_base;
+        bias[N] = cfg.puct_init + ::log(static_cast<double>(ratio));
+        sq[N] = ::sqrt(static_cast<double>(N));
+    }
+    MZ_HIP(hipMemcpy(bias_tab_.p, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice));
+    MZ_HIP(hipMemcpy(sqrt_tab_.p, sq.data(), sq.size() * sizeof(double), hipMemcpyHostToDevice));
+    t.bias_tab = bias_tab_.p;
+    t.sqrt_tab = sqrt_tab_.p;
+    MZ_HIP(hipMemset(walk_i_.p, 0, walk_i_.n * sizeof(int)));
+    MZ_HIP(hipMemset(status_.p, 0, status_.n * sizeof(int)));
+    MZ_HIP(hipMemset(feat_.p, 0, feat_.n * sizeof(uint32_t))); // the forward runs over every (game, walk) entry: the ones no query ever wrote hold empty planes
+    memset(h_rot_.p, 0, Q);
+    memset(h_status_.p, 0, 4 * G * sizeof(int));
+    return clearAsync();
+}
+
+int ThinkDeviceImpl::clearAsync()
+{
+    MZ_HIP(hipMemsetAsync(vl_.p, 0, vl_.n * sizeof(float), stream_));
+    return MZ_OK;
+}
+
+int ThinkDeviceImpl::stepAsync(Pool& pool, const GoDevView& gv, Net& net)
+{
+    const PoolView& pv = pool.v_;
+    const int Q = games_ * v_.B;
+    float *d_policy = out_.p, *d_logit = out_.p + size_t(Q) * pv.A, *d_value = out_.p + 2 * size_t(Q) * pv.A;
+    MZ_HIP(hipMemcpyAsync(d_rot_.p, h_rot_.p, Q, hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL(think_select_kernel, dim3(games_), dim3(64), 0, stream_, pv, v_, pool.errFlag());
+    MZ_HIP(hipGetLastError());
+    const size_t leaf_smem = gv.kind == kGo ? goLeafSmemBytes(gv, pv.max_depth) : 0;
+    if (!forRulesArg(rulesArg(gv.kind, gv.n), [&](auto cpl) { hipLaunchKernelGGL(think_leaf_kernel<cpl()>, dim3(Q), dim3(64), leaf_smem, stream_, gv, pv, v_); })) {
+        setError("think: board too large");
+        return MZ_ERR_ARG;
+    }
+    MZ_HIP(hipGetLastError());
+    int rc = net.forwardAZ(reinterpret_cast<const float*>(v_.feat), Q, d_policy, d_logit, d_value, true);
+    if (rc) { return rc; }
+    hipLaunchKernelGGL(think_cand_kernel, dim3(Q), dim3(64), azCandSmemBytes(gv.A), stream_, gv, v_, d_policy, d_logit, d_value, pool.errFlag());
+    MZ_HIP(hipGetLastError());
+    hipLaunchKernelGGL(think_expand_backup_kernel, dim3(games_), dim3(64), 0, stream_, pv, v_, pool.errFlag());
+    MZ_HIP(hipGetLastError());
+    MZ_HIP(hipMemcpyAsync(h_status_.p, status_.p, size_t(games_) * 4 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    return MZ_OK;
+}
+
+} // namespace mz

@@ -14,6 +14,7 @@
 #include "net.h"
 #include "pool.h"
 #include "go_dev.h"
+#include "think.h"
 #include "gumbel.h"
 #include "host_threads.h"
 #include <pthread.h>
@@ -140,6 +141,13 @@ public:
     int envResetSeed(int g, int seed);
     int envRotateAction(int g, int action_id, int rotation) const;
     mz_worker_stats stats_{};
+    int thinkStats(uint64_t* steps, uint64_t* walks, uint64_t* queries) const
+    {
+        if (steps) { *steps = think_steps_; }
+        if (walks) { *walks = think_walks_; }
+        if (queries) { *queries = think_queries_; }
+        return MZ_OK;
+    }
     int getStats(mz_worker_stats* out)
     {
         *out = stats_;
@@ -220,6 +228,18 @@ private:
     int phase2(Lane& L);
     int phase2Resident(Lane& L);
     int runCyclesSim(int n);
+    // batched think (actor_mcts_think_batch_size > 1 under mz_manual_step; think.h): a cycle is one STEP of every game whose search is not done
+    int thinkB_ = 1;                       // the batch size in force (1: today's path, untouched)
+    std::unique_ptr<ThinkDevice> think_;   // lane 0's (a think worker has one lane)
+    std::vector<int> think_count_;         // root visits of every game (the games of a worker finish after different numbers of steps)
+    std::vector<uint8_t> think_done_;
+    std::vector<int> think_vl_child_;      // >= -1: the decision of game g sees one virtual loss on the root and on this root child (-1: on the root alone); -2: none
+    uint64_t think_steps_ = 0, think_walks_ = 0, think_queries_ = 0;
+    int thinkRefusal() const;
+    int thinkCycle();
+    int thinkReadRoots(Lane& L);
+    void drawRootNoise(int g, std::vector<float>& noise);
+    float vlOf(int g, int child) const { return (think_vl_child_.empty() || think_vl_child_[g] < -1) ? 0.0f : ((child < 0 || child == think_vl_child_[g]) ? 1.0f : 0.0f); }
     void drawCycles(int b0, int b1, int noise_row);
     void drawStream(int t, int b0, int b1, int noise_row);
     int uploadRoots(Lane& L);
@@ -231,7 +251,7 @@ private:
     void buildCandidates(int g);
     void buildLeaf(int g);
     // per-move host logic on root statistics (rr_* mirrors)
-    float normalizedMean(float reward, float mean, float count, int player, int g) const;
+    float normalizedMean(float reward, float mean, float count, int player, int g, float vl = 0.0f) const;
     int selectChildByMaxCount(int g) const;
     int selectChildBySoftmaxCount(int g, float temperature, float value_threshold = 0.1f);
     bool isResign(int g) const;
@@ -360,6 +380,8 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     if (cfg_.zero_num_parallel_games > 4096) { setError("zero_num_parallel_games > 4096 (ref alphazero_network.h:120 kReserved_batch_size)"); return MZ_ERR_ARG; }
     if (cfg_.mz_nn_precision != "f32" && cfg_.mz_nn_precision != "bf16x3") { setError("mz_nn_precision '%s' unknown (f32 | bf16x3)", cfg_.mz_nn_precision.c_str()); return MZ_ERR_ARG; }
     if (shared && shared->device_ != device) { setError("worker: the shared network lives on device %d, the worker on %d", shared->device_, device); return MZ_ERR_ARG; }
+    thinkB_ = cfg_.mz_manual_step ? std::max(1, cfg_.actor_mcts_think_batch_size) : 1; // without mz_manual_step the key stays ignored, as ActorGroup never uses it
+    if (thinkB_ > 1) { int rt = thinkRefusal(); if (rt) { return rt; } }
     G_ = cfg_.zero_num_parallel_games;
     A_ = desc.action_size;
     n_ = cfg_.actor_num_simulation;
@@ -400,7 +422,29 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
         gum_.log2_m = std::log2(m);
     }
     rounds_ = plan_.rounds;
+    if (thinkB_ > 1) {
+        if (!plan_.resident) { setError("actor_mcts_think_batch_size=%d: the batched think runs on the device rules, which this game or pool size does not have", thinkB_); return MZ_ERR_ARG; }
+        Lane& L = *lanes_[0];
+        if (!createThinkDevice) { setError("actor_mcts_think_batch_size=%d: this build has no device code for the batched think", thinkB_); return MZ_ERR_DEVICE; }
+        think_.reset(createThinkDevice());
+        if ((rc = think_->init(device_, L.stream, L.pool, L.godev.v_, thinkB_, sc))) { return rc; }
+        think_count_.assign(G_, 0);
+        think_done_.assign(G_, 0);
+        think_vl_child_.assign(G_, -2);
+    }
     return resetAllSearches();
+}
+
+// actor_mcts_think_batch_size > 1: what the batched think does not cover is refused by name when the worker is created (documented differences)
+int Worker::thinkRefusal() const
+{
+    const int B = thinkB_;
+    if (B > kThinkMaxBatch) { setError("actor_mcts_think_batch_size=%d: at most %d walks per step", B, kThinkMaxBatch); return MZ_ERR_ARG; }
+    if (desc_.type != 0 || cfg_.nn_type_name != "alphazero") { setError("actor_mcts_think_batch_size=%d: the batched think searches AlphaZero networks only (a MuZero network's step is not built)", B); return MZ_ERR_ARG; }
+    if (cfg_.actor_use_gumbel) { setError("actor_mcts_think_batch_size=%d with actor_use_gumbel=true: the batched think has a PUCT root only", B); return MZ_ERR_ARG; }
+    if (!cfg_.mz_device_env) { setError("actor_mcts_think_batch_size=%d with mz_device_env=false: the batched think runs on the device rules", B); return MZ_ERR_ARG; }
+    if (cfg_.actor_mcts_value_rescale) { setError("actor_mcts_think_batch_size=%d with actor_mcts_value_rescale=true: the batched think keeps no value bounds (board games do not rescale)", B); return MZ_ERR_ARG; }
+    return MZ_OK;
 }
 
 // Every execution choice of the worker, from the configuration, the descriptor, the game, the first lane's network (which kernels its shape has), the pool's
@@ -410,7 +454,7 @@ Worker::Plan Worker::resolvePlan(int lanes) const
     Plan p;
     const GameEnv& e = *games_[0].env;
     const Net& net = *lanes_[0]->net;
-    p.lanes = (G_ < 2 * lanes || shared_net_) ? 1 : lanes; // a shared network has one stream: one lane
+    p.lanes = (G_ < 2 * lanes || shared_net_ || thinkB_ > 1) ? 1 : lanes; // a shared network has one stream: one lane; so has the batched think
     p.lane_size = (G_ + p.lanes - 1) / p.lanes;
     p.sim_mode.cluster = cfg_.mz_sim_cluster && p.lanes == 1; // two lanes = two concurrent cooperative launches: not with clusters that wait for each other
     // AlphaZero board games: every plane is 0 / 1, so leaves reach the network bit-packed whatever kernels serve its shape — the fused towers stage the bits
@@ -421,7 +465,7 @@ Worker::Plan Worker::resolvePlan(int lanes) const
     const bool gumbel_fits = !cfg_.actor_use_gumbel || (cfg_.actor_gumbel_sample_size >= 2 && cfg_.actor_gumbel_sample_size <= kGumbelMaxSample);
     p.resident = cfg_.mz_device_env && desc_.type == 0 && e.hasDeviceTwin() && p.lane_size <= kRotPackGames;
     p.sim_mz = cfg_.mz_sim_kernel && (desc_.type == 1 || desc_.type == 2) && net.hasSimKernelMz(n_) && gumbel_fits;
-    p.sim_kernel = p.sim_mz || (p.resident && cfg_.mz_sim_kernel && net.hasSimKernel(e.boardSize(), e.deviceKind(), n_) && gumbel_fits);
+    p.sim_kernel = p.sim_mz || (p.resident && cfg_.mz_sim_kernel && thinkB_ == 1 && net.hasSimKernel(e.boardSize(), e.deviceKind(), n_) && gumbel_fits);
     p.sim_root_host = p.sim_mz && desc_.type == 2;
     p.dev_gumbel = p.sim_kernel && cfg_.actor_use_gumbel;
     p.defer_info = p.sim_kernel && !cfg_.mz_manual_step;
@@ -476,7 +520,7 @@ Worker::Plan Worker::resolvePlan(int lanes) const
     // cycle is dominated by long convolution kernels runs faster as TWO lanes on two streams: one lane's single-wave tree kernels (select, leaf, candidates, expand:
     // ~0.3 ms per cycle with 255 CUs idle) run under the other lane's convolutions.  Measured (profiles/r06_lockstep_lanes.json): 19x19 6b x 128, 256 games, 331 GFLOP
     // per cycle: 64.1 -> 67.1 k leaf-evals/s; 13x13 6b x 96, 73 GFLOP per cycle: 182 -> 167 k (its convolutions at 128 samples no longer fill the chip) — hence the bound.
-    if (cfg_.mz_pipeline_lanes == 0 && p.lanes == 1 && !shared_net_ && p.resident && !p.sim_kernel && G_ >= 64) {
+    if (cfg_.mz_pipeline_lanes == 0 && p.lanes == 1 && !shared_net_ && thinkB_ == 1 && p.resident && !p.sim_kernel && G_ >= 64) {
         const double P = double(desc_.hidden_channel_height) * desc_.hidden_channel_width, C = desc_.num_hidden_channels;
         const double conv_flops = 2.0 * 9.0 * P * (double(desc_.num_input_channels) * C + 2.0 * desc_.num_blocks * C * C);
         if (double(G_) * conv_flops >= 2.0e11) { return resolvePlan(2); }
@@ -764,7 +808,7 @@ void Worker::buildLeaf(int gi)
 
 // ------------------------------------------------------------------------------------------------
 // host logic on root statistics
-float Worker::normalizedMean(float reward, float mean, float count, int player, int g) const // ref mcts.cpp:40-53
+float Worker::normalizedMean(float reward, float mean, float count, int player, int g, float vl) const // ref mcts.cpp:40-53; vl: the node's virtual loss (batched think: thinkCycle)
 {
     float value = reward + cfg_.actor_mcts_reward_discount * mean;
     if (cfg_.actor_mcts_value_rescale) {
@@ -774,7 +818,7 @@ float Worker::normalizedMean(float reward, float mean, float count, int player, 
         value = ::fmin(static_cast<double>(1), ::fmax(static_cast<double>(-1), static_cast<double>(2 * value - 1)));
     }
     value = (player == flipping_player_ ? -value : value);
-    value = (value * count - 0.0f) / (count + 0.0f);
+    value = (value * count - vl) / (count + vl);
     return value;
 }
 
@@ -797,7 +841,7 @@ int Worker::selectChildBySoftmaxCount(int g, float temperature, float value_thre
     const int child_player = games_[g].env->turn();
     int selected = -1;
     const int best = selectChildByMaxCount(g);
-    const float best_mean = normalizedMean(rr_reward_[off + best], rr_mean_[off + best], rr_count_[off + best], child_player, g);
+    const float best_mean = normalizedMean(rr_reward_[off + best], rr_mean_[off + best], rr_count_[off + best], child_player, g, vlOf(g, best));
     float sum = 0.0f;
     const float exponent = 1 / temperature;
     for (int i = 0; i < rr_nc_[g]; ++i) {
@@ -805,7 +849,7 @@ int Worker::selectChildBySoftmaxCount(int g, float temperature, float value_thre
         // this loop runs over ~17 k children per move of BASELINE configs[1] between two launches
         const float count = exponent == 1.0f ? rr_count_[off + i] : std::pow(rr_count_[off + i], exponent);
         if (count == 0) { continue; }
-        const float mean = normalizedMean(rr_reward_[off + i], rr_mean_[off + i], rr_count_[off + i], child_player, g);
+        const float mean = normalizedMean(rr_reward_[off + i], rr_mean_[off + i], rr_count_[off + i], child_player, g, vlOf(g, i));
         if (mean < best_mean - value_threshold) { continue; }
         sum += count;
         float rand = rngOf(g).randReal(sum);
@@ -821,9 +865,9 @@ bool Worker::isResign(int g) const // ref mcts.cpp:84-89, zero_actor.h:40
     const size_t off = size_t(g) * A_;
     // the root's own reward field is only ever written by the first backup of the search with the root-evaluation
     // reward, which is 0 for every environment this worker supports
-    const float root_win_rate = normalizedMean(0.0f, rr_root_mean_[g], rr_root_count_[g], rootPlayerFor(gm), g);
+    const float root_win_rate = normalizedMean(0.0f, rr_root_mean_[g], rr_root_count_[g], rootPlayerFor(gm), g, vlOf(g, -1));
     const int s = gm.selected;
-    const float action_win_rate = normalizedMean(rr_reward_[off + s], rr_mean_[off + s], rr_count_[off + s], gm.env->turn(), g);
+    const float action_win_rate = normalizedMean(rr_reward_[off + s], rr_mean_[off + s], rr_count_[off + s], gm.env->turn(), g, vlOf(g, s));
     return (-root_win_rate < cfg_.actor_resign_threshold && action_win_rate < cfg_.actor_resign_threshold);
 }
 
@@ -1109,31 +1153,34 @@ void Worker::flushDeferred()
 
 thread_local Worker::StreamSink* Worker::tl_sink_ = nullptr;
 
+void Worker::drawRootNoise(int g, std::vector<float>& noise) // ref zero_actor.cpp:194-213
+{
+    const size_t off = size_t(g) * A_;
+    const int k = rr_nc_[g];
+    if (cfg_.actor_use_dirichlet_noise) {
+        const float epsilon = cfg_.actor_dirichlet_noise_epsilon;
+        rngOf(g).dirichlet(cfg_.actor_dirichlet_noise_alpha, k, noise);
+        for (int i = 0; i < k; ++i) {
+            rr_noise_[off + i] = noise[i];
+            rr_policy_[off + i] = (1 - epsilon) * rr_policy_[off + i] + epsilon * noise[i];
+        }
+    } else {
+        rngOf(g).gumbel(k, noise);
+        for (int i = 0; i < k; ++i) {
+            rr_noise_[off + i] = noise[i];
+            rr_logit_[off + i] = rr_logit_[off + i] + noise[i];
+        }
+    }
+    memcpy(noise_policy_.data() + off, rr_policy_.data() + off, k * sizeof(float));
+    memcpy(noise_logit_.data() + off, rr_logit_.data() + off, k * sizeof(float));
+    memcpy(noise_noise_.data() + off, rr_noise_.data() + off, k * sizeof(float));
+}
+
 // the per-move host logic of one game, in the reference's order: [root noise][move decision + Gumbel bookkeeping + act / record / reset][rotation]
 void Worker::serialGame(int g, bool want_noise, bool done, bool az, std::vector<float>& noise)
 {
     Game& gm = games_[g];
-    const size_t off = size_t(g) * A_;
-    if (want_noise) { // ref zero_actor.cpp:194-213
-        const int k = rr_nc_[g];
-        if (cfg_.actor_use_dirichlet_noise) {
-            const float epsilon = cfg_.actor_dirichlet_noise_epsilon;
-            rngOf(g).dirichlet(cfg_.actor_dirichlet_noise_alpha, k, noise);
-            for (int i = 0; i < k; ++i) {
-                rr_noise_[off + i] = noise[i];
-                rr_policy_[off + i] = (1 - epsilon) * rr_policy_[off + i] + epsilon * noise[i];
-            }
-        } else {
-            rngOf(g).gumbel(k, noise);
-            for (int i = 0; i < k; ++i) {
-                rr_noise_[off + i] = noise[i];
-                rr_logit_[off + i] = rr_logit_[off + i] + noise[i];
-            }
-        }
-        memcpy(noise_policy_.data() + off, rr_policy_.data() + off, k * sizeof(float));
-        memcpy(noise_logit_.data() + off, rr_logit_.data() + off, k * sizeof(float));
-        memcpy(noise_noise_.data() + off, rr_noise_.data() + off, k * sizeof(float));
-    }
+    if (want_noise) { drawRootNoise(g, noise); }
     if (done) { gm.selected = decideAction(g); }                  // zero_actor.cpp:96 handleSearchDone()
     if (cfg_.actor_use_gumbel) { gumbelSequentialHalving(g); }     // zero_actor.cpp:97
     if (done) { handleSearchDone(g); }                             // actor_group.cpp:92
@@ -1682,9 +1729,92 @@ int Worker::runCyclesSim(int n)
     return n;
 }
 
+// The lane's root statistics into the rr_* mirrors (the read every per-move decision starts from)
+int Worker::thinkReadRoots(Lane& L)
+{
+    const int g0 = L.g0;
+    const size_t o = size_t(g0) * A_;
+    int rc = L.pool.rootRead(rr_nc_.data() + g0, rr_action_.data() + o, rr_count_.data() + o, rr_mean_.data() + o, rr_policy_.data() + o, rr_logit_.data() + o,
+                             rr_noise_.data() + o, rr_value_.data() + o, rr_reward_.data() + o, rr_root_count_.data() + g0, rr_root_mean_.data() + g0,
+                             rr_root_value_.data() + g0, rr_lo_.data() + g0, rr_hi_.data() + g0, rr_bsize_.data() + g0, false);
+    if (rc) { return rc; }
+    return L.pool.checkError();
+}
+
+// One step (ref zero_actor.cpp:129-157) of every game whose search is not done.  The host draws the step's rotations — game by game, each game's walks in order,
+// also for the walks that turn out to be duplicates (:56 runs before :142) —, the device runs the step (think.h), and the host then does, game by game, what
+// afterNNEvaluation does on the host's generator: the root noise behind the first step, the decision behind the step that completes the search.
+int Worker::thinkCycle()
+{
+    const double t0 = nowMs();
+    MZ_HIP(hipSetDevice(device_));
+    Lane& L = *lanes_[0];
+    const int B = thinkB_;
+    uint8_t* rot = think_->hostRot();
+    std::vector<int> bs(G_, 0);
+    std::vector<uint8_t> expands_root(G_, 0);
+    for (int g = 0; g < G_; ++g) {
+        expands_root[g] = !think_done_[g] && think_count_[g] == 0;
+        bs[g] = think_done_[g] ? 0 : std::min(B, n_ + 1 - think_count_[g]);
+        for (int b = 0; b < bs[g]; ++b) { rot[size_t(g) * B + b] = cfg_.actor_use_random_rotation_features ? static_cast<uint8_t>(rngOf(g).randInt() % 8) : 0; }
+    }
+    int rc = think_->stepAsync(L.pool, L.godev.v_, *L.net);
+    if (rc) { return rc; }
+    MZ_HIP(hipStreamSynchronize(L.stream));
+    if ((rc = L.pool.checkError())) { return rc; }
+    const int* st = think_->hostStatus();
+    bool first = false, finished = false;
+    for (int g = 0; g < G_; ++g) {
+        if (bs[g] == 0) { continue; }
+        if (st[g * 4 + 1] != bs[g]) { setError("think: game %d walked %d times in a step of %d", g, st[g * 4 + 1], bs[g]); return MZ_ERR_STATE; }
+        ++think_steps_; think_walks_ += bs[g]; think_queries_ += st[g * 4 + 2];
+        stats_.leaf_evals += st[g * 4 + 2];
+        first = first || think_count_[g] == 0;
+        think_count_[g] = st[g * 4 + 0];
+        finished = finished || think_count_[g] == n_ + 1;
+    }
+    const bool want_noise = first && cfg_.actor_use_dirichlet_noise; // (a PUCT root: no Gumbel noise)
+    if (want_noise || finished) {
+        if ((rc = thinkReadRoots(L))) { return rc; }
+    }
+    std::vector<float>& noise = stream_noise_[0];
+    bool all_done = true;
+    for (int g = 0; g < G_; ++g) {
+        if (want_noise) { noise_mask_[g] = expands_root[g]; }
+        if (bs[g] != 0) {
+            if (want_noise && expands_root[g]) { drawRootNoise(g, noise); } // the leaf was the root (zero_actor.cpp:95)
+            if (think_count_[g] == n_ + 1) { // handleSearchDone() inside the last query's afterNNEvaluation (:96): its path still carries one virtual loss
+                think_vl_child_[g] = st[g * 4 + 3] >= -1 ? st[g * 4 + 3] : -1;
+                games_[g].selected = decideAction(g);
+                handleSearchDone(g);
+                think_vl_child_[g] = -2;
+                think_done_[g] = 1;
+            }
+        }
+        all_done = all_done && think_done_[g];
+    }
+    if (want_noise) {
+        if ((rc = L.pool.rootSetNoise(noise_mask_.data(), noise_policy_.data(), noise_logit_.data(), noise_noise_.data()))) { return rc; }
+        std::fill(noise_mask_.begin(), noise_mask_.end(), 1);
+    }
+    pending_ = true;
+    ++stats_.cycles;
+    if (all_done) { search_done_ = true; pending_ = false; }
+    stats_.ms_total += nowMs() - t0;
+    return MZ_OK;
+}
+
 int Worker::runCycles(int n)
 {
     if (!running_ || search_done_) { return 0; }
+    if (think_) {
+        for (int i = 0; i < n; ++i) {
+            int rc = thinkCycle();
+            if (rc) { return rc; }
+            if (search_done_) { return i + 1; }
+        }
+        return n;
+    }
     if (plan_.sim_kernel) { return runCyclesSim(n); }
     stop_now_ = false;
     for (int i = 0; i < n; ++i) {
@@ -1767,6 +1897,12 @@ int Worker::resetSearchAll() // ZeroActor::resetSearch (ref zero_actor.cpp:29-34
     search_done_ = false;
     root_host_pending_ = false;
     for (auto& h : held_) { h = Held(); }
+    if (think_) {
+        std::fill(think_count_.begin(), think_count_.end(), 0);
+        std::fill(think_done_.begin(), think_done_.end(), 0);
+        int rc = think_->clearAsync();
+        if (rc) { return rc; }
+    }
     return resetAllSearches();
 }
 
@@ -1777,6 +1913,23 @@ int Worker::finishSearch()
 {
     if (!cfg_.mz_manual_step) { setError("finish_search: the worker plays on its own (mz_manual_step=false)"); return MZ_ERR_STATE; }
     if (search_done_) { return MZ_OK; }
+    if (think_) { // between two steps no virtual loss is outstanding: the games that are not done decide on the plain statistics, the others keep their decision
+        for (int g = 0; g < G_; ++g) {
+            if (think_count_[g] < 1) { setError("finish_search: the root has not been evaluated yet (run at least one step of the search first)"); return MZ_ERR_STATE; }
+        }
+        MZ_HIP(hipSetDevice(device_));
+        int rc = thinkReadRoots(*lanes_[0]);
+        if (rc) { return rc; }
+        for (int g = 0; g < G_; ++g) {
+            if (think_done_[g]) { continue; }
+            games_[g].selected = decideAction(g);
+            handleSearchDone(g);
+            think_done_[g] = 1;
+        }
+        search_done_ = true;
+        pending_ = false;
+        return MZ_OK;
+    }
     if (!pending_ || sims_done_ < 1) { setError("finish_search: the root has not been evaluated yet (run at least two cycles of the search first)"); return MZ_ERR_STATE; }
     MZ_HIP(hipSetDevice(device_));
     sim_pre_ = sims_done_;
@@ -2154,6 +2307,11 @@ int mz_worker_env_rotate_action(const mz_worker* w, int game, int action_id, int
 {
     if (!w) { mz::setError("NULL worker"); return MZ_ERR_ARG; }
     return w->w.envRotateAction(game, action_id, rotation);
+}
+int mz_worker_think_stats(mz_worker* w, uint64_t* steps, uint64_t* walks, uint64_t* queries)
+{
+    if (!w) { mz::setError("think_stats: NULL argument"); return MZ_ERR_ARG; }
+    return w->w.thinkStats(steps, walks, queries);
 }
 int mz_worker_get_stats(mz_worker* w, mz_worker_stats* out)
 {

@@ -143,6 +143,14 @@ def load():
         L.mz_worker_pop_line.argtypes = [vp, C.c_char_p, C.c_int]
         L.mz_worker_wait_lines.argtypes = [vp]
         L.mz_worker_get_stats.argtypes = [vp, C.POINTER(WorkerStats)]
+        if hasattr(L, "mz_worker_think_stats"):  # (MZ_LIBMZGPU may name a build from before the batched think: tools/think_bench.py measures one)
+            u64p = C.POINTER(C.c_uint64)
+            L.mz_worker_think_stats.argtypes = [vp, u64p, u64p, u64p]
+        L.mz_worker_search_done.argtypes = [vp]
+        L.mz_worker_search_action.argtypes = [vp, C.c_int, ip, ip, ip]
+        L.mz_worker_act.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+        L.mz_worker_reset_search.argtypes = [vp]
+        L.mz_worker_finish_search.argtypes = [vp]
         L.mz_worker_peek_record.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
         L.mz_worker_net.restype = vp
         L.mz_worker_net.argtypes = [vp]
@@ -509,6 +517,30 @@ class Worker:
         s = WorkerStats()
         _check(self.L, self.L.mz_worker_get_stats(self.h, C.byref(s)))
         return {k: getattr(s, k) for k, _ in WorkerStats._fields_}
+
+    def think_stats(self):
+        """(steps, walks, queries) of the batched think (actor_mcts_think_batch_size > 1 under mz_manual_step), summed over the games; zeros otherwise"""
+        s, w, q = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(self.L, self.L.mz_worker_think_stats(self.h, C.byref(s), C.byref(w), C.byref(q)))
+        return s.value, w.value, q.value
+
+    def search_done(self):
+        return _check(self.L, self.L.mz_worker_search_done(self.h)) == 1
+
+    def search_action(self, game):
+        """(action id, player, resigns?) of the completed search of a game (mz_manual_step)"""
+        a, p, r = C.c_int(), C.c_int(), C.c_int()
+        _check(self.L, self.L.mz_worker_search_action(self.h, game, C.byref(a), C.byref(p), C.byref(r)))
+        return a.value, p.value, bool(r.value)
+
+    def act(self, game, action, player):
+        return _check(self.L, self.L.mz_worker_act(self.h, game, action, player)) == 1
+
+    def reset_search(self):
+        _check(self.L, self.L.mz_worker_reset_search(self.h))
+
+    def finish_search(self):
+        _check(self.L, self.L.mz_worker_finish_search(self.h))
 
     def net(self):
         return Net(self.desc, None, handle=self.L.mz_worker_net(self.h))
