@@ -21,7 +21,13 @@
 //   * getEnvironment() is an `Environment` over the library's rules engine with the members the actor's callers use (isTerminal, getTurn, setTurn,
 //     getEvalScore, getReward, getFeatures, getRotateAction, isLegalAction, getLegalActions, getNumActions() for getActionHistory().size(), reset(seed), toString) —
 //     toString() is a plain-text board, not the reference's ANSI-coloured one; game-specific members (GoEnv::getBenson..., ...) are not there;
-//   * getSearchInfo() is a one-line summary (the reference's is a free-form, time-stamped debug string: zero_actor.cpp:159-176);
+//   * getSearchInfo() is a one-line summary (the reference's is a free-form, time-stamped debug string: zero_actor.cpp:159-176); its two node dumps
+//     (`root node info:` / `action node info:`, zero_actor.cpp:173-174) are getSearchNodeInfo();
+//   * getMCTS() returns a HOST SNAPSHOT of the visited tree, taken at the call (std::shared_ptr<const MCTS>): the root and every node with count > 0, read back
+//     from the library's node pool.  MCTSNode has the reference's getters and no mutators — code that writes into the tree does not compile instead of
+//     silently writing into a copy.  getChild(i) only reaches VISITED children: an unvisited child is not read back and getChild(i) is nullptr for it, while
+//     getNumChildren() still reports the real number (so the reference's `for (i < getNumChildren())` loops need a null check).  A later search does not
+//     change a snapshot already taken;
 //   * createSearch() returns nullptr: the tree lives in the library's node pool (mz_pool_*).
 // Header-only; link with -lmzgpu.
 #pragma once
@@ -29,6 +35,9 @@
 #include "network.h"
 #include <chrono>
 #include <cstdlib>
+#include <iostream>
+#include <memory>
+#include <sstream>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -174,6 +183,131 @@ public:
     virtual ~Search() = default;
     virtual void reset() = 0;
 };
+
+// A node of the host snapshot ZeroActor::getMCTS() returns (ref actor/mcts.h:17-64, tree.h:32-53): the reference's getters, no mutators
+class MCTS;
+class MCTSNode {
+public:
+    inline bool isLeaf() const { return num_children_ == 0; }
+    inline Action getAction() const { return action_; }
+    inline int getNumChildren() const { return num_children_; } // the real number, unvisited children included
+    inline const MCTSNode* getChild(int index) const;           // nullptr for an unvisited child (not read back) and past the end
+    inline float getCount() const { return count_; }
+    inline float getMean() const { return mean_; }
+    inline float getPolicy() const { return policy_; }
+    inline float getPolicyLogit() const { return policy_logit_; }
+    inline float getPolicyNoise() const { return policy_noise_; }
+    inline float getValue() const { return value_; }
+    inline float getReward() const { return reward_; }
+    inline bool displayInTreeLog() const { return count_ > 0; } // ref mcts.h:27
+    std::string toString() const // ref mcts.cpp:63-75
+    {
+        std::ostringstream oss;
+        oss.precision(4);
+        oss << std::fixed << "p = " << policy_ << ", p_logit = " << policy_logit_ << ", p_noise = " << policy_noise_ << ", v = " << value_ << ", r = " << reward_
+            << ", mean = " << mean_ << ", count = " << count_;
+        return oss.str();
+    }
+
+private:
+    friend class MCTS;
+    Action action_;
+    int num_children_ = 0, ordinal_ = 0;
+    int first_kept_ = 0, num_kept_ = 0; // its visited children in the snapshot: nodes [first_kept_, first_kept_ + num_kept_), ascending in ordinal_
+    float count_ = 0, mean_ = 0, policy_ = 0, policy_logit_ = 0, policy_noise_ = 0, value_ = 0, reward_ = 0;
+    const MCTS* tree_ = nullptr;
+};
+
+// The visited tree of one search as a host snapshot (ref actor/mcts.h:66-119, tree.h:55-122): what mz_worker_tree reads back, breadth-first
+class MCTS {
+public:
+    explicit MCTS(mz_worker* w)
+    {
+        const int n = mz_worker_tree_size(w, 0);
+        if (n < 0) { std::cerr << mz_last_error() << std::endl; std::abort(); }
+        std::vector<int> parent(n), ordinal(n), action(n), player(n), nc(n);
+        std::vector<float> f[7];
+        for (auto& v : f) { v.resize(n); }
+        if (mz_worker_tree(w, 0, n, parent.data(), ordinal.data(), action.data(), player.data(), nc.data(), nullptr, f[0].data(), f[1].data(), f[2].data(), f[3].data(),
+                           f[4].data(), f[5].data(), f[6].data()) != n) {
+            std::cerr << mz_last_error() << std::endl;
+            std::abort();
+        }
+        nodes_.resize(n);
+        for (int e = 0; e < n; ++e) {
+            MCTSNode& x = nodes_[e];
+            x.action_ = Action(action[e], static_cast<env::Player>(player[e]));
+            x.num_children_ = nc[e]; x.ordinal_ = ordinal[e];
+            x.count_ = f[0][e]; x.mean_ = f[1][e]; x.policy_ = f[2][e]; x.policy_logit_ = f[3][e]; x.policy_noise_ = f[4][e]; x.value_ = f[5][e]; x.reward_ = f[6][e];
+            x.tree_ = this;
+            if (e > 0) { MCTSNode& p = nodes_[parent[e]]; if (p.num_kept_++ == 0) { p.first_kept_ = e; } } // the children of one parent are contiguous
+        }
+    }
+    MCTS(const MCTS&) = delete;
+    MCTS& operator=(const MCTS&) = delete;
+
+    inline const MCTSNode* getRootNode() const { return &nodes_[0]; }
+    inline int getNumSimulation() const { return static_cast<int>(nodes_[0].getCount()); } // ref mcts.h:100
+    inline int getNumNodes() const { return static_cast<int>(nodes_.size()); }               // nodes of the snapshot
+    std::string toString(const std::string& env_string) const // ref tree.h:79-87
+    {
+        std::ostringstream oss;
+        oss << env_string.substr(0, env_string.size() - 1) << "C[" << getRootNode()->toString() << "]" << getTreeInfo_r(getRootNode()) << ")";
+        return oss.str();
+    }
+    std::string getTreeInfo_r(const MCTSNode* node) const // ref tree.h:89-110; an expanded child has been visited, so isLeaf() is counted over the kept ones
+    {
+        std::ostringstream oss;
+        int numChildren = 0;
+        for (int k = 0; k < node->num_kept_; ++k) { if (!nodes_[node->first_kept_ + k].isLeaf()) { ++numChildren; } }
+        for (int k = 0; k < node->num_kept_; ++k) {
+            const MCTSNode* child = &nodes_[node->first_kept_ + k];
+            if (!child->displayInTreeLog()) { continue; }
+            if (numChildren > 1) { oss << "("; }
+            oss << env::playerToChar(child->getAction().getPlayer()) << "[" << child->getAction().getActionID() << "]"
+                << "C[" << child->toString() << "]" << getTreeInfo_r(child);
+            if (numChildren > 1) { oss << ")"; }
+        }
+        return oss.str();
+    }
+    std::string getSearchDistributionString() const // ref mcts.cpp:126-137
+    {
+        const MCTSNode* root = getRootNode();
+        std::ostringstream oss;
+        for (int k = 0; k < root->num_kept_; ++k) {
+            const MCTSNode* child = &nodes_[root->first_kept_ + k];
+            if (child->getCount() == 0) { continue; }
+            oss << (oss.str().empty() ? "" : ",") << child->getAction().getActionID() << ":" << child->getCount();
+        }
+        return oss.str();
+    }
+    const MCTSNode* selectChildByMaxCount(const MCTSNode* node) const // ref mcts.cpp:91-104 (an unvisited child never has the largest count)
+    {
+        float max_count = 0.0f;
+        const MCTSNode* selected = nullptr;
+        for (int k = 0; k < node->num_kept_; ++k) {
+            const MCTSNode* child = &nodes_[node->first_kept_ + k];
+            if (child->getCount() <= max_count) { continue; }
+            max_count = child->getCount();
+            selected = child;
+        }
+        return selected;
+    }
+
+private:
+    friend class MCTSNode;
+    std::vector<MCTSNode> nodes_;
+};
+
+inline const MCTSNode* MCTSNode::getChild(int index) const
+{
+    for (int k = 0; k < num_kept_; ++k) {
+        const MCTSNode* c = &tree_->nodes_[first_kept_ + k];
+        if (c->ordinal_ == index) { return c; }
+        if (c->ordinal_ > index) { break; }
+    }
+    return nullptr;
+}
 
 class BaseActor {
 public:
@@ -360,6 +494,15 @@ public:
             << ", player: " << env::playerToChar(a.getPlayer()) << (isResign() ? " (resign)" : "") << std::endl;
         return oss.str();
     }
+    // the two node dumps of ZeroActor::handleSearchDone (ref zero_actor.cpp:173-174); valid once the search is done
+    std::string getSearchNodeInfo() const
+    {
+        std::ostringstream oss;
+        oss << "  root node info: " << nodeInfo(0) << std::endl << "action node info: " << nodeInfo(1) << std::endl;
+        return oss.str();
+    }
+    // ref zero_actor.h:62-63: here a host snapshot of the visited tree, taken at the call (see the header comment)
+    std::shared_ptr<const MCTS> getMCTS() const { return std::make_shared<const MCTS>(handle()); }
     void setNetwork(const std::shared_ptr<network::Network>& network) override // ref zero_actor.cpp:100-112
     {
         if (!network || !network->handle()) { std::cerr << "setNetwork: null network (call loadModel first)" << std::endl; std::abort(); }
@@ -386,6 +529,14 @@ protected:
         check(mz_worker_run_cycles(handle(), cyclesPerMove() + 1));
     }
     int cyclesPerMove() const { return mz_worker_cycles_per_move(handle()); }
+    std::string nodeInfo(int which) const
+    {
+        const int need = mz_worker_node_info(handle(), 0, which, nullptr, 0);
+        check(need);
+        std::vector<char> buf(static_cast<size_t>(need) + 1);
+        check(mz_worker_node_info(handle(), 0, which, buf.data(), static_cast<int>(buf.size())));
+        return buf.data();
+    }
     static constexpr int kThinkFirst = 2;  // cycles of the first call under a think-time limit (the root's expansion precedes any decision)
     static constexpr int kThinkChunk = 64; // ... and the most cycles between two looks at the clock
     uint64_t tree_node_size_;

@@ -258,6 +258,23 @@ int mz_worker_env_legal_mask(const mz_worker* w, int game, uint8_t* out, int cap
 int mz_worker_env_set_turn(mz_worker* w, int game, int player);
 int mz_worker_env_reset_seed(mz_worker* w, int game, int seed);
 int mz_worker_env_rotate_action(const mz_worker* w, int game, int action_id, int rotation);
+/* The visited search tree of game `game`, read back from the node pool by a kernel of its own (what Tree::toString, MCTS and the node dumps of
+ * ZeroActor::handleSearchDone show in the reference: ref actor/tree.h:79-110, mcts.cpp:63-75, zero_actor.cpp:159-176).  Entries are the root (entry 0) and every
+ * node with count > 0 (MCTSNode::displayInTreeLog, ref mcts.h:27), breadth-first, the children of one parent contiguous and in child order; unvisited children
+ * are not read back (num_children still reports how many a node has).  At most actor_num_simulation + 2 entries.
+ * Valid with mz_manual_step=true at every return of mz_worker_run_cycles — mid-search, after the last cycle, after mz_worker_finish_search, also under the
+ * batched think — until mz_worker_reset_search starts the next search; it reports what the pool holds and does not disturb the search.  Without mz_manual_step
+ * the worker has already played on: MZ_ERR_STATE.  A game index out of range: MZ_ERR_ARG.
+ *   mz_worker_tree_size     the number of entries
+ *   mz_worker_tree          the entries into caller buffers of `cap` entries each (any may be NULL); returns the entry count, MZ_ERR_CAPACITY (the message names the
+ *                           needed size) if cap is too small.  parent = entry index (-1 for the root), ordinal = index among the parent's children
+ *   mz_worker_tree_string   Tree::toString(env_string) with env_string = the record as mz_worker_peek_record gives it; returns the length (buf == NULL: length only)
+ *   mz_worker_node_info     MCTSNode::toString() of the root (which = 0) or of the node the decision chose (which = 1: only once the search is done) */
+int mz_worker_tree_size(mz_worker* w, int game);
+int mz_worker_tree(mz_worker* w, int game, int cap, int* parent, int* ordinal, int* action, int* player, int* num_children, int* depth, float* count, float* mean,
+                   float* policy, float* logit, float* noise, float* value, float* reward);
+int mz_worker_tree_string(mz_worker* w, int game, char* buf, int cap);
+int mz_worker_node_info(mz_worker* w, int game, int which, char* buf, int cap);
 typedef struct mz_worker_stats {
     uint64_t cycles, leaf_evals, moves, games;
     double ms_select, ms_env, ms_forward, ms_expand, ms_move, ms_total;

@@ -15,6 +15,7 @@
 #include "pool.h"
 #include "go_dev.h"
 #include "think.h"
+#include "tree_read.h"
 #include "gumbel.h"
 #include "host_threads.h"
 #include <pthread.h>
@@ -124,6 +125,10 @@ public:
     int popLine(char* buf, int cap);
     int waitLines();
     int peekRecord(int game, char* buf, int cap, const char* const* keys = nullptr, const char* const* values = nullptr, int ntags = 0);
+    // the visited tree of a game as the pool holds it (tree_read.h): arrays, Tree::toString's SGF, and the node texts of ZeroActor::handleSearchDone
+    int treeSnapshot(int g, TreeSnapshot* out);
+    int treeString(int g, char* buf, int cap);
+    int nodeInfo(int g, int which, char* buf, int cap);
     // per-actor stepping (mz_manual_step=true): BaseActor / ZeroActor surface (ref actor/base_actor.h:16-55, zero_actor.h:24-70)
     bool searchDone() const { return search_done_; }
     int searchAction(int g, int* action_id, int* player, int* resign) const;
@@ -174,6 +179,7 @@ private:
         Net* net = nullptr;            // the lane's network: its own (own_net) or the caller's (mz_worker_create_shared)
         std::unique_ptr<Net> own_net;
         Pool pool;
+        std::unique_ptr<TreeReader> tree; // created with the lane's first read-out
         hipStream_t stream = nullptr;
         PinBuf<float> h_feat, h_out;
         PinBuf<uint8_t> h_raw;   // raw root observations (muzero_atari: bytes up, planes expanded on the device)
@@ -2067,6 +2073,98 @@ int Worker::peekRecord(int game, char* buf, int cap, const char* const* keys, co
     return len;
 }
 
+// The read-out of game g's visited tree.  Valid under mz_manual_step at every return of mz_worker_run_cycles — mid-search, after the last cycle, after
+// finish_search, until reset_search starts the next search —, also under the batched think (between two steps no virtual loss is outstanding).  It reports what
+// the pool holds and changes nothing: one kernel and three copies on the lane's stream, behind whatever the last cycle queued.
+int Worker::treeSnapshot(int g, TreeSnapshot* out)
+{
+    if (g < 0 || g >= G_) { setError("tree: game %d out of range", g); return MZ_ERR_ARG; }
+    if (!cfg_.mz_manual_step) { setError("tree: the worker plays on its own (mz_manual_step=false)"); return MZ_ERR_STATE; }
+    Lane& L = laneOf(g);
+    if (!L.tree) {
+        if (!createTreeReader) { setError("tree: this build has no device code for the read-out"); return MZ_ERR_DEVICE; }
+        std::unique_ptr<TreeReader> r(createTreeReader());
+        int rc = r->init(device_, L.stream, L.pool, n_ + 2); // n + 1 simulations visit at most n + 1 nodes besides the root
+        if (rc) { return rc; }
+        L.tree = std::move(r);
+    }
+    return L.tree->read(L.pool, g - L.g0, out);
+}
+
+namespace {
+
+std::string nodeText(const TreeSnapshot& t, int e) // MCTSNode::toString (ref mcts.cpp:63-75)
+{
+    std::ostringstream oss;
+    oss.precision(4);
+    oss << std::fixed << "p = " << t.frow(kTrPolicy)[e] << ", p_logit = " << t.frow(kTrLogit)[e] << ", p_noise = " << t.frow(kTrNoise)[e] << ", v = " << t.frow(kTrValue)[e]
+        << ", r = " << t.frow(kTrReward)[e] << ", mean = " << t.frow(kTrMean)[e] << ", count = " << t.frow(kTrCount)[e];
+    return oss.str();
+}
+
+int copyOut(const std::string& s, char* buf, int cap, const char* what)
+{
+    const int len = static_cast<int>(s.size());
+    if (!buf) { return len; } // size query
+    if (cap <= len) { setError("%s: buffer of %d bytes too small for %d", what, cap, len); return MZ_ERR_CAPACITY; }
+    memcpy(buf, s.data(), len);
+    buf[len] = 0;
+    return len;
+}
+
+} // namespace
+
+// Tree::toString(env_string) (ref tree.h:79-110) from the read-out.  The kept children of an entry are contiguous and in child order, so the recursion of
+// getTreeInfo_r is a walk over [first[e], first[e + 1]).  An expanded child has been visited, so it is among the kept ones: isLeaf() can be counted there.
+int Worker::treeString(int g, char* buf, int cap)
+{
+    TreeSnapshot t;
+    int rc = treeSnapshot(g, &t);
+    if (rc) { return rc; }
+    flushDeferred();
+    const std::string env_string = record(games_[g], ActionInfo());
+    const int n = t.entries;
+    const int *parent = t.irow(kTrParent), *action = t.irow(kTrAction), *player = t.irow(kTrPlayer), *nc = t.irow(kTrNumChildren);
+    std::vector<int> first(n + 1, n), expanded(n, 0);
+    for (int e = n - 1; e >= 1; --e) { first[parent[e]] = e; if (nc[e] > 0) { ++expanded[parent[e]]; } }
+    for (int e = n - 1; e >= 0; --e) { if (first[e] == n) { first[e] = first[e + 1]; } } // no kept children: an empty range
+    std::ostringstream oss;
+    oss << env_string.substr(0, env_string.size() - 1) << "C[" << nodeText(t, 0) << "]";
+    // the recursion without the stack of calls: (entry, next child, end)
+    struct Frame { int e, c, end; };
+    std::vector<Frame> st;
+    st.push_back({0, first[0], first[1]});
+    while (!st.empty()) {
+        Frame& f = st.back();
+        const bool paren = expanded[f.e] > 1;
+        if (f.c > first[f.e] && paren) { oss << ")"; } // the child before this one is complete
+        if (f.c == f.end) { st.pop_back(); continue; }
+        const int c = f.c++;
+        if (paren) { oss << "("; }
+        oss << (player[c] == 0 ? 'N' : player[c] == 1 ? 'B' : player[c] == 2 ? 'W' : '?') << "[" << action[c] << "]C[" << nodeText(t, c) << "]";
+        st.push_back({c, first[c], first[c + 1]});
+    }
+    oss << ")";
+    return copyOut(oss.str(), buf, cap, "tree_string");
+}
+
+// which = 0: the root node's text; 1: the text of the node the decision chose (selected_node_, ref zero_actor.cpp:173-174), once the search is done
+int Worker::nodeInfo(int g, int which, char* buf, int cap)
+{
+    if (which != 0 && which != 1) { setError("node_info: which = %d (0 root, 1 action node)", which); return MZ_ERR_ARG; }
+    TreeSnapshot t;
+    int rc = treeSnapshot(g, &t);
+    if (rc) { return rc; }
+    if (which == 0) { return copyOut(nodeText(t, 0), buf, cap, "node_info"); }
+    if (!search_done_) { setError("node_info: the search is not complete"); return MZ_ERR_STATE; }
+    const int sel = games_[g].selected;
+    for (int e = 1; e < t.entries && t.irow(kTrParent)[e] == 0; ++e) {
+        if (t.irow(kTrOrdinal)[e] == sel) { return copyOut(nodeText(t, e), buf, cap, "node_info"); }
+    }
+    setError("node_info: the chosen root child %d of game %d has no visits and is not read back", sel, g);
+    return MZ_ERR_STATE;
+}
+
 // load_model with the file's content in hand (Network::loadModel of every network of this worker, ref actor_group.cpp:227-232, network.h:18-37)
 int Worker::loadModel(const std::string& path, const mz_net_desc& file_desc, const float* weights, size_t count)
 {
@@ -2231,6 +2329,37 @@ int mz_worker_peek_record(mz_worker* w, int game, char* buf, int cap)
 {
     if (!w) { mz::setError("NULL argument"); return MZ_ERR_ARG; }
     return w->w.peekRecord(game, buf, cap);
+}
+int mz_worker_tree_size(mz_worker* w, int game)
+{
+    if (!w) { mz::setError("NULL worker"); return MZ_ERR_ARG; }
+    mz::TreeSnapshot t;
+    int rc = w->w.treeSnapshot(game, &t);
+    return rc ? rc : t.entries;
+}
+int mz_worker_tree(mz_worker* w, int game, int cap, int* parent, int* ordinal, int* action, int* player, int* num_children, int* depth, float* count, float* mean,
+                   float* policy, float* logit, float* noise, float* value, float* reward)
+{
+    if (!w) { mz::setError("NULL worker"); return MZ_ERR_ARG; }
+    mz::TreeSnapshot t;
+    int rc = w->w.treeSnapshot(game, &t);
+    if (rc) { return rc; }
+    if (cap < t.entries) { mz::setError("tree: buffers of %d entries, %d needed", cap, t.entries); return MZ_ERR_CAPACITY; }
+    int* io[mz::kTreeInts] = {parent, ordinal, action, player, num_children, depth};
+    float* fo[mz::kTreeFloats] = {count, mean, policy, logit, noise, value, reward};
+    for (int r = 0; r < mz::kTreeInts; ++r) { if (io[r]) { memcpy(io[r], t.irow(r), t.entries * sizeof(int)); } }
+    for (int r = 0; r < mz::kTreeFloats; ++r) { if (fo[r]) { memcpy(fo[r], t.frow(r), t.entries * sizeof(float)); } }
+    return t.entries;
+}
+int mz_worker_tree_string(mz_worker* w, int game, char* buf, int cap)
+{
+    if (!w) { mz::setError("NULL worker"); return MZ_ERR_ARG; }
+    return w->w.treeString(game, buf, cap);
+}
+int mz_worker_node_info(mz_worker* w, int game, int which, char* buf, int cap)
+{
+    if (!w) { mz::setError("NULL worker"); return MZ_ERR_ARG; }
+    return w->w.nodeInfo(game, which, buf, cap);
 }
 int mz_worker_record(mz_worker* w, int game, const char* const* keys, const char* const* values, int ntags, char* buf, int cap)
 {

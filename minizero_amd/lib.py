@@ -152,6 +152,11 @@ def load():
         L.mz_worker_reset_search.argtypes = [vp]
         L.mz_worker_finish_search.argtypes = [vp]
         L.mz_worker_peek_record.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
+        if hasattr(L, "mz_worker_tree"):  # (MZ_LIBMZGPU may name a build from before the tree read-out: an A/B run of bench.py measures one)
+            L.mz_worker_tree_size.argtypes = [vp, C.c_int]
+            L.mz_worker_tree.argtypes = [vp, C.c_int, C.c_int] + [ip] * 6 + [fp] * 7
+            L.mz_worker_tree_string.argtypes = [vp, C.c_int, C.c_char_p, C.c_int]
+            L.mz_worker_node_info.argtypes = [vp, C.c_int, C.c_int, C.c_char_p, C.c_int]
         L.mz_worker_net.restype = vp
         L.mz_worker_net.argtypes = [vp]
         L.mz_env_create.restype = vp
@@ -541,6 +546,33 @@ class Worker:
 
     def finish_search(self):
         _check(self.L, self.L.mz_worker_finish_search(self.h))
+
+    TREE_INTS = ("parent", "ordinal", "action", "player", "num_children", "depth")
+    TREE_FLOATS = ("count", "mean", "policy", "logit", "noise", "value", "reward")
+
+    def tree(self, game):
+        """The visited tree of a game as the pool holds it (mz_worker_tree; mz_manual_step): a dict of numpy arrays, one entry per node with
+        count > 0 plus the root (entry 0), breadth-first, the children of one parent contiguous and in child order.  `parent` is an entry
+        index (-1 for the root), `ordinal` the index among the parent's children; unvisited children are not read back."""
+        cap = self.cycles_per_move() + 1  # n + 2 entries hold every tree of n + 1 simulations: one read-out, no size query first
+        out = {k: np.zeros(cap, np.int32) for k in self.TREE_INTS}
+        out.update({k: np.zeros(cap, np.float32) for k in self.TREE_FLOATS})
+        n = _check(self.L, self.L.mz_worker_tree(self.h, game, cap, *[_i(out[k]) for k in self.TREE_INTS], *[_f(out[k]) for k in self.TREE_FLOATS]))
+        return {k: v[:n].copy() for k, v in out.items()}
+
+    def _string(self, call, *args):
+        need = _check(self.L, call(self.h, *args, None, 0))
+        buf = C.create_string_buffer(need + 1)
+        _check(self.L, call(self.h, *args, buf, len(buf)))
+        return buf.value.decode()
+
+    def tree_string(self, game):
+        """Tree::toString(record of the game) of the reference (mz_worker_tree_string): the SGF of the visited tree"""
+        return self._string(self.L.mz_worker_tree_string, game)
+
+    def node_info(self, game, which):
+        """MCTSNode::toString() of the root (which = 0) or of the node the decision chose (which = 1, once the search is done)"""
+        return self._string(self.L.mz_worker_node_info, game, which)
 
     def net(self):
         return Net(self.desc, None, handle=self.L.mz_worker_net(self.h))

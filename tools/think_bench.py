@@ -5,6 +5,9 @@ lock-step otherwise (--b1-extra :mz_sim_kernel=false).  Another build of the lib
 from before the batched think ignores the key: measure it with --B 1).
 
     python tools/think_bench.py --board 9 --n 1600 --B 1,8,16,32,64 --runs 5 --tag new
+
+--tree adds "tree_ms": the wall time of one read-out of the visited tree (Worker.tree: the read-out kernel twice, for the size and for the entries, and the
+copies) after each of the timed thinks, and "tree_entries", the entries it returned.
 """
 import argparse
 import json
@@ -25,6 +28,7 @@ def main():
     ap.add_argument("--blocks", type=int, default=6)
     ap.add_argument("--channels", type=int, default=64)
     ap.add_argument("--tag", default="new")
+    ap.add_argument("--tree", action="store_true", help="also time one read-out of the visited tree after every think")
     ap.add_argument("--b1-extra", default="", help="configuration keys added for B = 1 only, e.g. :mz_sim_kernel=false where the simulation kernel has no room for n")
     a = ap.parse_args()
     s = a.board
@@ -35,7 +39,7 @@ def main():
                 f":zero_num_threads=1:actor_mcts_think_batch_size={B}" + (a.b1_extra if B == 1 else ""))
         wk = mz.Worker(conf, d, w)
         wk.command("start")
-        ms = []
+        ms, tree_ms, tree_entries = [], [], 0
         for run in range(a.runs + 1):  # the first think warms up (code objects, buffers)
             wk.reset_search()
             t0 = time.perf_counter()
@@ -43,10 +47,18 @@ def main():
                 wk.run_cycles(a.n + 2)
             if run:
                 ms.append(round((time.perf_counter() - t0) * 1e3, 3))
+            if a.tree:
+                t1 = time.perf_counter()
+                tree_entries = len(wk.tree(0)["parent"])
+                if run:
+                    tree_ms.append(round((time.perf_counter() - t1) * 1e3, 3))
         steps, walks, queries = wk.think_stats() if hasattr(wk.L, "mz_worker_think_stats") else (0, 0, 0)
         sim_launches = wk.stats()["sim_launches"]
         wk.close()
-        print(json.dumps(dict(tag=a.tag, board=s, n=a.n, B=B, extra=a.b1_extra if B == 1 else "", sim_launches=sim_launches, ms=ms, steps=steps, walks=walks, queries=queries)), flush=True)
+        row = dict(tag=a.tag, board=s, n=a.n, B=B, extra=a.b1_extra if B == 1 else "", sim_launches=sim_launches, ms=ms, steps=steps, walks=walks, queries=queries)
+        if a.tree:
+            row.update(tree_ms=tree_ms, tree_entries=tree_entries)
+        print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":
