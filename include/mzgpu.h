@@ -371,6 +371,8 @@ int mz_env_name(const mz_env* e, char* out, int cap);
  * towers * members workgroups must fit the device at once; members of tower t are the workgroups t, t + towers, ..).  out [towers][64][81] the
  * last layer's activations, xcc_out [towers * members] XCC_ID + 1 of every workgroup, *err_flag_out the error flag of the exchanges (0: none),
  * *status_out 0, or 1: the members of a tower do not share an XCD — found out before any member waits for another; no exchange is run then.
+ * mz_tail_tower_tile: the 16 pixels (-1: a padding column) of MFMA pixel tile `tile` (0 .. 5) of that tower, as its kernels' tile map has them; the pair
+ * tower hands the accumulator of tile 2 from one wave to another in mid-chain (sim_help.h).
  * ------------------------------------------------------------------------------------------ */
 int mz_godev_playout(int device, int board_size, float komi, const int* actions, int count, int root_prefix, const int* rots,
                      uint32_t* feat_out, uint8_t* legal_out, int* terminal_out, float* eval_out, int* player_out);
@@ -384,6 +386,7 @@ int mz_sort_candidates(int device, const float* policy, int n, int* order_out);
 int mz_invert_values_device(int device, const float* values, int n, float* out);
 int mz_exp_tanh_device(int device, const float* x, int n, float* exp_out, float* tanh_out);
 int mz_tail_towers_device(mz_net* net, const uint32_t* bits, int towers, int members, float* out, uint32_t* xcc_out, int* err_flag_out, int* status_out);
+int mz_tail_tower_tile(int tile, int* pixels_out);
 
 #ifdef __cplusplus
 }

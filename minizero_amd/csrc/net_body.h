@@ -122,18 +122,27 @@ __device__ __forceinline__ PixSet<NT> makePixSet(int lane, int tile0)
 // (the geometry of the LDS planes as template arguments: CS = plane stride, PW = row stride of the padded plane, DUMP = a spare float of every plane that lanes of
 // padding columns write, P = pixels per sample in `gout` — the board kernels pass those of one padded H x W board, sim_rounds.hip those of several boards
 // stacked in one plane)
-template <int CS, int PW, int DUMP, int P, int CG, int NT, int CGN, bool CORNER, bool NTW = false, bool XOUT = false>
+// TAP0 / TAP1, ACC_IN, EPI (the split chain of the pair tower, sim_help.h): the layer runs taps [TAP0, TAP1) only.  ACC_IN: the chain does not start at +0 but
+// at `*accio`, the accumulator another wave has brought up to tap TAP0; EPI = false: no epilogue, the accumulator goes to `*accio` instead.  With a_first /
+// have_first it is tap TAP0 that the caller has fetched.  The defaults are the whole layer: every instantiation without them is the code it was.
+template <int CS, int PW, int DUMP, int P, int CG, int NT, int CGN, bool CORNER, bool NTW = false, bool XOUT = false, int TAP0 = 0, int TAP1 = 9, bool ACC_IN = false,
+          bool EPI = true>
 __device__ __forceinline__ void tower_layer_geo(const float* __restrict__ tin, const float* __restrict__ tskip, float* __restrict__ tout,
                                             float* __restrict__ gout, const float* __restrict__ wp, const float* __restrict__ bias, int cout, int OT,
                                             int lane, int ot, const PixSet<NT>& px, bool have_first, float (&a_first)[CG],
-                                            const float* __restrict__ next_wp, float (&a_next)[CGN], float* __restrict__ xout = nullptr, unsigned xsign = 0)
+                                            const float* __restrict__ next_wp, float (&a_next)[CGN], float* __restrict__ xout = nullptr, unsigned xsign = 0,
+                                            f32x4* __restrict__ accio = nullptr)
 {
+    static_assert(TAP0 >= 0 && TAP0 < TAP1 && TAP1 <= 9, "taps [TAP0, TAP1)");
+    static_assert((!ACC_IN && EPI) || NT == 1, "a chain that is handed over is a wave's only one");
+    constexpr int TL = TAP1 - 1; // the last tap: the epilogue's inputs and the next layer's first fragments are fetched in front of it
     const int (&pixoff)[NT] = px.off;
     const int (&pixdst)[NT] = px.dst;
     const int (&pixq)[NT] = px.q;
     f32x4 acc[NT];
 #pragma unroll
     for (int j = 0; j < NT; ++j) { acc[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f}; }
+    if constexpr (ACC_IN) { acc[0] = *accio; }
     const float4 bias4 = *reinterpret_cast<const float4*>(bias + 16 * ot + 4 * (lane >> 4)); // the 4 output channels of this lane's accumulators
     const float biasv[4] = {bias4.x, bias4.y, bias4.z, bias4.w};
     // A-fragments in the interleaved layout of weights.cpp (w4_off): for (tap, oc-tile) CG * 64 contiguous floats
@@ -173,7 +182,7 @@ __device__ __forceinline__ void tower_layer_geo(const float* __restrict__ tin, c
 #pragma unroll
         for (int cg = 0; cg < CG; ++cg) {
             float bn[NT];
-            if (cg + 1 < CG) { bload(bn, t, cg + 1); } else if (t < 8) { bload(bn, t + 1, 0); }
+            if (cg + 1 < CG) { bload(bn, t, cg + 1); } else if (t < TL) { bload(bn, t + 1, 0); }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
@@ -185,7 +194,7 @@ __device__ __forceinline__ void tower_layer_geo(const float* __restrict__ tin, c
             for (int j = 0; j < NT; ++j) { bc[j] = bn[j]; }
         }
     };
-    bload(bc, 0, 0);
+    bload(bc, TAP0, 0);
     MZ_TPROF(0);
     // A narrow layer (the stem of a board-game tower: 18-20 input planes = 5 k-groups per tap) has 480 cycles of MFMAs per tap and wave, less than an L2 round
     // trip: double-buffered by tap it waits for its fragments at every tap (the stem of BASELINE configs[1]: 12.6 k cycles for 7.8 k of MFMAs).  Its nine taps
@@ -194,29 +203,36 @@ __device__ __forceinline__ void tower_layer_geo(const float* __restrict__ tin, c
     float aall[kAllTaps ? 9 : 1][CG];
     if constexpr (kAllTaps) {
 #pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            if (t == 0 && have_first) {
+        for (int t = TAP0; t < TAP1; ++t) {
+            if (t == TAP0 && have_first) {
 #pragma unroll
-                for (int cg = 0; cg < CG; ++cg) { aall[0][cg] = a_first[cg]; }
+                for (int cg = 0; cg < CG; ++cg) { aall[TAP0][cg] = a_first[cg]; }
             } else {
                 loadA(aall[t], t);
             }
         }
 #pragma unroll
-        for (int t = 0; t < 8; ++t) { tap(aall[t], t); }
+        for (int t = TAP0; t < TL; ++t) { tap(aall[t], t); }
     } else {
     if (have_first) {
 #pragma unroll
         for (int cg = 0; cg < CG; ++cg) { a0[cg] = a_first[cg]; }
     } else {
-        loadA(a0, 0);
+        loadA(a0, TAP0);
     }
+    if constexpr (TAP0 == 0 && TAP1 == 9) {
 #pragma unroll
     for (int t = 0; t < 8; t += 2) {
         loadA(a1, t + 1);
         tap(a0, t);
         loadA(a0, t + 2);
         tap(a1, t + 1);
+    }
+    } else { // a part of the layer: tap t in a0 if t - TAP0 is even, in a1 if odd
+#pragma unroll
+    for (int t = TAP0; t < TL; ++t) {
+        if ((t - TAP0) & 1) { loadA(a0, t + 1); tap(a1, t); } else { loadA(a1, t + 1); tap(a0, t); }
+    }
     }
     }
     if (next_wp) { // the next layer's first tap (its block of this wave's oc-tile): in flight during the last tap, the epilogue and the barrier
@@ -236,14 +252,17 @@ __device__ __forceinline__ void tower_layer_geo(const float* __restrict__ tin, c
     const float* sk = has_skip ? tskip : tin;
     const int ocb = 16 * ot + 4 * (lane >> 4); // the 4 output channels of this lane's accumulators: ocb .. ocb + 3
     float skv[NT][4];
+    if constexpr (EPI) {
 #pragma unroll
     for (int j = 0; j < NT; ++j) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { skv[j][r] = sk[(ocb + r) * CS + pixdst[j]]; }
     }
     asm volatile("" ::: "memory");
-    if constexpr (kAllTaps) { tap(aall[8], 8); } else { tap(a0, 8); }
+    }
+    if constexpr (kAllTaps) { tap(aall[TL], TL); } else if constexpr (((TL - TAP0) & 1) != 0) { tap(a1, TL); } else { tap(a0, TL); }
     MZ_TPROF(1);
+    if constexpr (!EPI) { *accio = acc[0]; return; }
     if (gout) { // stand-alone launch, last layer: NCHW to HBM
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
@@ -278,14 +297,15 @@ __device__ __forceinline__ void tower_layer_geo(const float* __restrict__ tin, c
     MZ_TPROF(2);
 }
 
-template <int H, int W, int CG, int NT, int CGN, bool CORNER, bool NTW = false, bool XOUT = false>
+template <int H, int W, int CG, int NT, int CGN, bool CORNER, bool NTW = false, bool XOUT = false, int TAP0 = 0, int TAP1 = 9, bool ACC_IN = false, bool EPI = true>
 __device__ __forceinline__ void tower_layer(const float* __restrict__ tin, const float* __restrict__ tskip, float* __restrict__ tout,
                                             float* __restrict__ gout, const float* __restrict__ wp, const float* __restrict__ bias, int cout, int OT,
                                             int lane, int ot, const PixSet<NT>& px, bool have_first, float (&a_first)[CG],
-                                            const float* __restrict__ next_wp, float (&a_next)[CGN], float* __restrict__ xout = nullptr, unsigned xsign = 0)
+                                            const float* __restrict__ next_wp, float (&a_next)[CGN], float* __restrict__ xout = nullptr, unsigned xsign = 0,
+                                            f32x4* __restrict__ accio = nullptr)
 {
-    tower_layer_geo<planeStride(H, W), W + 2, (H + 2) * (W + 2), H * W, CG, NT, CGN, CORNER, NTW, XOUT>(tin, tskip, tout, gout, wp, bias, cout, OT, lane, ot, px, have_first,
-                                                                                                       a_first, next_wp, a_next, xout, xsign);
+    tower_layer_geo<planeStride(H, W), W + 2, (H + 2) * (W + 2), H * W, CG, NT, CGN, CORNER, NTW, XOUT, TAP0, TAP1, ACC_IN, EPI>(
+        tin, tskip, tout, gout, wp, bias, cout, OT, lane, ot, px, have_first, a_first, next_wp, a_next, xout, xsign, accio);
 }
 
 // the layer sequence of one wave: oc-tile `ot` x the NT pixel tiles from `tile0` (CORNER: the last of them is the corner tile); T0 = the

@@ -757,8 +757,10 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     }
     // Tail help (sim_help.h): the 9x9 x 64 f32 instance, at most one workgroup per CU (a helper must never keep a game from starting), not with MZ_NO_SPEC=32.
     // The blocks are part of the argument block whenever the pool qualifies; whether a LAUNCH helps is a launch argument (bit 1 of host_start): only launches of
-    // at least kSimHelpMinLaunch simulations do (of the 1 + 16 + 383 of a BASELINE configs[1] move the last one) — in a short launch the games finish
-    // within a few simulations of each other and there is no tail to fill.  MZ_SIM_HELP_MIN=k (tests, experiments): launches of >= k simulations help, and a
+    // at least kSimHelpMinLaunch simulations do (of the 1 + 16 + 383 of a BASELINE configs[1] move the last one).  Help in the 16-simulation launch was measured and
+    // is no gain (MZ_SIM_HELP_MIN=16 against the default, five alternating bench.py runs each, profiles/r20_ab_pair_split.txt): ms_forward 60.69 - 60.80 against
+    // 60.63 - 60.74 per move, means + 0.10 %; on the build with the split pair chains + 0.07 %.  The launch model had promised - 0.18 ms: what a claim and the
+    // cleared help blocks cost in a launch of 2.7 ms is not in the model.  MZ_SIM_HELP_MIN=k (tests, experiments): launches of >= k simulations help, and a
     // game is claimed while it has >= min(k, kSimHelpMinLeft) simulations left.
     bool help = false;
     if (tail_help_ && !bf && !(a.no_spec & 32) && H == 9 && W == 9 && c0 == 20 && C == 64 && a.ta.OT == 4 && gv.n == 9 && gv.kind == kGo && gv.games >= 2 && gv.games <= cu_count_ &&
@@ -791,6 +793,12 @@ int Net::simLaunch(Pool& pool, const GoDevView& gv, float* d_policy, float* d_lo
     size_t lds = tile_bytes + size_t(a.rcp_n) * sizeof(double) +
                        (two_per_cu ? 0 : size_t(a.rcp_n) * (sizeof(double) + sizeof(float)) + kSpecWords * sizeof(int)) + (simXchgWords(gv.A, gv.channels, gv.W32) + 2 + 2 * size_t(pool.v_.max_depth) + 2) * sizeof(float) +
                        ((gv.kind == kGo && !two_per_cu) ? size_t(kGoSeenCap) * sizeof(uint64_t) + ((goLeafSmemBytes(gv, pool.v_.max_depth) + 7) & ~size_t(7)) : 0);
+    // the hand-over slot of the pair tower's split chains (sim_help.h): part of the plan of every launch whose argument block has the help blocks, on 16 bytes
+    if (a.help) {
+        const size_t off = (lds + 15) & ~size_t(15);
+        a.pair_slot = static_cast<int>(off / sizeof(float));
+        lds = off + kHpSlotFloats * sizeof(float);
+    }
     // sim_kernel<9,9,20,64,2>: the block of launch-invariant head weights behind everything else, on 16 bytes (net_body.h HeadsAhead) — if the network's heads are of
     // the shape the body is written for and the block still fits; otherwise (or with MZ_SIM_HEADS_LDS=0: tests) the launch keeps the old heads and the old figure
     if (!bf && !two_per_cu && H == 9 && W == 9 && c0 == 20 && C == 64 && gv.n == 9 && rulesArg(gv.kind, gv.n) == 2 && HeadsAhead::shape(a.hp) &&

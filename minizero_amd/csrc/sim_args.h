@@ -70,6 +70,8 @@ struct SimArgs {
     // sim_kernel<9,9,20,64,2>: word offset, from the start of the dynamic LDS, of the block of launch-invariant head weights (net_body.h HeadsAhead); 0: the launch
     // has none (no room in the LDS, another head shape, MZ_SIM_HEADS_LDS=0) and runs headsBody.  Last, so that no other field moves.
     int heads_lds;
+    // ... and of the hand-over slot of the pair tower's split chains (sim_help.h kHpSlotFloats), set whenever `help` is.  Behind everything else for the same reason.
+    int pair_slot;
 };
 
 // SimArgs never changes during a launch: the device functions read it through the CONSTANT address space, i.e. with scalar loads whose

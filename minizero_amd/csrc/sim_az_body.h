@@ -604,7 +604,7 @@ __device__ __forceinline__ const float* simTowerHelped(CSimArgs* __restrict__ a,
         u.w = hpCmdWord(unsigned(seq), MODE, xseq, lent);
         asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(hb + kHpCmd + 4 * tid), "v"(u) : "memory");
     }
-    HelpCtx c{hb, 0, xseq, abort_lds, a->err};
+    HelpCtx c{hb, 0, xseq, abort_lds, a->err, tiles + a->pair_slot};
     if constexpr (MODE == kHpModeQuad) { return towerBodyQuad<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c); }
     else { return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c); }
 }
@@ -637,7 +637,7 @@ __device__ __noinline__ bool simHelpTower(CSimArgs* __restrict__ a, int o, int m
     o = __builtin_amdgcn_readfirstlane(o);
     member = __builtin_amdgcn_readfirstlane(member);
     xseq = __builtin_amdgcn_readfirstlane(xseq);
-    HelpCtx c{a->help + size_t(o) * a->help_words, member, xseq, abort_lds, a->err};
+    HelpCtx c{a->help + size_t(o) * a->help_words, member, xseq, abort_lds, a->err, tiles + a->pair_slot};
     if constexpr (MODE == kHpModeQuad) { return towerBodyQuad<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c) != nullptr; }
     else { return towerBodyPair<H, W, CIN0_PAD, CPAD>(bits, a->params, *(const TowerArgs*)&a->ta, tid, tiles, c) != nullptr; }
 }

@@ -11,6 +11,19 @@
 //    self-validating words (the phase of the exchange in the sign bit of the ReLU outputs) and loads past the vector cache; after the last layer only the owner reads;
 //  * the owner tells the helper what to compute with 16-byte stores that each carry the simulation's sequence number (three words of the leaf's bit-packed
 //    planes + the sequence number), so the helper needs no other input and never touches the tree.
+//    No whole (oc-tile, pixel-tile) dealing gets below 3 x 144 = 432 MFMAs on one SIMD (20 full units over 8 SIMDs), where the work is 392 per SIMD.  So ONE chain
+//    per oc-tile is split: SIMDs s and s + 1 (s = 0, 2) share oc-tile 2 m + s / 2.  On SIMD s the low wave has tiles {0, 1}, its partner (wave s + 4) brings tile
+//    2 up to tap kPairCut = 6 — 96 MFMAs, no epilogue —, stores its f32x4 accumulator to a slot in LDS (64 lanes x 16 bytes per oc-tile) and publishes the number
+//    of the layer behind it (hpHandOut).  On SIMD s + 1 the low wave has tiles {3, 4}; its partner runs the corner tile's chain and epilogue as before (64 MFMAs),
+//    polls for the layer's number, takes the accumulator (hpHandIn) and runs taps 6 .. 8 of tile 2 in the same k order (48 MFMAs) and that tile's epilogue:
+//    384 and 400 MFMAs per SIMD and layer, and every output is still the one tap-major, k-ordered chain (tower_layer_geo TAP0 / TAP1 / ACC_IN / EPI).
+//    The wait cannot hang: the first wave waits for nobody before it publishes, both waves belong to one resident workgroup, the poll is bounded (kHpPollLimit
+//    rounds of s_sleep; then the abort flag and kHpErrHand are raised and the exchange behind the layer makes the workgroup leave).  The two barriers of the
+//    exchange lie between one use of the slot and the next; the words are cleared at the start of a tower and the layers count from 1, so a word left by an earlier
+//    layer or tower never matches.  Measured (profiles/r20_pair_split_tower.txt): 93.35 -> 88.0 us per pair tower.
+//    (Tried beside it and dropped: waves that are done with their epilogue polling for the other member's half at once instead of behind the exchange's first
+//    barrier — the planes they write are read by nobody during the layer.  89.8 us against 88.8: the early polls cost the waves that still compute more than
+//    they take off the end of the layer.)
 // Every wait is bounded; a time-out raises the pool's error flag and both sides leave the kernel.  No workgroup waits for one that is not running: a helper only
 // claims a game that has published its XCC_ID in this launch, an owner only waits for a helper that has claimed it.
 //
@@ -70,7 +83,12 @@ constexpr int kHpMaxUnits = 32;
 constexpr int kHpMaxGames = 1024; // games of a launch that helps (simLaunch's gate): simHelpTail and simLendScan pack (progress << 10) | game into one search key
 constexpr int kHpErrQuad = 98, kHpErrQuadCmd = 99; // error flags: a quad tower's exchange timed out (95: the pair's), the holder of slot 2 or 3 saw no command (96: slot 1)
 constexpr int kHpErrLend = 100;                    // a volunteer saw neither the command of the offer it had claimed nor its withdrawal
+constexpr int kHpErrHand = 101;                    // pair tower: the second wave of a split chain did not see the first wave's accumulator
 constexpr int kHpModePair = 0, kHpModeQuad = 1;
+// the hand-over slot of the pair tower's split chains, in the LDS of each member: per oc-tile of the member 64 lanes x 16 bytes of accumulator, behind them one
+// sequence word per oc-tile (kHpSlotFloats keeps what follows on 16 bytes)
+constexpr int kHpSlotAcc = 2 * 64 * 4, kHpSlotFloats = kHpSlotAcc + 4;
+constexpr int kPairCut = 6; // the first wave of a split chain runs taps [0, kPairCut), the second wave the rest
 // the last word of every command unit: the simulation's sequence number (1 ..), whether the command is for a volunteer (lending) or for the holders of the helper
 // slots, the tower's mode and the exchange count it starts at (its two low bits: hpPart and hpSign use no others); a unit is valid when all units of the command
 // carry the same word
@@ -103,7 +121,37 @@ struct HelpCtx {
     unsigned xseq;  // layer exchanges of this game so far in this launch
     int* abort_lds; // workgroup-wide abort flag
     int* err;
+    float* slot = nullptr; // pair tower: kHpSlotFloats floats of LDS, 16-byte aligned (the quad tower has no use for it)
 };
+
+// The hand-over of a split chain's accumulator between two waves of a member (towerBodyPair): the first wave stores its lanes' f32x4 and, behind them, the
+// layer's number; the second wave polls for that number — bounded, kHpErrHand — and takes the accumulator.  The word is cleared at the start of every tower and a
+// tower's layers count 1, 2, ..: a word left by an earlier layer or tower never matches.
+typedef __attribute__((address_space(3))) f32x4 HpLdsAcc;
+typedef __attribute__((address_space(3))) unsigned HpLdsWord;
+__device__ __forceinline__ void hpHandOut(const HelpCtx& c, int half, int lane, const f32x4& acc, unsigned seq)
+{
+    ((HpLdsAcc*)c.slot)[half * 64 + lane] = acc;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    if (lane == 0) { __hip_atomic_store((HpLdsWord*)c.slot + kHpSlotAcc + half, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+}
+__device__ __forceinline__ bool hpHandIn(const HelpCtx& c, int half, int lane, f32x4& acc, unsigned seq)
+{
+    HpLdsWord* w = (HpLdsWord*)c.slot + kHpSlotAcc + half;
+    unsigned seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    for (int i = 0; i < kHpPollLimit && seen != seq; ++i) {
+        __builtin_amdgcn_s_sleep(1);
+        seen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    if (seen != seq) {
+        if (lane == 0) { *c.abort_lds = 1; atomicExch(c.err, kHpErrHand); }
+        return false;
+    }
+    acc = ((HpLdsAcc*)c.slot)[half * 64 + lane];
+    return true;
+}
 
 // my 16 x P block of the exchange buffer for the NEXT exchange, and the tag its words carry (the two buffers alternate, the phase flips each time a buffer is
 // reused; the host clears them: phase 0 = "never written", the first use writes 1)
@@ -185,6 +233,79 @@ __device__ __forceinline__ bool pairRun(const float* __restrict__ params, const 
     return true;
 }
 
+// The split chain of pixel tile 2 (towerBodyPair), first wave: taps [0, kPairCut) of every layer, no epilogue — the accumulator goes to the slot of oc-tile half
+// `half` of the member.  The wave waits for nobody but the exchanges.
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __forceinline__ bool pairRunHead(const float* __restrict__ params, const TowerArgs& ta, float* __restrict__ T0, float* __restrict__ T1, int lane, int tid, int ot,
+                                            int half, HelpCtx& c)
+{
+    const PixSet<1> px = makePixSet<H, W, 1>(lane, 2);
+    float aS[CIN0_PAD / 4], aA[CPAD / 4], aB[CPAD / 4];
+    bool have = false;
+    f32x4 acc;
+    if (ta.has_stem) {
+        const float* nw = ta.nlayers > 1 ? params + ta.w_off[1] : nullptr;
+        tower_layer<H, W, CIN0_PAD / 4, 1, CPAD / 4, false, false, true, 0, kPairCut, false, false>(T0, nullptr, T1, nullptr, params + ta.w_off[0], params + ta.b_off[0], ta.C, ta.OT,
+                                                                                                    lane, ot, px, false, aS, nw, aA, nullptr, 0u, &acc);
+        hpHandOut(c, half, lane, acc, 1u);
+        have = nw != nullptr;
+        if (!hpExchange<H, W, CPAD>(c, T1, tid, c.member == 0 || ta.nlayers > 1)) { return false; }
+    }
+    float *x = T1, *tmp = T0;
+#pragma unroll 1
+    for (int l = ta.has_stem; l < ta.nlayers; ++l) {
+        const bool second = ((l - ta.has_stem) & 1) != 0, last = l + 1 == ta.nlayers;
+        tower_layer<H, W, CPAD / 4, 1, CPAD / 4, false, false, true, 0, kPairCut, false, false>(second ? tmp : x, second ? x : nullptr, second ? x : tmp, nullptr, params + ta.w_off[l],
+                                                                                                params + ta.b_off[l], ta.C, ta.OT, lane, ot, px, have, aA,
+                                                                                                last ? nullptr : params + ta.w_off[l + 1], aB, nullptr, 0u, &acc);
+        hpHandOut(c, half, lane, acc, unsigned(l) + 1u);
+#pragma unroll
+        for (int cg = 0; cg < CPAD / 4; ++cg) { aA[cg] = aB[cg]; }
+        have = !last;
+        if (!hpExchange<H, W, CPAD>(c, second ? x : tmp, tid, c.member == 0 || !last)) { return false; }
+    }
+    return true;
+}
+
+// ... second wave: the corner tile's chain of the layer as before, then taps [kPairCut, 9) of pixel tile 2 on the first wave's accumulator, in the same k order,
+// and that tile's epilogue.  The fragments of tap kPairCut are fetched during the corner chain's last tap (the layer function's look-ahead, pointed at this layer's
+// own weights), so the wait for the accumulator hides their round trip.  A wait that times out leaves the tile undone: the abort flag is up, and the exchange
+// behind the layer returns false.
+template <int H, int W, int CIN0_PAD, int CPAD>
+__device__ __forceinline__ bool pairRunCornerTail(const float* __restrict__ params, const TowerArgs& ta, float* __restrict__ T0, float* __restrict__ T1, int lane, int tid, int ot,
+                                                  int half, HelpCtx& c)
+{
+    constexpr int P = H * W;
+    const PixSet<1> pxc = makePixSet<H, W, 1>(lane, 5), pxt = makePixSet<H, W, 1>(lane, 2);
+    float nS[CIN0_PAD / 4], cutS[CIN0_PAD / 4], nA[CPAD / 4], cutA[CPAD / 4]; // (nS, nA: never read — the corner chain starts without fragments, the rest fetches none ahead)
+    f32x4 acc;
+    if (ta.has_stem) {
+        const float* wl = params + ta.w_off[0];
+        tower_layer<H, W, CIN0_PAD / 4, 1, CIN0_PAD / 4, true, false, true>(T0, nullptr, T1, nullptr, wl, params + ta.b_off[0], ta.C, ta.OT, lane, ot, pxc, false, nS,
+                                                                            wl + size_t(kPairCut) * ta.OT * (CIN0_PAD / 4) * 64, cutS, hpPart<CPAD, P>(c, ot), hpSign(c));
+        if (hpHandIn(c, half, lane, acc, 1u)) {
+            tower_layer<H, W, CIN0_PAD / 4, 1, CPAD / 4, false, false, true, kPairCut, 9, true, true>(T0, nullptr, T1, nullptr, wl, params + ta.b_off[0], ta.C, ta.OT, lane, ot, pxt, true,
+                                                                                                      cutS, nullptr, nA, hpPart<CPAD, P>(c, ot), hpSign(c), &acc);
+        }
+        if (!hpExchange<H, W, CPAD>(c, T1, tid, c.member == 0 || ta.nlayers > 1)) { return false; }
+    }
+    float *x = T1, *tmp = T0;
+#pragma unroll 1
+    for (int l = ta.has_stem; l < ta.nlayers; ++l) {
+        const bool second = ((l - ta.has_stem) & 1) != 0, last = l + 1 == ta.nlayers;
+        const float* wl = params + ta.w_off[l];
+        tower_layer<H, W, CPAD / 4, 1, CPAD / 4, true, false, true>(second ? tmp : x, second ? x : nullptr, second ? x : tmp, nullptr, wl, params + ta.b_off[l], ta.C, ta.OT, lane, ot,
+                                                                    pxc, false, nA, wl + size_t(kPairCut) * ta.OT * (CPAD / 4) * 64, cutA, hpPart<CPAD, P>(c, ot), hpSign(c));
+        if (hpHandIn(c, half, lane, acc, unsigned(l) + 1u)) {
+            tower_layer<H, W, CPAD / 4, 1, CPAD / 4, false, false, true, kPairCut, 9, true, true>(second ? tmp : x, second ? x : nullptr, second ? x : tmp, nullptr, wl,
+                                                                                                  params + ta.b_off[l], ta.C, ta.OT, lane, ot, pxt, true, cutA, nullptr, nA,
+                                                                                                  hpPart<CPAD, P>(c, ot), hpSign(c), &acc);
+        }
+        if (!hpExchange<H, W, CPAD>(c, second ? x : tmp, tid, c.member == 0 || !last)) { return false; }
+    }
+    return true;
+}
+
 // shapes the pair tower covers: 4 oc-tiles (two per member), 6 pixel tiles the last of which is the corner tile (9x9)
 template <int H, int W, int CPAD>
 constexpr bool pairTowerShape() { return CPAD == 64 && TileMap<H, W>::PT == 6 && TileMap<H, W>::kCorner; }
@@ -193,8 +314,9 @@ constexpr bool pairTowerShape() { return CPAD == 64 && TileMap<H, W>::PT == 6 &&
 // its two oc-tiles of every layer and swaps them with the other member; the owner ends with the complete output x in its tile T1 (returned), the helper with all
 // but the owner's half of the last layer.  nullptr: aborted.
 // Waves w and w + 4 share a SIMD.  SIMD s works on oc-tile 2 m + s / 2: the wave of the lower half takes two full pixel tiles (0, 1 or 3, 4), its partner one
-// (tile 2, or the corner tile 5) with the higher priority, like the wave with fewer accumulator chains of the solo tower (net_body.h towerBody): at most
-// 3 x 144 = 432 MFMAs per SIMD and layer instead of 784.
+// (the first six taps of tile 2; or the corner tile 5 and then the last three taps of tile 2 — the split chain of the header comment) with the higher priority,
+// like the wave with fewer accumulator chains of the solo tower (net_body.h towerBody): at most 400 MFMAs per SIMD and layer instead of 784.
+// c.slot: kHpSlotFloats floats of LDS outside the tiles.
 template <int H, int W, int CIN0_PAD, int CPAD>
 __device__ __forceinline__ float* towerBodyPair(const unsigned* __restrict__ bits, const float* __restrict__ params, const TowerArgs& ta, int tid, float* __restrict__ tiles,
                                                 HelpCtx& c)
@@ -206,6 +328,7 @@ __device__ __forceinline__ float* towerBodyPair(const unsigned* __restrict__ bit
     float* T0 = tiles;
     float* T1 = tiles + CMAX * CS;
     for (int i = tid; i < kTowerTiles * CMAX * CS / 4; i += 512) { reinterpret_cast<float4*>(tiles)[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
+    if (tid < 2) { ((HpLdsWord*)c.slot)[kHpSlotAcc + tid] = 0u; } // the sequence words of the hand-over: a tower's layers count from 1
     __syncthreads();
     float* Tin = ta.has_stem ? T0 : T1;
     for (int i = tid; i < ta.cin0 * P; i += 512) {
@@ -219,8 +342,8 @@ __device__ __forceinline__ float* towerBodyPair(const unsigned* __restrict__ bit
         ok = pairRun<H, W, CIN0_PAD, CPAD, 2, false>(params, ta, T0, T1, lane, tid, ot, 3 * grp, c);
     } else {
         __builtin_amdgcn_s_setprio(2);
-        if (grp == 0) { ok = pairRun<H, W, CIN0_PAD, CPAD, 1, false>(params, ta, T0, T1, lane, tid, ot, 2, c); }
-        else { ok = pairRun<H, W, CIN0_PAD, CPAD, 1, true>(params, ta, T0, T1, lane, tid, ot, 5, c); }
+        if (grp == 0) { ok = pairRunHead<H, W, CIN0_PAD, CPAD>(params, ta, T0, T1, lane, tid, ot, simd >> 1, c); }
+        else { ok = pairRunCornerTail<H, W, CIN0_PAD, CPAD>(params, ta, T0, T1, lane, tid, ot, simd >> 1, c); }
         __builtin_amdgcn_s_setprio(0);
     }
     return ok ? T1 : nullptr;

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     }
     if (tid < a.fw) { s_bits[tid] = a.bits[size_t(tower) * a.fw + tid]; }
     __syncthreads();
-    HelpCtx c{a.help + size_t(tower) * a.help_words, member, 0u, &s_abort, a.err};
+    HelpCtx c{a.help + size_t(tower) * a.help_words, member, 0u, &s_abort, a.err, tiles + kTowerTiles * 64 * planeStride(H, W)}; // (the slot: behind the tiles)
     const float* xt;
     if constexpr (NM == 4) { xt = towerBodyQuad<H, W, C0, C>(s_bits, a.params, ta, tid, tiles, c); }
     else if constexpr (NM == 2) { xt = towerBodyPair<H, W, C0, C>(s_bits, a.params, ta, tid, tiles, c); }
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
 template <int NM>
 static int launchTailTowers(const TailTowersArgs& a, const TowerArgs& ta, int wgs, hipStream_t s)
 {
-    constexpr size_t lds = size_t(kTowerTiles) * 64 * planeStride(9, 9) * sizeof(float);
+    constexpr size_t lds = (size_t(kTowerTiles) * 64 * planeStride(9, 9) + kHpSlotFloats) * sizeof(float);
     MZ_LDS_ATTR((tail_towers_kernel<NM>), lds);
     hipLaunchKernelGGL((tail_towers_kernel<NM>), dim3(wgs), dim3(512), lds, s, a, ta);
     MZ_HIP(hipGetLastError());
@@ -120,4 +120,11 @@ extern "C" int mz_tail_towers_device(mz_net* net, const uint32_t* bits, int towe
 {
     if (!net || !bits || !out || !xcc_out || !err_flag_out || !status_out) { mz::setError("mz_tail_towers_device: bad arguments"); return MZ_ERR_ARG; }
     return net->net.tailTowers(bits, towers, members, out, xcc_out, err_flag_out, status_out);
+}
+extern "C" int mz_tail_tower_tile(int tile, int* pixels_out)
+{
+    constexpr mz::TileMap<9, 9> tm{};
+    if (tile < 0 || tile >= mz::TileMap<9, 9>::PT || !pixels_out) { mz::setError("mz_tail_tower_tile: bad arguments"); return MZ_ERR_ARG; }
+    for (int n = 0; n < 16; ++n) { pixels_out[n] = tm.q[tile * 16 + n]; }
+    return MZ_OK;
 }

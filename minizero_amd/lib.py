@@ -777,6 +777,15 @@ def tail_towers(net, bits, members):
     return out, xcc, err.value, status.value
 
 
+def tail_tower_tile(tile):
+    """The pixels (0 .. 80; -1: a padding column) of MFMA pixel tile `tile` of the 9x9 tower, read from the tile map its kernels are compiled with."""
+    L = load()
+    L.mz_tail_tower_tile.argtypes = [C.c_int, C.POINTER(C.c_int)]
+    q = np.zeros(16, np.int32)
+    _check(L, L.mz_tail_tower_tile(tile, _i(q)))
+    return q
+
+
 def sort_candidates(policy, device=0):
     """Order of candidates under the reference's std::sort(policy descending), computed by the device path."""
     L = load()

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 4))) voi
     if (tid == 0) { s_abort = 0; a.xcc[blockIdx.x] = hpXccId(); }
     if (tid < 18 * W32) { s_bits[tid] = a.in[sample * 18 * W32 + tid]; }
     __syncthreads();
-    HelpCtx c{a.help + size_t(sample) * a.help_words, member, 0u, &s_abort, a.err};
+    HelpCtx c{a.help + size_t(sample) * a.help_words, member, 0u, &s_abort, a.err, tiles + kTowerTiles * 64 * planeStride(H, W)}; // (the hand-over slot: behind the tiles)
     const unsigned long long t0 = wall_clock64();
     const float* xt = nullptr;
     for (int it = 0; it < a.iters; ++it) {
@@ -93,7 +93,7 @@ int main(int argc, char** argv)
     CK(hipMalloc(&a.ticks, wgs * 8));
     CK(hipMalloc(&a.xcc, wgs * 4));
     CK(hipMalloc(&a.err, 4)); CK(hipMemset(a.err, 0, 4));
-    const size_t lds = size_t(kTowerTiles) * 64 * planeStride(H, W) * 4;
+    const size_t lds = (size_t(kTowerTiles) * 64 * planeStride(H, W) + kHpSlotFloats) * 4;
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(tower_loop<1>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(tower_loop<2>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(tower_loop<4>), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
