@@ -187,6 +187,38 @@ mz_worker* mz_worker_create(int device, const char* conf, const mz_net_desc* des
  * worker's next search sees; the worker's own `load_model <path>` then only renames (EV tag).  One host thread drives the worker and the
  * network (they share the network's stream). */
 mz_worker* mz_worker_create_shared(int device, const char* conf, mz_net* net);
+
+/* External evaluator: the worker searches on the CALLER's network — any code that fills a policy, its logits and a value from the feature planes
+ * (Network::pushBack / forward are all the reference's actors know of a network, ref actor_group.cpp createNeuralNetworks).  AlphaZero, lock-step, device
+ * rules; one cycle is: select, leaf planes, export into `features`, wait, forward(user, rows), import of the outputs, candidate lists, expand + backup.
+ *   forward   called once per lock-step cycle on the thread that called mz_worker_run_cycles, rows = zero_num_parallel_games.  The planes of every game's
+ *             current leaf are complete in `features` (the worker has waited for its stream), with the cycle's feature rotation; rows of terminal leaves are
+ *             evaluated and ignored.  The outputs must be complete when it returns 0 (the caller synchronises its own stream).  A non-zero return abandons the
+ *             cycle before anything of it reaches a tree: mz_worker_run_cycles returns MZ_ERR_STATE (the text names the value), and so does every later call.
+ *   features  device, [games][C][H][W] of feature_dtype, planes not padded.  NULL: the library allocates all four buffers (policy included, f32 / f32)
+ *             and mz_worker_evaluator_buffers names them.
+ *   policy    device, [games][A] of output_dtype, or NULL: policy = softmax(logits) computed by the library with its heads' own arithmetic
+ *   logits    device, [games][A];  value: device, [games], in game scale (what AlphaZeroNetworkOutput::value_ holds)
+ * desc: only type (0), num_input_channels, input_channel_height / width and action_size are read and checked against the game.  Refused by name
+ * (MZ_ERR_ARG, "external evaluator"): MuZero, a game without device rules, mz_device_env=false, more games than one resident lane holds,
+ * mz_pipeline_lanes=2, actor_mcts_think_batch_size > 1, mz_nn_precision other than f32.  `load_model <path>` only renames (EV tag). */
+#define MZ_F32 0
+#define MZ_F16 1
+#define MZ_BF16 2
+typedef struct mz_evaluator {
+    int (*forward)(void* user, int rows);
+    void* user;
+    void* features;
+    const void* policy;
+    const void* logits;
+    const void* value;
+    int feature_dtype, output_dtype;
+} mz_evaluator;
+mz_worker* mz_worker_create_external(int device, const char* conf, const mz_net_desc* desc, const mz_evaluator* ev);
+/* the pointers in use (library-owned ones included; policy is NULL where the library computes it); any argument may be NULL */
+int mz_worker_evaluator_buffers(mz_worker* w, void** features, void** policy, void** logits, void** value);
+/* test access: the worker's own f32 policy [games][A] as the last import left it for the search, copied to the host (waits for the worker's stream) */
+int mz_worker_evaluator_lane_policy(mz_worker* w, float* out, int capacity);
 void mz_worker_destroy(mz_worker* w);
 /* one stdin line: start | stop | load_model <path> | update_config k=v:.. | reset_actors | quit | other (ignored)
  * (ref actor_group.cpp:200-252).  load_model <path> reads the file itself (mz_net_read_weight_file) and checks that its hyper-parameters

@@ -12,6 +12,7 @@
 #include "config.h"
 #include "env.h"
 #include "net.h"
+#include "ext_eval.h"
 #include "pool.h"
 #include "go_dev.h"
 #include "think.h"
@@ -111,7 +112,10 @@ public:
     }
     int counted_device_ = -1;
     // shared != nullptr: the worker runs on the caller's network (BaseActor::setNetwork's shared_ptr, ref zero_actor.cpp:100-112) instead of its own copy
-    int init(int device, const char* conf, const mz_net_desc& desc, const float* weights, size_t count, Net* shared = nullptr);
+    // ext != nullptr: no network at all — the caller's code evaluates the leaves (mz_worker_create_external, ext_eval.h)
+    int init(int device, const char* conf, const mz_net_desc& desc, const float* weights, size_t count, Net* shared = nullptr, const mz_evaluator* ext = nullptr);
+    int evaluatorBuffers(void** features, void** policy, void** logits, void** value) const;
+    int evaluatorLanePolicy(float* out, int capacity);
     int command(const std::string& line);
     int loadModel(const std::string& path, const mz_net_desc& file_desc, const float* weights, size_t count);
     int setWeights(const float* w, size_t n)
@@ -158,6 +162,7 @@ public:
         *out = stats_;
         MZ_HIP(hipSetDevice(device_));
         for (auto& L : lanes_) {
+            if (!L->net) { continue; } // external evaluator: no simulation kernels, nothing evaluated ahead
             unsigned hits = 0, evals = 0, alt = 0;
             int rc = L->net->simPreStats(&hits, &evals, &alt);
             if (rc) { return rc; }
@@ -167,6 +172,7 @@ public:
         return MZ_OK;
     }
     Net& net0() { return *lanes_[0]->net; }
+    Net* netOrNull() { return lanes_[0]->net; } // null: the worker runs on an external evaluator
 
 private:
     // A lane = a contiguous slice of the games with its own device pool, network instance, HIP stream and staging.
@@ -181,6 +187,7 @@ private:
         Pool pool;
         std::unique_ptr<TreeReader> tree; // created with the lane's first read-out
         hipStream_t stream = nullptr;
+        hipStream_t own_stream = nullptr; // external evaluator: there is no network whose stream the lane could share
         PinBuf<float> h_feat, h_out;
         PinBuf<uint8_t> h_raw;   // raw root observations (muzero_atari: bytes up, planes expanded on the device)
         DevBuf<uint8_t> d_raw;
@@ -227,12 +234,21 @@ private:
             for (int k = 0; k < kSimParts; ++k) { if (ev0[k]) { (void)hipEventDestroy(ev0[k]); } if (ev1[k]) { (void)hipEventDestroy(ev1[k]); } }
             if (ev_up) { (void)hipEventDestroy(ev_up); }
             if (up_stream) { (void)hipStreamDestroy(up_stream); }
+            if (own_stream) { (void)hipStreamDestroy(own_stream); }
         }
     };
     Lane& laneOf(int g) { return *lanes_[std::min(g / plan_.lane_size, plan_.lanes - 1)]; }
     int phase1(Lane& L, bool root_expansion, bool done, bool launch_select = true);
     int phase2(Lane& L);
     int phase2Resident(Lane& L);
+    // external evaluator (ext_eval.h): the network step of the resident cycle is a hand-over to the caller's code and back
+    std::unique_ptr<ExtEval> ext_;         // lane 0's (an external worker has one lane)
+    bool external_ = false;
+    mz_evaluator ext_ev_{};
+    int feat_size_ = 0;                    // floats per sample of the feature planes: the network's, or the external evaluator's descriptor's
+    std::string ext_failed_;               // forward() returned non-zero: the text every later run_cycles repeats
+    int extRefusal() const;
+    int extCheckDesc(const GameEnv& e) const;
     int runCyclesSim(int n);
     // batched think (actor_mcts_think_batch_size > 1 under mz_manual_step; think.h): a cycle is one STEP of every game whose search is not done
     int thinkB_ = 1;                       // the batch size in force (1: today's path, untouched)
@@ -371,12 +387,15 @@ private:
 };
 
 // ------------------------------------------------------------------------------------------------
-int Worker::init(int device, const char* conf, const mz_net_desc& desc, const float* weights, size_t count, Net* shared)
+int Worker::init(int device, const char* conf, const mz_net_desc& desc, const float* weights, size_t count, Net* shared, const mz_evaluator* ext)
 {
     if (!conf || !cfg_.loadFromString(conf)) { return MZ_ERR_ARG; }
     desc_ = desc;
     device_ = device;
+    external_ = ext != nullptr;
+    if (external_) { ext_ev_ = *ext; }
     if (device >= 0 && device < 64) { counted_device_ = device; g_workers_on_device[device].fetch_add(1); }
+    if (external_) { int rx = extRefusal(); if (rx) { return rx; } }
     if (cfg_.nn_type_name == "muzero" && desc.type == 0) { setError("nn_type_name=muzero but the network descriptor is alphazero"); return MZ_ERR_ARG; }
     if (gameFromName(cfg_.env_game.c_str()) == kHavannah && (cfg_.nn_type_name != "alphazero" || desc.type != 0)) { // ref havannah.cpp:233-236: getActionFeatures throws
         setError("env_game=havannah has no action features: a MuZero network cannot play it (nn_type_name=alphazero only, ref havannah.cpp:233-236)");
@@ -397,6 +416,7 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     // the first lane's network: the plan asks it which kernels the shape has (at its precision: hasSimKernelWide depends on it)
     int rc = addLane(shared, weights, count);
     if (rc) { return rc; }
+    feat_size_ = external_ ? desc.num_input_channels * desc.input_channel_height * desc.input_channel_width : net0().featSize();
     // the pool spins: never more spinners than CPUs the container may use, minus one for the HIP runtime's helper threads
     threads_ = std::make_unique<ThreadPool>(hostThreads(), cfg_.mz_cpu_base);
     const size_t GA = size_t(G_) * A_;
@@ -417,7 +437,18 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     sc.value_rescale = cfg_.actor_mcts_value_rescale;
     sc.flipping_player = flipping_player_;
     sc.atari_init_q = cfg_.atari_init_q;
+    if (external_ && !plan_.resident) { // (extRefusal and extCheckDesc name every way there: kept for the plan's own conditions)
+        setError("external evaluator: this configuration does not run on the device rules (the resident plan), which the hand-over needs");
+        return MZ_ERR_ARG;
+    }
     for (int l = 0; l < plan_.lanes; ++l) { if ((rc = allocLane(l, sc))) { return rc; } }
+    if (external_) {
+        Lane& L = *lanes_[0];
+        if (!createExtEval) { setError("external evaluator: this build has no device code for the hand-over (ext_eval.hip is not linked)"); return MZ_ERR_DEVICE; }
+        ext_.reset(createExtEval());
+        const GoDevView& gv = L.godev.v_;
+        if ((rc = ext_->init(device_, L.stream, ExtEvalShape{L.n, gv.channels, gv.P, gv.W32, A_}, ext_ev_))) { return rc; }
+    }
     if (plan_.dev_gumbel) { // the constants of gumbel_zero.cpp:101,110 in the host's double arithmetic
         const int m = cfg_.actor_gumbel_sample_size;
         gum_.sample_size = m;
@@ -441,6 +472,36 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     return resetAllSearches();
 }
 
+// mz_worker_create_external: what the hand-over does not cover is refused by name when the worker is created
+int Worker::extRefusal() const
+{
+    if (!ext_ev_.forward) { setError("external evaluator: forward is NULL"); return MZ_ERR_ARG; }
+    if (desc_.type != 0) { setError("desc.type=%d: an external evaluator is an AlphaZero network (type 0; a MuZero one needs the caller to own the hidden states)", desc_.type); return MZ_ERR_ARG; }
+    if (cfg_.nn_type_name != "alphazero") { setError("nn_type_name=%s: an external evaluator is an AlphaZero network (nn_type_name=alphazero)", cfg_.nn_type_name.c_str()); return MZ_ERR_ARG; }
+    if (gameFromName(cfg_.env_game.c_str()) == kNoDeviceGame) { setError("env_game=%s has no rules on the device, which the external evaluator's hand-over needs", cfg_.env_game.c_str()); return MZ_ERR_ARG; }
+    if (!cfg_.mz_device_env) { setError("mz_device_env=false: the external evaluator is handed the leaves of the device rules"); return MZ_ERR_ARG; }
+    if (cfg_.zero_num_parallel_games > kRotPackGames) { setError("zero_num_parallel_games=%d: an external evaluator has one lane of at most %d games", cfg_.zero_num_parallel_games, kRotPackGames); return MZ_ERR_ARG; }
+    if (cfg_.mz_pipeline_lanes >= 2) { setError("mz_pipeline_lanes=%d: an external evaluator is called once per cycle, for one lane", cfg_.mz_pipeline_lanes); return MZ_ERR_ARG; }
+    if (cfg_.actor_mcts_think_batch_size > 1) { setError("actor_mcts_think_batch_size=%d: the batched think does not run on an external evaluator", cfg_.actor_mcts_think_batch_size); return MZ_ERR_ARG; }
+    if (cfg_.mz_nn_precision != "f32") { setError("mz_nn_precision=%s: with an external evaluator the precision is the caller's business (leave the key at f32)", cfg_.mz_nn_precision.c_str()); return MZ_ERR_ARG; }
+    return MZ_OK;
+}
+
+// the four numbers of the descriptor an external evaluator is created with, against the game's engine
+int Worker::extCheckDesc(const GameEnv& e) const
+{
+    if (!e.hasDeviceTwin()) { setError("env_game=%s at env_board_size=%d has no rules on the device, which the external evaluator's hand-over needs", cfg_.env_game.c_str(), cfg_.env_board_size); return MZ_ERR_ARG; }
+    const int planes = gameChannels(e.deviceKind());
+    if (desc_.num_input_channels != planes) { setError("external evaluator: desc.num_input_channels=%d, but %s has %d feature planes", desc_.num_input_channels, e.name().c_str(), planes); return MZ_ERR_ARG; }
+    if (desc_.input_channel_height != e.boardSize() || desc_.input_channel_width != e.boardSize()) {
+        setError("external evaluator: desc.input_channel_height x width = %d x %d, but the planes of %s are %d x %d", desc_.input_channel_height, desc_.input_channel_width,
+                 e.name().c_str(), e.boardSize(), e.boardSize());
+        return MZ_ERR_ARG;
+    }
+    if (desc_.action_size != e.policySize()) { setError("external evaluator: desc.action_size=%d, but the policy of %s has %d actions", desc_.action_size, e.name().c_str(), e.policySize()); return MZ_ERR_ARG; }
+    return MZ_OK;
+}
+
 // actor_mcts_think_batch_size > 1: what the batched think does not cover is refused by name when the worker is created (documented differences)
 int Worker::thinkRefusal() const
 {
@@ -459,6 +520,13 @@ Worker::Plan Worker::resolvePlan(int lanes) const
 {
     Plan p;
     const GameEnv& e = *games_[0].env;
+    if (external_) { // no network to ask: one lane on the device rules, lock-step, the host runs the Gumbel root
+        p.lane_size = G_;
+        p.sim_mode.cluster = false;
+        p.feat_bits = true;
+        p.resident = cfg_.mz_device_env && e.hasDeviceTwin() && G_ <= kRotPackGames;
+        return p;
+    }
     const Net& net = *lanes_[0]->net;
     p.lanes = (G_ < 2 * lanes || shared_net_ || thinkB_ > 1) ? 1 : lanes; // a shared network has one stream: one lane; so has the batched think
     p.lane_size = (G_ + p.lanes - 1) / p.lanes;
@@ -538,6 +606,19 @@ Worker::Plan Worker::resolvePlan(int lanes) const
 int Worker::addLane(Net* shared, const float* weights, size_t count)
 {
     auto L = std::make_unique<Lane>();
+    if (external_) { // no network: a stream of the lane's own
+        int count_dev = 0;
+        if (hipGetDeviceCount(&count_dev) != hipSuccess || device_ < 0 || device_ >= count_dev) {
+            (void)hipGetLastError();
+            setError("no such GPU: device %d of %d (libmzgpu has no CPU path)", device_, count_dev);
+            return MZ_ERR_DEVICE;
+        }
+        MZ_HIP(hipSetDevice(device_));
+        MZ_HIP(hipStreamCreateWithFlags(&L->own_stream, hipStreamNonBlocking));
+        L->stream = L->own_stream;
+        lanes_.push_back(std::move(L));
+        return MZ_OK;
+    }
     if (shared) {
         L->net = shared;
     } else {
@@ -567,7 +648,7 @@ int Worker::allocLane(int l, const mz_search_cfg& sc)
         L.pool.v_.host_path_len = L.pool.h_path_len_.p;
         L.pool.v_.host_path_action = L.pool.h_path_action_.p;
     }
-    const size_t n = L.n, GA = n * A_, feat = n * L.net->featSize(), rb = plan_.raw_bytes, sims = n_ + 1;
+    const size_t n = L.n, GA = n * A_, feat = n * feat_size_, rb = plan_.raw_bytes, sims = n_ + 1;
 #define WALLOC(b, k) \
     if (!(b).alloc(k)) { setError("worker: allocation failed (%s)", #b); return MZ_ERR_DEVICE; }
     WALLOC(L.h_feat, feat); WALLOC(L.d_feat, feat); WALLOC(L.h_out, 2 * GA + 2 * n); WALLOC(L.d_out, 2 * GA + 2 * n);
@@ -680,8 +761,9 @@ int Worker::createActors()
                                                           : cfg_.zero_actor_intermediate_sequence_length + 8 + cfg_.learner_n_step_return + cfg_.learner_muzero_unrolling_step) + 1;
         g.env = createGameEnv(envOptions(cfg_, recent_obs));
         if (!g.env) { return MZ_ERR_ARG; }
-        if (g.env->policySize() != A_ || g.env->featureSize() != net0().featSize()) {
-            setError("network (A=%d, features=%d) does not fit env %s (A=%d, features=%d)", A_, net0().featSize(), g.env->name().c_str(),
+        if (external_ && &g == &games_[0]) { int rx = extCheckDesc(*g.env); if (rx) { return rx; } }
+        if (g.env->policySize() != A_ || g.env->featureSize() != feat_size_) {
+            setError("network (A=%d, features=%d) does not fit env %s (A=%d, features=%d)", A_, feat_size_, g.env->name().c_str(),
                      g.env->policySize(), g.env->featureSize());
             return MZ_ERR_ARG;
         }
@@ -1337,7 +1419,21 @@ int Worker::phase2Resident(Lane& L)
     const int slot = sims_done_; // position slot of this simulation's leaf (slot 0 = the root)
     int rc;
     if ((rc = L.godev.leafAsync(L.pool.v_, L.rot, slot))) { return rc; }
-    if ((rc = L.net->forwardAZ(reinterpret_cast<const float*>(L.godev.v_.feat), L.n, L.d_policy.p, L.d_logit.p, L.d_value.p, true))) { return rc; }
+    if (ext_) {
+        // the hand-over: planes into the caller's tensor, wait, the caller's code (it returns with its outputs complete), its outputs into the lane's
+        if ((rc = ext_->exportAsync(L.godev.v_.feat))) { return rc; }
+        MZ_HIP(hipStreamSynchronize(L.stream));
+        const int frc = ext_ev_.forward(ext_ev_.user, L.n);
+        if (frc != 0) { // nothing of this cycle has reached a tree: the selection and the leaf position only wrote scratch of their own
+            char text[160];
+            snprintf(text, sizeof(text), "external evaluator: forward returned %d; the cycle was abandoned and the worker runs no further cycles", frc);
+            ext_failed_ = text;
+            setError("%s", text);
+            return MZ_ERR_STATE;
+        }
+        MZ_HIP(hipSetDevice(device_)); // (the caller's code may have chosen another device for this thread)
+        if ((rc = ext_->importAsync(L.d_policy.p, L.d_logit.p, L.d_value.p))) { return rc; }
+    } else if ((rc = L.net->forwardAZ(reinterpret_cast<const float*>(L.godev.v_.feat), L.n, L.d_policy.p, L.d_logit.p, L.d_value.p, true))) { return rc; }
     if ((rc = L.godev.candAsync(L.pool, L.d_policy.p, L.d_logit.p, L.d_value.p, L.rot))) { return rc; }
     if ((rc = L.pool.expandBackupAsync(slot, false))) { return rc; }
     // bound the host's run-ahead (kernel-argument ring, launch queue): a completion word every 32 cycles, wait for the one before
@@ -1812,6 +1908,7 @@ int Worker::thinkCycle()
 
 int Worker::runCycles(int n)
 {
+    if (!ext_failed_.empty()) { setError("%s", ext_failed_.c_str()); return MZ_ERR_STATE; }
     if (!running_ || search_done_) { return 0; }
     if (think_) {
         for (int i = 0; i < n; ++i) {
@@ -1838,6 +1935,28 @@ int Worker::runCycles(int n)
         stats_.ms_total += nowMs() - t0;
     }
     return n;
+}
+
+int Worker::evaluatorBuffers(void** features, void** policy, void** logits, void** value) const
+{
+    if (!ext_) { setError("evaluator_buffers: the worker has a network of its own (not created by mz_worker_create_external)"); return MZ_ERR_STATE; }
+    const mz_evaluator& ev = ext_->evaluator();
+    if (features) { *features = ev.features; }
+    if (policy) { *policy = const_cast<void*>(ev.policy); }
+    if (logits) { *logits = const_cast<void*>(ev.logits); }
+    if (value) { *value = const_cast<void*>(ev.value); }
+    return MZ_OK;
+}
+
+int Worker::evaluatorLanePolicy(float* out, int capacity)
+{
+    if (!ext_) { setError("evaluator_lane_policy: the worker has a network of its own (not created by mz_worker_create_external)"); return MZ_ERR_STATE; }
+    Lane& L = *lanes_[0];
+    if (capacity < 0 || size_t(capacity) < L.d_policy.n) { setError("evaluator_lane_policy: buffer of %d floats, %zu needed", capacity, L.d_policy.n); return MZ_ERR_CAPACITY; }
+    MZ_HIP(hipSetDevice(device_));
+    MZ_HIP(hipStreamSynchronize(L.stream));
+    MZ_HIP(hipMemcpy(out, L.d_policy.p, L.d_policy.n * sizeof(float), hipMemcpyDeviceToHost));
+    return MZ_OK;
 }
 
 int Worker::popLine(char* buf, int cap)
@@ -2168,6 +2287,7 @@ int Worker::nodeInfo(int g, int which, char* buf, int cap)
 // load_model with the file's content in hand (Network::loadModel of every network of this worker, ref actor_group.cpp:227-232, network.h:18-37)
 int Worker::loadModel(const std::string& path, const mz_net_desc& file_desc, const float* weights, size_t count)
 {
+    if (external_) { cfg_.nn_file_name = path; return MZ_OK; } // the weights are the caller's: the actor only follows the name (EV tag)
     MZ_HIP(hipSetDevice(device_));
     mz_net_desc a = file_desc, b = desc_;
     a.game_name[sizeof(a.game_name) - 1] = 0;
@@ -2207,7 +2327,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
     } else if (prefix == "load_model") {
         if (line.find(' ') == std::string::npos) { setError("load_model needs a path"); return MZ_ERR_ARG; }
         const std::string path = line.substr(line.find(' ') + 1);
-        if (shared_net_) { // the caller's Network::loadModel has (or will have) reloaded the weights; the actor only follows the name (EV tag)
+        if (shared_net_ || external_) { // the caller's Network::loadModel has (or will have) reloaded the weights; the actor only follows the name (EV tag)
             pending_weights_.clear();
             cfg_.nn_file_name = path;
             return MZ_OK;
@@ -2291,6 +2411,23 @@ mz_worker* mz_worker_create_shared(int device, const char* conf, mz_net* net)
     std::unique_ptr<mz_worker> w(new mz_worker());
     if (w->w.init(device, conf, net->net.desc_, nullptr, 0, &net->net) != MZ_OK) { return nullptr; }
     return w.release();
+}
+mz_worker* mz_worker_create_external(int device, const char* conf, const mz_net_desc* desc, const mz_evaluator* ev)
+{
+    if (!conf || !desc || !ev) { mz::setError("mz_worker_create_external: NULL argument"); return nullptr; }
+    std::unique_ptr<mz_worker> w(new mz_worker());
+    if (w->w.init(device, conf, *desc, nullptr, 0, nullptr, ev) != MZ_OK) { return nullptr; }
+    return w.release();
+}
+int mz_worker_evaluator_buffers(mz_worker* w, void** features, void** policy, void** logits, void** value)
+{
+    if (!w) { mz::setError("NULL worker"); return MZ_ERR_ARG; }
+    return w->w.evaluatorBuffers(features, policy, logits, value);
+}
+int mz_worker_evaluator_lane_policy(mz_worker* w, float* out, int capacity)
+{
+    if (!w || !out) { mz::setError("mz_worker_evaluator_lane_policy: NULL argument"); return MZ_ERR_ARG; }
+    return w->w.evaluatorLanePolicy(out, capacity);
 }
 int mz_worker_cycles_per_move(const mz_worker* w) { return w ? w->w.cyclesPerMove() : MZ_ERR_ARG; }
 int mz_worker_lanes(const mz_worker* w) { return w ? w->w.numLanes() : MZ_ERR_ARG; }
@@ -2447,7 +2584,7 @@ int mz_worker_get_stats(mz_worker* w, mz_worker_stats* out)
     if (!w || !out) { return MZ_ERR_ARG; }
     return w->w.getStats(out);
 }
-mz_net* mz_worker_net(mz_worker* w) { return w ? reinterpret_cast<mz_net*>(&w->w.net0()) : nullptr; }
+mz_net* mz_worker_net(mz_worker* w) { return w ? reinterpret_cast<mz_net*>(w->w.netOrNull()) : nullptr; } // NULL on an external evaluator
 
 mz_env* mz_env_create(const char* conf)
 {

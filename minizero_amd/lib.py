@@ -40,6 +40,16 @@ class WorkerStats(C.Structure):
                 ("pre_batch_launches", C.c_uint64), ("pre_pair_launches", C.c_uint64)]
 
 
+EVAL_FORWARD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)
+
+
+class Evaluator(C.Structure):
+    """mz_evaluator (include/mzgpu.h): the caller's network as the worker sees it"""
+    _fields_ = [("forward", EVAL_FORWARD), ("user", C.c_void_p), ("features", C.c_void_p), ("policy", C.c_void_p), ("logits", C.c_void_p),
+                ("value", C.c_void_p), ("feature_dtype", C.c_int), ("output_dtype", C.c_int)]
+
+
+DTYPES = {"f32": 0, "f16": 1, "bf16": 2}  # MZ_F32, MZ_F16, MZ_BF16
 NET_TYPES = {"alphazero": 0, "muzero": 1, "muzero_atari": 2}
 
 
@@ -178,6 +188,11 @@ def load():
         L.mz_env_name.argtypes = [vp, C.c_char_p, C.c_int]
         L.mz_worker_create_shared.restype = vp
         L.mz_worker_create_shared.argtypes = [C.c_int, C.c_char_p, vp]
+        if hasattr(L, "mz_worker_create_external"):  # (MZ_LIBMZGPU may name a build from before the external evaluator)
+            L.mz_worker_create_external.restype = vp
+            L.mz_worker_create_external.argtypes = [C.c_int, C.c_char_p, C.POINTER(NetDesc), C.POINTER(Evaluator)]
+            L.mz_worker_evaluator_buffers.argtypes = [vp] + [C.POINTER(vp)] * 4
+            L.mz_worker_evaluator_lane_policy.argtypes = [vp, fp, C.c_int]
         L.mz_godev_playout.argtypes = [C.c_int, C.c_int, C.c_float, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
         L.mz_envdev_playout.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_float, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
         L.mz_envdev_playout_conf.argtypes = [C.c_int, C.c_char_p, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
@@ -576,6 +591,107 @@ class Worker:
 
     def net(self):
         return Net(self.desc, None, handle=self.L.mz_worker_net(self.h))
+
+
+def _device_ptr(a, what):
+    """a device pointer for mz_evaluator: a torch CUDA tensor (data_ptr(), as DataLoader._ptr takes them), a raw address, or None"""
+    if a is None:
+        return None
+    if hasattr(a, "data_ptr"):
+        if not (a.is_cuda and a.is_contiguous()):
+            raise MzError(f"ExternalWorker: {what} must be a contiguous CUDA tensor")
+        return a.data_ptr()
+    return int(a)
+
+
+class ExternalWorker(Worker):
+    """A Worker whose network is the caller's code (mz_worker_create_external): every cycle the planes of all games' leaves are written into `features`
+    ([games][C][H][W]), `forward(rows)` is called on the calling thread, and it returns (None or 0) when `logits` [games][A], `value` [games] and — unless
+    it is None: then the library computes softmax(logits) — `policy` [games][A] are complete.  Buffers are torch CUDA tensors or raw device addresses;
+    features=None: the library allocates all four (f32) and buffers() names them.  An exception in `forward` ends the cycle and is raised again from
+    run_cycles; a non-zero return makes run_cycles raise MzError (MZ_ERR_STATE).  After either the worker runs no further cycles.
+    Only type, the input planes' shape and action_size of `desc` are read."""
+
+    def __init__(self, conf, desc, forward, *, features=None, policy=None, logits=None, value=None, feature_dtype="f32", output_dtype="f32", device=0):
+        self.L = load()
+        self.shared = None
+        self.desc = desc
+        self._keep = (features, policy, logits, value)  # the caller's tensors stay alive as long as the worker writes and reads them
+        state = self._state = {"exc": None}
+
+        def trampoline(user, rows):  # no exception may cross the C frames above this one
+            try:
+                rc = forward(rows)
+                return 0 if rc is None else int(rc)
+            except BaseException as e:  # noqa: B036 — KeyboardInterrupt too: it is raised again from run_cycles
+                state["exc"] = e
+                return -1
+
+        self._cb = EVAL_FORWARD(trampoline)
+        ev = Evaluator(self._cb, None, _device_ptr(features, "features"), _device_ptr(policy, "policy"), _device_ptr(logits, "logits"),
+                       _device_ptr(value, "value"), DTYPES[feature_dtype], DTYPES[output_dtype])
+        self.h = self.L.mz_worker_create_external(device, conf.encode(), C.byref(desc), C.byref(ev))
+        if not self.h:
+            raise MzError("mz_worker_create_external failed: " + _err(self.L))
+
+    def run_cycles(self, n):
+        rc = self.L.mz_worker_run_cycles(self.h, n)
+        exc, self._state["exc"] = self._state["exc"], None
+        if exc is not None:
+            raise exc  # the exception `forward` raised, its traceback continued here
+        return _check(self.L, rc)
+
+    def buffers(self):
+        """(features, policy, logits, value): the device addresses in use, library-owned ones included (policy is None where the library computes it)"""
+        p = [C.c_void_p() for _ in range(4)]
+        _check(self.L, self.L.mz_worker_evaluator_buffers(self.h, *[C.byref(x) for x in p]))
+        return tuple(x.value for x in p)
+
+    def lane_policy(self, games):
+        """test access: the worker's own f32 policy [games][A] as the last import left it for the search"""
+        out = np.empty((games, self.desc.action_size), np.float32)
+        _check(self.L, self.L.mz_worker_evaluator_lane_policy(self.h, _f(out), out.size))
+        return out
+
+    def net(self):
+        raise MzError("ExternalWorker: the network is the caller's")
+
+
+class TorchEvaluator:
+    """A torch module as an ExternalWorker's network: the tensors of the hand-over and the callable.  `module(features)` — features [games][C][H][W] of
+    `dtype` on `device` — returns (policy, logits, value) or (logits, value); which of the two is found by one call on empty planes here, and with
+    (logits, value) the library computes the policy.  value is [games] or [games][1], in game scale.  Called under torch.no_grad(); the outputs are copied
+    into the hand-over tensors and the current stream is synchronised.  torch is imported here, not with the package."""
+
+    def __init__(self, module, games, C, H, W, A, dtype="f32", device="cuda"):
+        import torch
+        self.torch, self.module, self.games, self.dtype = torch, module, games, dtype
+        td = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dtype]
+        self.features = torch.zeros((games, C, H, W), dtype=td, device=device)
+        self.logits = torch.zeros((games, A), dtype=td, device=device)
+        self.value = torch.zeros((games,), dtype=td, device=device)
+        with torch.no_grad():
+            arity = len(module(self.features))
+        if arity not in (2, 3):
+            raise MzError(f"TorchEvaluator: the module returns {arity} outputs: (policy, logits, value) or (logits, value) expected")
+        self.policy = torch.zeros((games, A), dtype=td, device=device) if arity == 3 else None
+
+    def __call__(self, rows):
+        torch = self.torch
+        with torch.no_grad():
+            out = self.module(self.features)
+            if self.policy is not None:
+                self.policy.copy_(out[0])
+            self.logits.copy_(out[-2])
+            self.value.copy_(out[-1].reshape(self.games))
+        torch.cuda.current_stream(self.features.device).synchronize()
+        return 0
+
+    def worker(self, conf, desc, device=None):
+        """the ExternalWorker that searches on this evaluator"""
+        dev = self.features.device.index if device is None else device
+        return ExternalWorker(conf, desc, self, features=self.features, policy=self.policy, logits=self.logits, value=self.value,
+                              feature_dtype=self.dtype, output_dtype=self.dtype, device=dev or 0)
 
 
 class DataLoader:
