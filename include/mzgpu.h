@@ -325,7 +325,40 @@ int mz_worker_get_stats(mz_worker* w, mz_worker_stats* out);
    queries, expand + backup per query (ref actor/zero_actor.cpp:129-157).  Counters since the worker was created, summed over its games: steps, walks
    (selections) and queries (walks whose leaf carried no virtual loss: the leaves evaluated).  All three stay 0 with B = 1. */
 int mz_worker_think_stats(mz_worker* w, uint64_t* steps, uint64_t* walks, uint64_t* queries);
+/* the worker's network (lane 0's); NULL on an external evaluator and on a match (whose networks are fixed and take turns: there is no handle to reload) */
 mz_net* mz_worker_net(mz_worker* w);
+
+/* Match play: two weight blobs for ONE descriptor meet on one worker (no reference equivalent: the reference's tools/fight-eval.sh runs two GTP
+ * consoles under an outside referee).  Side 0 is "A" (weights_a), side 1 is "B" (weights_b).  The games are two lanes of G / 2 slots
+ * (G = zero_num_parallel_games); both lanes hold both networks.  With t = the worker's steps (one move of every game each) since `start`, lane h is
+ * searched by side (h + t) mod 2 in step t, and a game that starts in lane h at step t0 has side (h + t0) mod 2 as its first player: a slot freed by a
+ * game of odd length hands the first move to the other side, no slot idles, and all games of a lane share their side to move.  mz_match_games = N
+ * games are counted: a game gets its serial number when it starts, in slot order, while fewer than N have started; a slot that frees up after that
+ * plays an uncounted filler game (searched like any other, never printed, never tallied).  The match is over when the N-th counted game has
+ * finished: mz_worker_run_cycles returns the cycles it ran, then 0.  A counted game's line is the self-play line with first word `Match`, and
+ * its record carries the root tags PB[<first player's side name>]PW[<the other's>] behind DLEN (mz_match_name_a / _b, defaults A / B);
+ * mz_worker_peek_record shows the two tags too.  Each side has its own tower arithmetic: mz_match_precision_a / _b, default mz_nn_precision.
+ * Everything else works as on any worker: `start`, run_cycles, pop_line, peek_record, get_stats.
+ * Refused by name (MZ_ERR_ARG, the text names the key and says "match"): zero_num_parallel_games odd or below 2, mz_match_games below
+ * zero_num_parallel_games, env_game=atari, mz_manual_step=true, actor_mcts_think_batch_size > 1, zero_actor_intermediate_sequence_length > 0, two
+ * precisions that resolve to different execution plans; on the live worker (MZ_ERR_STATE): load_model, mz_worker_set_weights, mz_worker_load_model
+ * and reset_actors — a new match is a new worker; mz_worker_net returns NULL.  A game whose player to move disagrees with the schedule's parity stops the match with MZ_ERR_STATE. */
+mz_worker* mz_worker_create_match(int device, const char* conf, const mz_net_desc* desc, const float* weights_a, size_t count_a, const float* weights_b,
+                                  size_t count_b);
+typedef struct mz_match_stats {
+    uint64_t games_started;   /* counted games that have started (at most mz_match_games) */
+    uint64_t games_finished;  /* ... and finished: a_first[0..2] + a_second[0..2] */
+    uint64_t moves;           /* moves played in counted games */
+    uint64_t filler_games;    /* uncounted games started in slots that freed up after the last counted game had started */
+    uint64_t a_first[3];      /* side A's wins, draws, losses in the games it started (it had the first player's colour) */
+    uint64_t a_second[3];     /* ... and in the games side B started */
+    uint64_t resignations;    /* counted games that ended by resignation */
+    uint64_t steps;           /* the step counter t */
+    int32_t done;             /* 1: the match is over */
+    int32_t reserved;
+} mz_match_stats;
+/* MZ_ERR_STATE on a worker that is not a match */
+int mz_worker_match_stats(mz_worker* w, mz_match_stats* out);
 
 /* ------------------------------------------------------------------------------------------
  * Learner-side sampler.  Replaces learner::DataLoader and its pybind surface (ref learner/data_loader.h:75-93, data_loader.cpp:200-255,

@@ -90,6 +90,11 @@ struct WorkerConfig {
     // Built for AlphaZero networks of 64 hidden channels on 9x9 / 8x8 / 11x11 / 15x15 boards (Go, Othello, Hex, Gomoku, Havannah edge size 8) and of 128 / 256
     // on 9x9 boards; every other network is refused at init (Net::setPrecision)
     std::string mz_nn_precision = "f32";
+    // not reference keys: match play (mz_worker_create_match) — the number of counted games, the two sides' names (the PB / PW tags of a
+    // record) and each side's tower arithmetic ("" = mz_nn_precision).  Read by a match worker only; every other worker ignores them.
+    int mz_match_games = 0;
+    std::string mz_match_name_a = "A", mz_match_name_b = "B";
+    std::string mz_match_precision_a, mz_match_precision_b;
     int mz_zero_copy = 3; // bit 0: kernels read their inputs from pinned host memory; bit 1: kernels write their outputs there
 
     // returns false (and sets the library error string) on an unknown key or an unparsable value,

@@ -166,6 +166,9 @@ public:
 
     mz_net_desc desc_{};
     int device_ = -1;
+    // Every launch and copy of the network goes to stream_ as it is at the time of the call; nothing may keep a copy of it, an event recorded on it or a stream
+    // forked from it across calls (the muzero_atari representation's at_streams_ fork and join inside one call).  A match worker relies on that: it moves side
+    // B's network onto its lane's stream after init (worker.cpp addLane: stream_ replaced, own_stream_ cleared, the stream of init destroyed with the lane).
     hipStream_t stream_ = nullptr;
     bool own_stream_ = false;
     int P() const { return desc_.hidden_channel_height * desc_.hidden_channel_width; }

@@ -61,6 +61,12 @@ struct Game {
     int selected = -1; // index of the chosen root child
     uint64_t raw_seen = ~0ull; // rawSerial() of the observation block last sent to the device
     std::vector<ActionInfo> action_info_history;
+    // match play (mz_worker_create_match): serial number of a counted game (-1: a filler), the step it started at, the side of its first player, and what
+    // the last move did to it — written by handleSearchDone, consumed in slot order by matchAfterMoves
+    int m_serial = -1, m_first_side = 0;
+    uint64_t m_t0 = 0;
+    bool m_acted = false, m_ended = false, m_resigned = false;
+    float m_score = 0.0f;
 };
 
 // optional host-side phase trace (MZ_TRACE=1): prints per-sub-step averages to stderr when the worker is destroyed
@@ -114,12 +120,31 @@ public:
     // shared != nullptr: the worker runs on the caller's network (BaseActor::setNetwork's shared_ptr, ref zero_actor.cpp:100-112) instead of its own copy
     // ext != nullptr: no network at all — the caller's code evaluates the leaves (mz_worker_create_external, ext_eval.h)
     int init(int device, const char* conf, const mz_net_desc& desc, const float* weights, size_t count, Net* shared = nullptr, const mz_evaluator* ext = nullptr);
+    // match play: two weight blobs of one descriptor, side A = (weights, count) of init, side B = these
+    int initMatch(int device, const char* conf, const mz_net_desc& desc, const float* wa, size_t ca, const float* wb, size_t cb)
+    {
+        match_ = true;
+        match_wb_ = wb;
+        match_cb_ = cb;
+        const int rc = init(device, conf, desc, wa, ca);
+        match_wb_ = nullptr; // the caller's buffer: not kept
+        return rc;
+    }
+    int matchStats(mz_match_stats* out) const
+    {
+        if (!match_) { setError("match_stats: the worker is not a match (mz_worker_create_match)"); return MZ_ERR_STATE; }
+        *out = ms_;
+        out->steps = match_t_;
+        out->done = match_done_ ? 1 : 0;
+        return MZ_OK;
+    }
     int evaluatorBuffers(void** features, void** policy, void** logits, void** value) const;
     int evaluatorLanePolicy(float* out, int capacity);
     int command(const std::string& line);
     int loadModel(const std::string& path, const mz_net_desc& file_desc, const float* weights, size_t count);
     int setWeights(const float* w, size_t n)
     {
+        if (match_) { return matchFixed("set_weights"); }
         pending_weights_.assign(w, w + n);
         return MZ_OK;
     }
@@ -163,16 +188,21 @@ public:
         MZ_HIP(hipSetDevice(device_));
         for (auto& L : lanes_) {
             if (!L->net) { continue; } // external evaluator: no simulation kernels, nothing evaluated ahead
-            unsigned hits = 0, evals = 0, alt = 0;
-            int rc = L->net->simPreStats(&hits, &evals, &alt);
-            if (rc) { return rc; }
-            out->pre_hits += hits; out->pre_evals += evals; out->pre_alt_hits += alt;
-            out->pre_pair_launches += L->net->pre_pair_launches_;
+            for (Net* net : {L->net_b ? L->own_net.get() : L->net, L->net_b.get()}) { // (a match: both sides' networks)
+                if (!net) { continue; }
+                unsigned hits = 0, evals = 0, alt = 0;
+                int rc = net->simPreStats(&hits, &evals, &alt);
+                if (rc) { return rc; }
+                out->pre_hits += hits; out->pre_evals += evals; out->pre_alt_hits += alt;
+                out->pre_pair_launches += net->pre_pair_launches_;
+            }
         }
         return MZ_OK;
     }
     Net& net0() { return *lanes_[0]->net; }
-    Net* netOrNull() { return lanes_[0]->net; } // null: the worker runs on an external evaluator
+    // null: the worker runs on an external evaluator — or it is a match: Lane::net changes sides every step and the networks of a match are fixed,
+    // so there is no handle through which mz_net_reload could reach one of them
+    Net* netOrNull() { return match_ ? nullptr : lanes_[0]->net; }
 
 private:
     // A lane = a contiguous slice of the games with its own device pool, network instance, HIP stream and staging.
@@ -184,6 +214,11 @@ private:
         int g0 = 0, n = 0;
         Net* net = nullptr;            // the lane's network: its own (own_net) or the caller's (mz_worker_create_shared)
         std::unique_ptr<Net> own_net;
+        // match play: the lane holds BOTH sides' networks — own_net is side A's, net_b side B's — and `net` points at the one that searches this step.  Side B's
+        // runs on the lane's stream (the pool's and the device rules' kernels are ordered with the network's on it); the stream it was created with goes with the lane
+        std::unique_ptr<Net> net_b;
+        hipStream_t net_b_stream = nullptr;
+        int index = 0;
         Pool pool;
         std::unique_ptr<TreeReader> tree; // created with the lane's first read-out
         hipStream_t stream = nullptr;
@@ -235,6 +270,7 @@ private:
             if (ev_up) { (void)hipEventDestroy(ev_up); }
             if (up_stream) { (void)hipStreamDestroy(up_stream); }
             if (own_stream) { (void)hipStreamDestroy(own_stream); }
+            if (net_b_stream) { (void)hipStreamDestroy(net_b_stream); }
         }
     };
     Lane& laneOf(int g) { return *lanes_[std::min(g / plan_.lane_size, plan_.lanes - 1)]; }
@@ -381,7 +417,24 @@ private:
         long split_min_draws = 32768;   // mz_sim_split: AlphaZero rotation draws a move needs before its launch gets a third part (MZ_SIM_SPLIT_MIN_DRAWS: tests, 0 = always)
     };
     Plan plan_;
-    Plan resolvePlan(int lanes) const;
+    Plan resolvePlan(int lanes, const Net* asked = nullptr) const; // asked: the network whose kernels decide (nullptr: the first lane's)
+    // ---- match play (mz_worker_create_match) ----
+    bool match_ = false, match_done_ = false;
+    const float* match_wb_ = nullptr;  // side B's parameters while init runs
+    size_t match_cb_ = 0;
+    uint64_t match_t_ = 0;             // the step counter t: steps (one move of every game each) since `start`
+    mz_match_stats ms_{};
+    int matchRefusal() const;
+    int matchFixed(const char* what) const { setError("%s: the networks of a match are fixed when it is created (a new match is a new worker)", what); return MZ_ERR_STATE; }
+    const std::string& matchPrecision(int side) const
+    {
+        const std::string& p = side ? cfg_.mz_match_precision_b : cfg_.mz_match_precision_a;
+        return p.empty() ? cfg_.mz_nn_precision : p;
+    }
+    const std::string& matchName(int side) const { return side ? cfg_.mz_match_name_b : cfg_.mz_match_name_a; }
+    int matchBeginStep(Lane& L, uint64_t t);
+    void matchAfterMoves(Lane& L);
+    bool matchOver() const { return ms_.games_finished >= uint64_t(cfg_.mz_match_games); }
     int addLane(Net* shared, const float* weights, size_t count);
     int allocLane(int l, const mz_search_cfg& sc);
 };
@@ -396,6 +449,7 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     if (external_) { ext_ev_ = *ext; }
     if (device >= 0 && device < 64) { counted_device_ = device; g_workers_on_device[device].fetch_add(1); }
     if (external_) { int rx = extRefusal(); if (rx) { return rx; } }
+    if (match_) { int rm = matchRefusal(); if (rm) { return rm; } }
     if (cfg_.nn_type_name == "muzero" && desc.type == 0) { setError("nn_type_name=muzero but the network descriptor is alphazero"); return MZ_ERR_ARG; }
     if (gameFromName(cfg_.env_game.c_str()) == kHavannah && (cfg_.nn_type_name != "alphazero" || desc.type != 0)) { // ref havannah.cpp:233-236: getActionFeatures throws
         setError("env_game=havannah has no action features: a MuZero network cannot play it (nn_type_name=alphazero only, ref havannah.cpp:233-236)");
@@ -427,7 +481,19 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     held_.assign(G_, Held());
     noise_policy_.resize(GA); noise_logit_.resize(GA); noise_noise_.resize(GA);
     if ((rc = createActors())) { return rc; }
-    plan_ = resolvePlan(std::max(1, cfg_.mz_pipeline_lanes));
+    plan_ = resolvePlan(match_ ? 2 : std::max(1, cfg_.mz_pipeline_lanes));
+    if (match_) {
+        // one plan serves both lanes and every step: the two sides' networks (the first lane holds both) must ask for the same one
+        const Plan pb = resolvePlan(2, lanes_[0]->net_b.get());
+        if (pb.resident != plan_.resident || pb.sim_mz != plan_.sim_mz || pb.sim_kernel != plan_.sim_kernel || pb.sim_root_host != plan_.sim_root_host ||
+            pb.dev_gumbel != plan_.dev_gumbel || pb.feat_bits != plan_.feat_bits || pb.slab_slots != plan_.slab_slots || pb.rounds.size() != plan_.rounds.size() ||
+            pb.sim_mode.cluster != plan_.sim_mode.cluster || pb.sim_mode.rounds != plan_.sim_mode.rounds || pb.sim_mode.alt_base != plan_.sim_mode.alt_base) {
+            setError("mz_match_precision_a=%s / mz_match_precision_b=%s: the two sides of a match resolve to different execution plans (%s against %s); "
+                     "set mz_sim_kernel=false to play both in the lock-step mode", matchPrecision(0).c_str(), matchPrecision(1).c_str(),
+                     plan_.sim_kernel ? "a simulation kernel" : "lock-step", pb.sim_kernel ? "a simulation kernel" : "lock-step");
+            return MZ_ERR_ARG;
+        }
+    }
     while (int(lanes_.size()) < plan_.lanes) { if ((rc = addLane(shared, weights, count))) { return rc; } }
     mz_search_cfg sc{};
     sc.num_simulation = n_;
@@ -459,6 +525,14 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
         gum_.log2_m = std::log2(m);
     }
     rounds_ = plan_.rounds;
+    if (match_) { // the first G games are counted (mz_match_games >= G) and start at step 0: lane h's first player is side h
+        for (int g = 0; g < G_; ++g) {
+            games_[g].m_serial = g;
+            games_[g].m_t0 = 0;
+            games_[g].m_first_side = laneOf(g).index & 1;
+        }
+        ms_.games_started = uint64_t(G_);
+    }
     if (thinkB_ > 1) {
         if (!plan_.resident) { setError("actor_mcts_think_batch_size=%d: the batched think runs on the device rules, which this game or pool size does not have", thinkB_); return MZ_ERR_ARG; }
         Lane& L = *lanes_[0];
@@ -485,6 +559,70 @@ int Worker::extRefusal() const
     if (cfg_.actor_mcts_think_batch_size > 1) { setError("actor_mcts_think_batch_size=%d: the batched think does not run on an external evaluator", cfg_.actor_mcts_think_batch_size); return MZ_ERR_ARG; }
     if (cfg_.mz_nn_precision != "f32") { setError("mz_nn_precision=%s: with an external evaluator the precision is the caller's business (leave the key at f32)", cfg_.mz_nn_precision.c_str()); return MZ_ERR_ARG; }
     return MZ_OK;
+}
+
+// mz_worker_create_match: what the schedule of a match (two lanes, one move of every game per step, strict alternation) does not cover is refused by name
+// when the worker is created
+int Worker::matchRefusal() const
+{
+    const int G = cfg_.zero_num_parallel_games, N = cfg_.mz_match_games;
+    if (G < 2 || (G & 1)) { setError("zero_num_parallel_games=%d: a match plays two lanes of G / 2 games each (an even number, at least 2)", G); return MZ_ERR_ARG; }
+    if (N < G) { setError("mz_match_games=%d: a match counts at least as many games as it plays side by side (zero_num_parallel_games=%d)", N, G); return MZ_ERR_ARG; }
+    if (cfg_.env_game == "atari") { setError("env_game=atari: a match needs a game of two players"); return MZ_ERR_ARG; }
+    if (cfg_.mz_manual_step) { setError("mz_manual_step=true: a match plays on its own, step by step for both sides"); return MZ_ERR_ARG; }
+    if (cfg_.actor_mcts_think_batch_size > 1) { setError("actor_mcts_think_batch_size=%d: a match searches one simulation at a time (the batched think has one lane)", cfg_.actor_mcts_think_batch_size); return MZ_ERR_ARG; }
+    if (cfg_.zero_actor_intermediate_sequence_length > 0) {
+        setError("zero_actor_intermediate_sequence_length=%d: a match prints whole games, one line each", cfg_.zero_actor_intermediate_sequence_length);
+        return MZ_ERR_ARG;
+    }
+    for (int side = 0; side < 2; ++side) {
+        const std::string& p = matchPrecision(side);
+        if (p != "f32" && p != "bf16x3") { setError("mz_match_precision_%c '%s' unknown (f32 | bf16x3): a match runs each side at one of the two", side ? 'b' : 'a', p.c_str()); return MZ_ERR_ARG; }
+    }
+    if (!match_wb_) { setError("match: side B has no parameters"); return MZ_ERR_ARG; }
+    return MZ_OK;
+}
+
+// The schedule at a move boundary, before the step's first launch: in step t lane h is searched by side (h + t) mod 2, and every game of the lane must have
+// that side to move — a game that started at step t0 has had t - t0 steps (a move each), so its first player (Black) moves when t - t0 is even.
+int Worker::matchBeginStep(Lane& L, uint64_t t)
+{
+    const int side = static_cast<int>((uint64_t(L.index) + t) & 1);
+    L.net = side ? L.net_b.get() : L.own_net.get();
+    for (int g = L.g0; g < L.g0 + L.n; ++g) {
+        const Game& gm = games_[g];
+        const int expect = ((t - gm.m_t0) & 1) ? 2 : 1;
+        if (gm.env->turn() != expect) {
+            setError("match: game %d of lane %d has player %d to move at step %llu, %llu steps after its start: turn disagrees with the schedule's parity (player %d), "
+                     "so the lane's games no longer share their side to move", g, L.index, gm.env->turn(), (unsigned long long)t, (unsigned long long)(t - gm.m_t0), expect);
+            return MZ_ERR_STATE;
+        }
+    }
+    return MZ_OK;
+}
+
+// What the step's moves did, in slot order (the host section that made them may have run the RNG streams side by side): the tally of the counted games that
+// ended, and for every slot that freed up the game that starts in it at step t + 1 — the next serial number while fewer than mz_match_games have started,
+// else an uncounted filler; its first player is side (h + t + 1) mod 2, the side that searches the lane in that step.
+void Worker::matchAfterMoves(Lane& L)
+{
+    for (int g = L.g0; g < L.g0 + L.n; ++g) {
+        Game& gm = games_[g];
+        if (gm.m_serial >= 0 && gm.m_acted) { ++ms_.moves; }
+        if (gm.m_ended) {
+            if (gm.m_serial >= 0) {
+                const int first = gm.m_score > 0 ? 0 : (gm.m_score < 0 ? 2 : 1); // win / draw / loss of the first player (Black)
+                if (gm.m_first_side == 0) { ++ms_.a_first[first]; } else { ++ms_.a_second[2 - first]; }
+                ++ms_.games_finished;
+                if (gm.m_resigned) { ++ms_.resignations; }
+            }
+            gm.m_t0 = match_t_ + 1;
+            gm.m_first_side = static_cast<int>((uint64_t(L.index) + gm.m_t0) & 1);
+            if (ms_.games_started < uint64_t(cfg_.mz_match_games)) { gm.m_serial = static_cast<int>(ms_.games_started++); }
+            else { gm.m_serial = -1; ++ms_.filler_games; }
+        }
+        gm.m_acted = gm.m_ended = gm.m_resigned = false;
+    }
 }
 
 // the four numbers of the descriptor an external evaluator is created with, against the game's engine
@@ -516,7 +654,7 @@ int Worker::thinkRefusal() const
 
 // Every execution choice of the worker, from the configuration, the descriptor, the game, the first lane's network (which kernels its shape has), the pool's
 // size and whether the network is shared.  Pure — nothing is allocated — so the automatic lane count can resolve the plan for one lane and then for two.
-Worker::Plan Worker::resolvePlan(int lanes) const
+Worker::Plan Worker::resolvePlan(int lanes, const Net* asked) const
 {
     Plan p;
     const GameEnv& e = *games_[0].env;
@@ -527,8 +665,9 @@ Worker::Plan Worker::resolvePlan(int lanes) const
         p.resident = cfg_.mz_device_env && e.hasDeviceTwin() && G_ <= kRotPackGames;
         return p;
     }
-    const Net& net = *lanes_[0]->net;
+    const Net& net = asked ? *asked : *lanes_[0]->net;
     p.lanes = (G_ < 2 * lanes || shared_net_ || thinkB_ > 1) ? 1 : lanes; // a shared network has one stream: one lane; so has the batched think
+    if (match_) { p.lanes = 2; } // a match is two lanes of G / 2 games, down to one game each
     p.lane_size = (G_ + p.lanes - 1) / p.lanes;
     p.sim_mode.cluster = cfg_.mz_sim_cluster && p.lanes == 1; // two lanes = two concurrent cooperative launches: not with clusters that wait for each other
     // AlphaZero board games: every plane is 0 / 1, so leaves reach the network bit-packed whatever kernels serve its shape — the fused towers stage the bits
@@ -625,9 +764,19 @@ int Worker::addLane(Net* shared, const float* weights, size_t count)
         L->own_net = std::make_unique<Net>();
         L->net = L->own_net.get();
         int rc = L->net->init(device_, desc_, weights, count);
-        if (!rc) { rc = L->net->setPrecision(cfg_.mz_nn_precision == "bf16x3" ? 1 : 0); }
+        if (!rc) { rc = L->net->setPrecision((match_ ? matchPrecision(0) : cfg_.mz_nn_precision) == "bf16x3" ? 1 : 0); }
         if (rc) { return rc; }
+        if (match_) { // side B's network beside side A's, on the same stream
+            L->net_b = std::make_unique<Net>();
+            rc = L->net_b->init(device_, desc_, match_wb_, match_cb_);
+            if (!rc) { rc = L->net_b->setPrecision(matchPrecision(1) == "bf16x3" ? 1 : 0); }
+            if (rc) { return rc; }
+            MZ_HIP(hipStreamSynchronize(L->net_b->stream_));
+            if (L->net_b->own_stream_) { L->net_b_stream = L->net_b->stream_; L->net_b->own_stream_ = false; }
+            L->net_b->stream_ = L->net->stream_;
+        }
     }
+    L->index = static_cast<int>(lanes_.size());
     L->stream = L->net->stream_;
     lanes_.push_back(std::move(L));
     return MZ_OK;
@@ -706,7 +855,7 @@ void Worker::adaptRounds()
     }
     // (sim_pre_pair_kernel_mz: a partner workgroup stayed out — the GPU is shared.  Looked at whatever the second-leaf settings are: with mz_sim_round_alt=false every
     // small round goes to the pairs, and a shared GPU would pay the partner's bounded wait in every round of every move)
-    if (now[129] != 0) { for (auto& L : lanes_) { L->net->pairTrouble(); } }
+    if (now[129] != 0) { for (auto& L : lanes_) { L->net->pairTrouble(); if (L->net_b) { L->own_net->pairTrouble(); L->net_b->pairTrouble(); } } } // (a match: both sides' networks)
     if (!cfg_.mz_sim_round_alt || plan_.sim_mode.alt_base == 0) { return; }
     if (prestat_prev_.size() == 512) {
         const int cus = net0().cuCount();
@@ -1160,9 +1309,11 @@ void Worker::outputGame(Game& gm) // ref actor_group.cpp:24-50
     const bool is_terminal = (cfg_.zero_actor_intermediate_sequence_length == 0 || gm.env->isTerminal());
     std::ostringstream oss;
     std::string obs_raw;
-    oss << "SelfPlay " << (is_terminal ? "true" : "false") << " " << (range.second - range.first + 1) << " " << game_length << " "
+    ActionInfo tags = {{"DLEN", std::to_string(range.first) + "-" + std::to_string(range.second)}};
+    if (match_) { tags.push_back({"PB", matchName(gm.m_first_side)}); tags.push_back({"PW", matchName(1 - gm.m_first_side)}); } // who had which colour
+    oss << (match_ ? "Match " : "SelfPlay ") << (is_terminal ? "true" : "false") << " " << (range.second - range.first + 1) << " " << game_length << " "
         << gm.env->evalScore(!gm.env->isTerminal()) << " "
-        << record(gm, {{"DLEN", std::to_string(range.first) + "-" + std::to_string(range.second)}}, &obs_raw) << " "
+        << record(gm, tags, &obs_raw) << " "
         << "#";
     if (!is_terminal) {
         // (i < size: a resignation before the first move of an intermediate-sequence game has range 0-0 and an EMPTY history — the reference indexes it anyway)
@@ -1221,8 +1372,14 @@ void Worker::handleSearchDone(int g) // ref actor_group.cpp:116-134 + base_actor
         if (plan_.defer_info && !is_endgame && !intermediate) { (tl_sink_ ? tl_sink_->deferred : deferred_).push_back({g, mover, gm.action_info_history.size() - 1}); }
         else { gm.action_info_history.back() = actionInfo(g, mover); }
     }
+    if (match_) { // what matchAfterMoves tallies, taken before the slot's next game starts
+        gm.m_acted = acted;
+        gm.m_ended = is_endgame;
+        gm.m_resigned = is_endgame && resign;
+        if (is_endgame) { gm.m_score = gm.env->evalScore(!gm.env->isTerminal()); }
+    }
     if (is_endgame) {
-        outputGame(gm);
+        if (!match_ || gm.m_serial >= 0) { outputGame(gm); } // (a filler game of a match is never printed)
         resetGame(gm, rngOf(g));
     } else if (intermediate) {
         outputGame(gm);
@@ -1349,6 +1506,10 @@ int Worker::phase1(Lane& L, bool root_expansion, bool done, bool launch_select)
         trace_.add(3, t2 - te);
         // ---- the RNG-ordered section: actor index order within every RNG stream ----
         serialSection(L, want_noise, done, az);
+        if (match_ && done) { // the move boundary of a match: the tally, the games that start, and the side that searches the lane in the next step
+            matchAfterMoves(L);
+            if ((rc = matchBeginStep(L, match_t_ + 1))) { return rc; }
+        }
         const double ts = nowMs();
         trace_.add(4, ts - t2);
         if (want_noise) {
@@ -1371,6 +1532,7 @@ int Worker::phase1(Lane& L, bool root_expansion, bool done, bool launch_select)
         stats_.ms_move += t0 - t2;
         trace_.add(5, t0 - ts);
     } else {
+        if (match_) { int rcm = matchBeginStep(L, match_t_); if (rcm) { return rcm; } }
         for (int g = g0; g < g1; ++g) {
             if (az) { games_[g].rot = cfg_.actor_use_random_rotation_features ? rngOf(g).randInt() % 8 : 0; }
         }
@@ -1535,6 +1697,18 @@ int Worker::cycle()
     }
     root_host_pending_ = false;
     if (done && cfg_.mz_manual_step) { search_done_ = true; stop_now_ = true; pending_ = false; sims_done_ = 0; return MZ_OK; }
+    if (match_ && done) {
+        ++match_t_;
+        if (matchOver()) { // the N-th counted game has finished: what the boundary queued (search reset, roots, a selection) ends, and no further cycle runs
+            match_done_ = true; stop_now_ = true; pending_ = false; sims_done_ = 0;
+            for (auto& L : lanes_) {
+                MZ_HIP(hipStreamSynchronize(L->stream));
+                int rc = L->pool.checkError();
+                if (rc) { return rc; }
+            }
+            return MZ_OK;
+        }
+    }
     if (pending_) { sims_done_ = done ? 0 : sim_post_; }
     for (auto& L : lanes_) {
         int rc = phase2(*L);
@@ -1655,6 +1829,19 @@ int Worker::runCyclesSim(int n)
         }
         root_host_pending_ = false;
         if (done && cfg_.mz_manual_step) { search_done_ = true; pending_ = false; sims_done_ = 0; stats_.ms_total += nowMs() - t0; return i; }
+        if (match_ && done) {
+            ++match_t_;
+            if (matchOver()) { // the N-th counted game has finished: what the boundary queued (search reset, roots) ends, and no further cycle runs
+                match_done_ = true; pending_ = false; sims_done_ = 0;
+                for (auto& L : lanes_) {
+                    MZ_HIP(hipStreamSynchronize(L->stream));
+                    int rc = L->pool.checkError();
+                    if (rc) { return rc; }
+                }
+                stats_.ms_total += nowMs() - t0;
+                return i;
+            }
+        }
         if (pending_) { sims_done_ = done ? 0 : sim_post_; }
         int sim0 = sims_done_;
         bool root_on_device = false;
@@ -1909,7 +2096,7 @@ int Worker::thinkCycle()
 int Worker::runCycles(int n)
 {
     if (!ext_failed_.empty()) { setError("%s", ext_failed_.c_str()); return MZ_ERR_STATE; }
-    if (!running_ || search_done_) { return 0; }
+    if (!running_ || search_done_ || match_done_) { return 0; }
     if (think_) {
         for (int i = 0; i < n; ++i) {
             int rc = thinkCycle();
@@ -2182,6 +2369,7 @@ int Worker::peekRecord(int game, char* buf, int cap, const char* const* keys, co
     if (game < 0 || game >= G_) { setError("peek_record: game %d out of range", game); return MZ_ERR_ARG; }
     flushDeferred();
     ActionInfo extra;
+    if (match_) { extra.push_back({"PB", matchName(games_[game].m_first_side)}); extra.push_back({"PW", matchName(1 - games_[game].m_first_side)}); }
     for (int i = 0; i < ntags; ++i) { extra.push_back({keys[i], values[i]}); }
     const std::string s = record(games_[game], extra);
     const int len = static_cast<int>(s.size());
@@ -2288,6 +2476,7 @@ int Worker::nodeInfo(int g, int which, char* buf, int cap)
 int Worker::loadModel(const std::string& path, const mz_net_desc& file_desc, const float* weights, size_t count)
 {
     if (external_) { cfg_.nn_file_name = path; return MZ_OK; } // the weights are the caller's: the actor only follows the name (EV tag)
+    if (match_) { return matchFixed("load_model"); }
     MZ_HIP(hipSetDevice(device_));
     mz_net_desc a = file_desc, b = desc_;
     a.game_name[sizeof(a.game_name) - 1] = 0;
@@ -2319,6 +2508,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
     if (prefix == "start") { running_ = true; }
     else if (prefix == "stop") { running_ = false; }
     else if (prefix == "reset_actors") {
+        if (match_) { setError("reset_actors: the games of a match follow its schedule from step 0 (a new match is a new worker)"); return MZ_ERR_STATE; }
         for (auto& gm : games_) { resetGame(gm, main_rng_); } // handleCommand runs on the main thread (actor_group.cpp:200-219)
         sims_done_ = 0;
         pending_ = false;
@@ -2327,6 +2517,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
     } else if (prefix == "load_model") {
         if (line.find(' ') == std::string::npos) { setError("load_model needs a path"); return MZ_ERR_ARG; }
         const std::string path = line.substr(line.find(' ') + 1);
+        if (match_) { return matchFixed("load_model"); }
         if (shared_net_ || external_) { // the caller's Network::loadModel has (or will have) reloaded the weights; the actor only follows the name (EV tag)
             pending_weights_.clear();
             cfg_.nn_file_name = path;
@@ -2355,6 +2546,9 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         MZ_FIXED(nn_type_name) MZ_FIXED(env_board_size) MZ_FIXED(env_go_komi) MZ_FIXED(env_go_ko_rule) MZ_FIXED(env_game) MZ_FIXED(atari_init_q)
         MZ_FIXED(env_atari_name) MZ_FIXED(env_atari_episode_length) MZ_FIXED(mz_pipeline_lanes) MZ_FIXED(mz_rng_streams) MZ_FIXED(mz_cpu_base) MZ_FIXED(mz_signal_wait)
         MZ_FIXED(mz_sim_kernel) MZ_FIXED(mz_sim_cluster) MZ_FIXED(mz_sim_split) MZ_FIXED(mz_sim_rounds) MZ_FIXED(mz_sim_round_min) MZ_FIXED(mz_sim_round_alt) MZ_FIXED(mz_sim_round_batch) MZ_FIXED(mz_sim_rounds_board) MZ_FIXED(mz_sim_round_pairs) MZ_FIXED(mz_sim_round_leaves) MZ_FIXED(mz_manual_step) MZ_FIXED(mz_nn_precision) MZ_FIXED(mz_raw_observations) MZ_FIXED(mz_device_env) MZ_FIXED(mz_zero_copy)
+        // a match's length, names and arithmetic are part of its records and its tally from step 0 (every other worker never reads the five keys)
+        MZ_FIXED(mz_match_games) MZ_FIXED(mz_match_name_a) MZ_FIXED(mz_match_name_b) MZ_FIXED(mz_match_precision_a) MZ_FIXED(mz_match_precision_b)
+        if (match_) { MZ_FIXED(zero_actor_intermediate_sequence_length) }
         // the Atari-shaped environments keep a window of screens sized from these three at creation (ref atari.cpp:87); records of a larger window
         // would miss frames, so they are fixed where observations are kept (board games: free to change, like the reference)
         if (games_[0].env->hasObservations()) { MZ_FIXED(zero_actor_intermediate_sequence_length) MZ_FIXED(learner_n_step_return) MZ_FIXED(learner_muzero_unrolling_step) }
@@ -2418,6 +2612,18 @@ mz_worker* mz_worker_create_external(int device, const char* conf, const mz_net_
     std::unique_ptr<mz_worker> w(new mz_worker());
     if (w->w.init(device, conf, *desc, nullptr, 0, nullptr, ev) != MZ_OK) { return nullptr; }
     return w.release();
+}
+mz_worker* mz_worker_create_match(int device, const char* conf, const mz_net_desc* desc, const float* weights_a, size_t count_a, const float* weights_b, size_t count_b)
+{
+    if (!conf || !desc || !weights_a || !weights_b) { mz::setError("mz_worker_create_match: NULL argument"); return nullptr; }
+    std::unique_ptr<mz_worker> w(new mz_worker());
+    if (w->w.initMatch(device, conf, *desc, weights_a, count_a, weights_b, count_b) != MZ_OK) { return nullptr; }
+    return w.release();
+}
+int mz_worker_match_stats(mz_worker* w, mz_match_stats* out)
+{
+    if (!w || !out) { mz::setError("mz_worker_match_stats: NULL argument"); return MZ_ERR_ARG; }
+    return w->w.matchStats(out);
 }
 int mz_worker_evaluator_buffers(mz_worker* w, void** features, void** policy, void** logits, void** value)
 {
@@ -2584,7 +2790,7 @@ int mz_worker_get_stats(mz_worker* w, mz_worker_stats* out)
     if (!w || !out) { return MZ_ERR_ARG; }
     return w->w.getStats(out);
 }
-mz_net* mz_worker_net(mz_worker* w) { return w ? reinterpret_cast<mz_net*>(w->w.netOrNull()) : nullptr; } // NULL on an external evaluator
+mz_net* mz_worker_net(mz_worker* w) { return w ? reinterpret_cast<mz_net*>(w->w.netOrNull()) : nullptr; } // NULL on an external evaluator and on a match
 
 mz_env* mz_env_create(const char* conf)
 {

@@ -1,5 +1,6 @@
 """ctypes binding of include/mzgpu.h (the C-ABI drop-in boundary)."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -41,6 +42,13 @@ class WorkerStats(C.Structure):
 
 
 EVAL_FORWARD = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)
+
+
+class MatchStats(C.Structure):
+    """mz_match_stats (include/mzgpu.h)"""
+    _fields_ = [("games_started", C.c_uint64), ("games_finished", C.c_uint64), ("moves", C.c_uint64), ("filler_games", C.c_uint64),
+                ("a_first", C.c_uint64 * 3), ("a_second", C.c_uint64 * 3), ("resignations", C.c_uint64), ("steps", C.c_uint64),
+                ("done", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Evaluator(C.Structure):
@@ -193,6 +201,10 @@ def load():
             L.mz_worker_create_external.argtypes = [C.c_int, C.c_char_p, C.POINTER(NetDesc), C.POINTER(Evaluator)]
             L.mz_worker_evaluator_buffers.argtypes = [vp] + [C.POINTER(vp)] * 4
             L.mz_worker_evaluator_lane_policy.argtypes = [vp, fp, C.c_int]
+        if hasattr(L, "mz_worker_create_match"):  # (MZ_LIBMZGPU may name a build from before match play)
+            L.mz_worker_create_match.restype = vp
+            L.mz_worker_create_match.argtypes = [C.c_int, C.c_char_p, C.POINTER(NetDesc), fp, C.c_size_t, fp, C.c_size_t]
+            L.mz_worker_match_stats.argtypes = [vp, C.POINTER(MatchStats)]
         L.mz_godev_playout.argtypes = [C.c_int, C.c_int, C.c_float, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
         L.mz_envdev_playout.argtypes = [C.c_int, C.c_char_p, C.c_int, C.c_float, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
         L.mz_envdev_playout_conf.argtypes = [C.c_int, C.c_char_p, ip, C.c_int, C.c_int, ip, C.POINTER(C.c_uint32), u8p, ip, fp, ip]
@@ -591,6 +603,68 @@ class Worker:
 
     def net(self):
         return Net(self.desc, None, handle=self.L.mz_worker_net(self.h))
+
+
+class MatchWorker(Worker):
+    """Two weight blobs of one descriptor against each other (mz_worker_create_match): side A = weights_a, side B = weights_b.  The
+    configuration carries mz_match_games (and the names / precisions of the sides); everything else is a Worker — with two differences for code that is
+    handed a MatchWorker as a Worker: stats() is the MATCH's tally (mz_match_stats), the counters every worker has are worker_stats(); and net() raises,
+    because a match gives out no network handle (mz_worker_net is NULL: its networks are fixed and take turns)."""
+
+    def __init__(self, conf, desc, weights_a, weights_b, device=0):
+        self.L = load()
+        self.shared = None
+        if not hasattr(self.L, "mz_worker_create_match"):
+            raise MzError("this libmzgpu build has no mz_worker_create_match")
+        wa, wb = np.ascontiguousarray(weights_a, np.float32), np.ascontiguousarray(weights_b, np.float32)
+        self.h = self.L.mz_worker_create_match(device, conf.encode(), C.byref(desc), _f(wa), wa.size, _f(wb), wb.size)
+        if not self.h:
+            raise MzError("mz_worker_create_match failed: " + _err(self.L))
+        self.desc = desc
+
+    def net(self):
+        raise MzError("MatchWorker: the networks of a match are fixed and take turns; there is no handle to one (mz_worker_net is NULL)")
+
+    def worker_stats(self):
+        """the counters every worker has (mz_worker_get_stats)"""
+        return Worker.stats(self)
+
+    def stats(self):
+        """mz_match_stats as a dictionary; a_first / a_second are side A's [wins, draws, losses] as first and as second player"""
+        s = MatchStats()
+        _check(self.L, self.L.mz_worker_match_stats(self.h, C.byref(s)))
+        out = {k: getattr(s, k) for k, _ in MatchStats._fields_ if k != "reserved"}
+        out["a_first"], out["a_second"], out["done"] = list(s.a_first), list(s.a_second), bool(s.done)
+        return out
+
+    def play(self):
+        """runs the match to its end, a move of every game per call -> (stats, the `Match` lines in the order the games finished)"""
+        self.command("start")
+        lines, k = [], self.cycles_per_move()
+        while not self.stats()["done"]:
+            self.run_cycles(k)
+            lines += self.pop_lines(wait=False)
+        return self.stats(), lines + self.pop_lines()
+
+
+def match_elo(stats):
+    """The rating difference A - B a match's tally stands for.  With w, d, l side A's wins, draws and losses over n games, the score is s = (w + d/2) / n and
+    elo = 400 log10(s / (1 - s)); the standard error of s comes from the trinomial variance, var = (w (1 - s)^2 + d (1/2 - s)^2 + l s^2) / n per game, and
+    goes through the slope of the logistic curve: se_elo = 400 / (ln 10 s (1 - s)) sqrt(var / n).  s = 0 or 1 gives -inf / +inf with an infinite error; no
+    games give nan.  Returns the figures for all games and separately for the games A started ("first") and the games B started ("second")."""
+    def one(w, d, l):
+        n = w + d + l
+        if n == 0:
+            return dict(games=0, score=math.nan, elo=math.nan, se=math.nan)
+        s = (w + 0.5 * d) / n
+        if s <= 0.0 or s >= 1.0:
+            return dict(games=n, score=s, elo=math.inf if s >= 1.0 else -math.inf, se=math.inf)
+        var = (w * (1.0 - s) ** 2 + d * (0.5 - s) ** 2 + l * s ** 2) / n
+        return dict(games=n, score=s, elo=400.0 * math.log10(s / (1.0 - s)), se=400.0 / (math.log(10.0) * s * (1.0 - s)) * math.sqrt(var / n))
+    f, s = list(stats["a_first"]), list(stats["a_second"])
+    out = one(*[a + b for a, b in zip(f, s)])
+    out["first"], out["second"] = one(*f), one(*s)
+    return out
 
 
 def _device_ptr(a, what):
