@@ -46,6 +46,7 @@ inline std::string mzgpuConfValue(const std::string& conf, const std::string& ke
 }
 
 // the merged configuration the worker is created with
+// (the worker's own keys — mz_manual_step, mz_nn_precision, mz_think_reuse_tree, ... — have no reference variable: they travel in mzgpuConfigurationString())
 inline std::string mzgpuCollectConfiguration()
 {
     if (!mzgpuConfigurationString().empty()) { return mzgpuConfigurationString(); }

@@ -325,6 +325,18 @@ int mz_worker_get_stats(mz_worker* w, mz_worker_stats* out);
    queries, expand + backup per query (ref actor/zero_actor.cpp:129-157).  Counters since the worker was created, summed over its games: steps, walks
    (selections) and queries (walks whose leaf carried no virtual loss: the leaves evaluated).  All three stay 0 with B = 1. */
 int mz_worker_think_stats(mz_worker* w, uint64_t* steps, uint64_t* walks, uint64_t* queries);
+
+/* Tree reuse of the batched think (mz_think_reuse_tree=true, default false; fixed at creation).  With the key on, mz_worker_act(game, action,
+ * player) re-roots the game's tree: if the root has a child with that action and the child is expanded, the child becomes the root (action -1, the player of
+ * the move) with everything below it, bit for bit; otherwise, and on mz_worker_reset_game, reset_actors, mz_worker_set_weights / load_model,
+ * mz_worker_env_set_turn and mz_worker_env_reset_seed, the tree is cleared as mz_worker_reset_search always did.  One act is one ply: a searched move followed
+ * by the opponent's move keeps the grandchild.  The next search goes on from the kept root: it is complete at n + 1 root visits as ever, so a root kept with
+ * c visits costs n + 1 - c simulations.  mz_worker_tree / tree_string / node_info(.., 0) show the kept tree from the return of act on.  The reference clears the tree at
+ * every move, so records made with the key on are not the reference's.  Refused by name (MZ_ERR_ARG, the text names the key): without mz_manual_step=true,
+ * with a batch size below 2 (and so wherever the batched think is refused), with actor_use_dirichlet_noise=true or actor_use_gumbel_noise=true, on an
+ * external-evaluator worker and on a match worker.
+ * The counters: moves handed to the re-root, those that kept a subtree, and the sum of the kept roots' visits (simulations the next searches did not run). */
+int mz_worker_think_reuse_stats(mz_worker* w, uint64_t* reroots, uint64_t* kept, uint64_t* kept_visits);
 /* the worker's network (lane 0's); NULL on an external evaluator and on a match (whose networks are fixed and take turns: there is no handle to reload) */
 mz_net* mz_worker_net(mz_worker* w);
 

@@ -95,6 +95,10 @@ struct WorkerConfig {
     int mz_match_games = 0;
     std::string mz_match_name_a = "A", mz_match_name_b = "B";
     std::string mz_match_precision_a, mz_match_precision_b;
+    // not a reference key: the batched think (mz_manual_step=true, actor_mcts_think_batch_size >= 2) keeps the subtree of the move played through
+    // mz_worker_act as the tree of the next search, which then runs n + 1 - (visits kept) simulations.  The reference clears the tree
+    // (zero_actor.cpp:29-34), so the records are not the reference's: opt-in, refused by name wherever the batched think does not run
+    bool mz_think_reuse_tree = false;
     int mz_zero_copy = 3; // bit 0: kernels read their inputs from pinned host memory; bit 1: kernels write their outputs there
 
     // returns false (and sets the library error string) on an unknown key or an unparsable value,

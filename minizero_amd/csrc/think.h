@@ -6,6 +6,9 @@
 //   (Net::forwardAZ over games * B samples)
 //   think_cand_kernel            one wave per (game, walk): azCandBody for the queries
 //   think_expand_backup_kernel   one wave per game: expandBackupBody per query in batch order, the virtual loss of the query's path removed after each
+//   think_reroot_kernel          (mz_think_reuse_tree) one wave per game after a move: the subtree of the move played is compacted to the front of the
+//                                game's node range and becomes the tree of the next search (the kept nodes' position slots move down with them); any
+//                                other game is left alone or cleared
 // The node records keep their layout: the virtual loss is an array of its own beside them, allocated here.
 #pragma once
 #include "go_dev.h"
@@ -39,12 +42,19 @@ struct ThinkView {
 class ThinkDevice {
 public:
     virtual ~ThinkDevice() = default;
-    virtual int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg) = 0;
+    // reuse: mz_think_reuse_tree — the scratch of the re-root (one int per node, a worklist of n + 2 entries per game) is allocated only then
+    virtual int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg, bool reuse) = 0;
     virtual int clearAsync() = 0;                             // a new search: no virtual loss anywhere
     virtual uint8_t* hostRot() = 0;                           // [games][B], uploaded by stepAsync
     // one step of every game: select, leaves, forward, candidates, expand + backup, then the status words on their way to hostStatus()
     virtual int stepAsync(Pool& pool, const GoDevView& gv, Net& net) = 0;
     virtual const int* hostStatus() const = 0;                // valid after the stream has been waited for
+    // the re-root: hostReroot() is [games][2] = (action, player) per game — action -2 leaves the game alone (reroot() puts that back everywhere), -1 clears
+    // its tree, an action id keeps the subtree of the root's child with it, if that child is expanded, and clears otherwise.  reroot() runs the kernel on
+    // the stream and waits; hostRerootStatus() is then [games][2] = (count of the kept root, 0 = cleared; nodes of the game)
+    virtual int* hostReroot() = 0;
+    virtual int reroot(Pool& pool, const GoDevView& gv) = 0;
+    virtual const int* hostRerootStatus() const = 0;
 };
 ThinkDevice* createThinkDevice() __attribute__((weak));
 

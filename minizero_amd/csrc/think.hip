@@ -87,15 +87,24 @@ __global__ __launch_bounds__(64) void think_expand_backup_kernel(PoolView pv, Th
     }
 }
 
+__global__ __launch_bounds__(64) void think_reroot_kernel(PoolView pv, GoDevView gv, float* __restrict__ vl, const int* __restrict__ args, int* newidx, int* work, int work_cap,
+                                                          int* __restrict__ status, int* __restrict__ err)
+{
+    thinkRerootBody(pv, gv, vl, args, newidx, work, work_cap, status, blockIdx.x, threadIdx.x, err);
+}
+
 } // namespace
 
 class ThinkDeviceImpl final : public ThinkDevice {
 public:
-    int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg) override;
+    int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg, bool reuse) override;
     int clearAsync() override;
     uint8_t* hostRot() override { return h_rot_.p; }
     int stepAsync(Pool& pool, const GoDevView& gv, Net& net) override;
     const int* hostStatus() const override { return h_status_.p; }
+    int* hostReroot() override { return h_reroot_.p; }
+    int reroot(Pool& pool, const GoDevView& gv) override;
+    const int* hostRerootStatus() const override { return h_reroot_.p + size_t(games_) * 2; }
 
 private:
     ThinkView v_{};
@@ -109,6 +118,10 @@ private:
     PinBuf<int> h_status_;
     DevBuf<uint32_t> feat_;
     DevBuf<uint64_t> legal_;
+    // mz_think_reuse_tree only: the new index per node, the worklist of expanded kept nodes, (action, player) + status per game
+    DevBuf<int> newidx_, work_, d_reroot_;
+    PinBuf<int> h_reroot_;
+    int work_cap_ = 0;
 };
 
 ThinkDevice* createThinkDevice() { return new ThinkDeviceImpl(); }
@@ -116,7 +129,7 @@ ThinkDevice* createThinkDevice() { return new ThinkDeviceImpl(); }
 #define TALLOC(buf, k) \
     if (!(buf).alloc(k)) { setError("think: allocation of %zu elements failed (%s)", size_t(k), #buf); return MZ_ERR_DEVICE; }
 
-int ThinkDeviceImpl::init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg)
+int ThinkDeviceImpl::init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg, bool reuse)
 {
     if (B < 2 || B > kThinkMaxBatch) { setError("think: batch size %d out of range", B); return MZ_ERR_ARG; }
     device_ = device;
@@ -156,7 +169,28 @@ int ThinkDeviceImpl::init(int device, hipStream_t stream, const Pool& pool, cons
     MZ_HIP(hipMemset(feat_.p, 0, feat_.n * sizeof(uint32_t))); // the forward runs over every (game, walk) entry: the ones no query ever wrote hold empty planes
     memset(h_rot_.p, 0, Q);
     memset(h_status_.p, 0, 4 * G * sizeof(int));
+    if (reuse) {
+        work_cap_ = cfg.num_simulation + 2; // a search expands at most n + 1 nodes
+        TALLOC(newidx_, G * pv.cap); TALLOC(work_, G * work_cap_); TALLOC(d_reroot_, 4 * G); TALLOC(h_reroot_, 4 * G);
+        MZ_HIP(hipMemset(d_reroot_.p, 0, d_reroot_.n * sizeof(int)));
+        for (size_t g = 0; g < G; ++g) { h_reroot_.p[g * 2] = -2; h_reroot_.p[g * 2 + 1] = 0; h_reroot_.p[(G + g) * 2] = 0; h_reroot_.p[(G + g) * 2 + 1] = 1; }
+    }
     return clearAsync();
+}
+
+int ThinkDeviceImpl::reroot(Pool& pool, const GoDevView& gv)
+{
+    if (!h_reroot_.p) { setError("think: the re-root was not set up (mz_think_reuse_tree=false)"); return MZ_ERR_STATE; }
+    MZ_HIP(hipSetDevice(device_));
+    const size_t G = games_;
+    MZ_HIP(hipMemcpyAsync(d_reroot_.p, h_reroot_.p, G * 2 * sizeof(int), hipMemcpyHostToDevice, stream_));
+    hipLaunchKernelGGL(think_reroot_kernel, dim3(games_), dim3(64), 0, stream_, pool.v_, gv, vl_.p, d_reroot_.p, newidx_.p, work_.p, work_cap_, d_reroot_.p + G * 2,
+                       pool.errFlag());
+    MZ_HIP(hipGetLastError());
+    MZ_HIP(hipMemcpyAsync(h_reroot_.p + G * 2, d_reroot_.p + G * 2, G * 2 * sizeof(int), hipMemcpyDeviceToHost, stream_));
+    MZ_HIP(hipStreamSynchronize(stream_));
+    for (size_t g = 0; g < G; ++g) { h_reroot_.p[g * 2] = -2; }
+    return pool.checkError();
 }
 
 int ThinkDeviceImpl::clearAsync()

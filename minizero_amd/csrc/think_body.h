@@ -6,6 +6,7 @@
 #pragma once
 #include "pool_body.h"
 #include "think.h"
+#include "go_dev.h"
 
 namespace mz {
 
@@ -117,6 +118,180 @@ __device__ __forceinline__ void thinkSelectBody(const PoolView& v, const ThinkVi
     if (lane == 0) {
         t.status[g * 4 + 1] = bs;
         t.status[g * 4 + 2] = nq;
+    }
+}
+
+// Re-root of game `g` after a move (mz_think_reuse_tree; think.h): ONE wave64.  args[g] = (action, player): action < -1 leaves the game alone, -1 clears
+// its tree, any other keeps the subtree of the root's child with that action if that child is expanded, and clears otherwise.  The pool allocates by bump, so
+// a parent precedes its block of children and the kept nodes, moved to the front of the game's range in ascending old index, keep their blocks contiguous and
+// their child order: a node's new index is <= its old one, and the move needs no second copy of the pool.  Nothing is computed: every value is copied.
+//   work    [work_cap] the expanded kept nodes whose blocks are still to be marked (a kept tree of c visits has at most c of them)
+//   newidx  [cap] 1 = kept while marking, then the node's new index (-1: dropped)
+//   status  [2] the kept root's count (0: cleared), the game's number of nodes
+// A visited node also owns a position slot of the device rules (go_dev.h: `hslot`, the slot a leaf's position is built from its parent's; a search hands out
+// slots 0 .. n in query order).  The next search hands out slots c .. n for a root kept with c visits, so the kept nodes' slots — at most c: a visit of the
+// subtree's root makes at most one node visited — are renumbered 0 .. in ascending old order and their positions moved down the same way (new <= old again;
+// the kept root was queried before anything below it, so it gets slot 0, where reset_search's root upload puts the same position).
+// Every index read from a record is checked against the game's node count before it is used; a tree that fails a check is cleared and the pool's error flag set.
+__device__ __forceinline__ void thinkCopySlot(const GoDevView& gv, size_t src, size_t dst, int lane)
+{
+    for (int w = lane; w < 2 * gv.W; w += 64) { gv.stones[dst * 2 * gv.W + w] = gv.stones[src * 2 * gv.W + w]; }
+    for (int p = lane; p < gv.Ppad; p += 64) { gv.lab[dst * gv.Ppad + p] = gv.lab[src * gv.Ppad + p]; }
+    if (lane == 0) {
+        gv.hash[dst] = gv.hash[src];
+        gv.meta[dst * 2] = gv.meta[src * 2];
+        gv.meta[dst * 2 + 1] = gv.meta[src * 2 + 1];
+    }
+}
+
+__device__ __forceinline__ void thinkRerootBody(const PoolView& v, const GoDevView& gv, float* __restrict__ vl, const int* __restrict__ args, int* newidx_all,
+                                                int* work_all, int work_cap, int* __restrict__ status, int g, int lane, int* err)
+{
+    const int action = __builtin_amdgcn_readfirstlane(args[g * 2]), player = __builtin_amdgcn_readfirstlane(args[g * 2 + 1]);
+    if (action < -1) { return; }
+    const size_t base = size_t(g) * v.cap;
+    NodeRec* recs = v.rec + base;
+    float* vls = vl + base;
+    int* newidx = newidx_all + base;
+    int* work = work_all + size_t(g) * work_cap;
+    int N = __builtin_amdgcn_readfirstlane(v.num_nodes[g]);
+    N = N < 1 ? 1 : (N > v.cap ? v.cap : N);
+    const NodeRec root = loadRec(recs);
+    bool bad = false;
+    const int S = gv.slots;
+    if (S < 1 || S > v.cap) { bad = true; } // (the slot map below lives in newidx)
+    // ---- 1. the child with the action: keep or clear ----
+    int child = -1;
+    NodeRec cr{};
+    if (action >= 0 && root.num_children > 0) {
+        const int nc = root.num_children, fc = root.first_child;
+        if (fc < 1 || fc > N - nc) { bad = true; }
+        for (int cb = 0; cb < nc && !bad && child < 0; cb += 64) {
+            const int i = cb + lane;
+            const unsigned long long m = __ballot(i < nc && recs[fc + (i < nc ? i : 0)].action == action);
+            if (m) { child = fc + cb + __builtin_ctzll(m); }
+        }
+        if (child >= 0) {
+            cr = loadRec(recs + child);
+            if (cr.num_children > 0 && (cr.first_child <= child || cr.first_child > N - cr.num_children)) { bad = true; }
+        }
+    }
+    bool keep = !bad && child >= 0 && cr.num_children > 0;
+    int M = 1;
+    if (keep) {
+        // ---- 2. mark the subtree: the whole block of every expanded kept node ----
+        for (int i = lane; i < N; i += 64) { newidx[i] = 0; }
+        thinkWaveSync();
+        if (lane == 0) { newidx[child] = 1; work[0] = child; }
+        int head = 0, tail = 1;
+        while (head < tail && !bad) { // head grows by one per turn, tail <= work_cap
+            thinkWaveSync();
+            const int e = __builtin_amdgcn_readfirstlane(work[head]);
+            ++head;
+            const NodeRec er = loadRec(recs + e);
+            const int nc = er.num_children, fc = er.first_child;
+            if (nc <= 0 || fc <= e || fc > N - nc) { bad = true; break; }
+            for (int cb = 0; cb < nc; cb += 64) {
+                const int i = cb + lane;
+                bool exp = false;
+                if (i < nc) {
+                    newidx[fc + i] = 1;
+                    exp = recs[fc + i].num_children > 0;
+                }
+                const unsigned long long m = __ballot(exp);
+                const int cnt = __popcll(m);
+                if (cnt > work_cap - tail) { bad = true; break; }
+                const int rank = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0u));
+                if (exp) { work[tail + rank] = fc + i; }
+                tail += cnt;
+            }
+        }
+        keep = !bad;
+    }
+    if (keep) {
+        // ---- 3. pass one: the new index of every kept node, ascending ----
+        thinkWaveSync();
+        int run = 0;
+        for (int cb = 0; cb < N; cb += 64) {
+            const int i = cb + lane;
+            const bool k = i < N && newidx[i] != 0;
+            const unsigned long long m = __ballot(k);
+            const int rank = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0u));
+            if (i < N) { newidx[i] = k ? run + rank : -1; }
+            run += __popcll(m);
+        }
+        M = run;
+        thinkWaveSync();
+        // ---- 4. pass two: move the records and the cold arrays, first_child remapped.  A chunk's stores land at or below its own indices, never in a later
+        // chunk's; inside the chunk every lane has its values in registers before any lane stores ----
+        for (int cb = 0; cb < N; cb += 64) {
+            const int i = cb + lane;
+            const int j = i < N ? newidx[i] : -1;
+            NodeRec r{};
+            float lg = 0.0f, ns = 0.0f, va = 0.0f;
+            int hs = -1;
+            if (j >= 0) {
+                r = loadRec(recs + i);
+                lg = v.logit[base + i]; ns = v.noise[base + i]; va = v.value[base + i]; hs = v.hslot[base + i];
+                if (r.num_children > 0 && r.first_child > i && r.first_child < N) { r.first_child = newidx[r.first_child]; } // (its block is kept and lies ahead of it: checked while marking)
+            }
+            thinkWaveSync();
+            if (j >= 0) {
+                if (j == 0) { r.action = -1; r.players = (r.players & ~0xFF) | (player & 0xFF); } // what ZeroActor::resetSearch writes (ref zero_actor.cpp:33)
+                reinterpret_cast<float4*>(recs + j)[0] = make_float4(r.count, r.mean, r.policy, r.reward);
+                reinterpret_cast<int4*>(recs + j)[1] = make_int4(r.first_child, r.num_children, r.action, r.players);
+                v.logit[base + j] = lg; v.noise[base + j] = ns; v.value[base + j] = va; v.hslot[base + j] = hs;
+            }
+            thinkWaveSync();
+        }
+        // ---- 5. the position slots of the kept nodes: renumbered in ascending old order, the positions moved down (newidx is free again: the slot map) ----
+        int* smap = newidx;
+        for (int i = lane; i < S; i += 64) { smap[i] = 0; }
+        thinkWaveSync();
+        for (int i = lane; i < M; i += 64) {
+            const int hs = v.hslot[base + i];
+            if (hs >= 0 && hs < S) { smap[hs] = 1; }
+        }
+        thinkWaveSync();
+        const size_t sb = size_t(g) * S;
+        int used = 0;
+        for (int cb = 0; cb < S; cb += 64) {
+            const int sl = cb + lane;
+            const bool k = sl < S && smap[sl] != 0;
+            unsigned long long m = __ballot(k);
+            const int rank = __builtin_amdgcn_mbcnt_hi(static_cast<unsigned>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<unsigned>(m), 0u));
+            if (sl < S) { smap[sl] = k ? used + rank : -1; }
+            while (m) { // a copy reads a slot above every slot written so far or the one the copy before it read: program order per lane is enough
+                const int src = cb + __builtin_ctzll(m);
+                m &= m - 1;
+                if (used != src) { thinkCopySlot(gv, sb + src, sb + used, lane); }
+                ++used;
+            }
+        }
+        thinkWaveSync();
+        for (int i = lane; i < M; i += 64) {
+            const int hs = v.hslot[base + i];
+            if (hs >= 0 && hs < S) { v.hslot[base + i] = smap[hs]; }
+        }
+        thinkWaveSync();
+        if (v.hslot[base] != 0) { bad = true; } // the kept root's position is the root upload's
+    } else if (lane == 0) { // reset_kernel's root (pool.hip)
+        NodeRec n;
+        n.count = 0; n.mean = 0; n.policy = 0; n.reward = 0;
+        n.first_child = -1; n.num_children = 0; n.action = -1;
+        n.players = player;
+        recs[0] = n;
+        v.logit[base] = 0; v.noise[base] = 0; v.value[base] = 0; v.hslot[base] = -1;
+        v.bound_size[g] = 0;
+        v.bound_lo[g] = 0; v.bound_hi[g] = 0;
+    }
+    for (int i = lane; i < N; i += 64) { vls[i] = 0.0f; } // between two searches no virtual loss is outstanding: cleared, not moved
+    if (lane == 0) {
+        v.num_nodes[g] = M;
+        v.path_len[g] = 0;
+        status[g * 2 + 0] = keep ? static_cast<int>(cr.count) : 0;
+        status[g * 2 + 1] = M;
+        if (bad) { atomicExch(err, MZ_ERR_CAPACITY); }
     }
 }
 

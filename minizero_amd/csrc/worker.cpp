@@ -146,7 +146,7 @@ public:
     {
         if (match_) { return matchFixed("set_weights"); }
         pending_weights_.assign(w, w + n);
-        return MZ_OK;
+        return thinkReroot(-1, -1); // (mz_think_reuse_tree) a kept tree holds the old network's outputs
     }
     int runCycles(int n);
     int cyclesPerMove() const { return n_ + 1; }
@@ -180,6 +180,13 @@ public:
         if (steps) { *steps = think_steps_; }
         if (walks) { *walks = think_walks_; }
         if (queries) { *queries = think_queries_; }
+        return MZ_OK;
+    }
+    int thinkReuseStats(uint64_t* reroots, uint64_t* kept, uint64_t* kept_visits) const
+    {
+        if (reroots) { *reroots = reuse_reroots_; }
+        if (kept) { *kept = reuse_kept_; }
+        if (kept_visits) { *kept_visits = reuse_kept_visits_; }
         return MZ_OK;
     }
     int getStats(mz_worker_stats* out)
@@ -293,6 +300,13 @@ private:
     std::vector<uint8_t> think_done_;
     std::vector<int> think_vl_child_;      // >= -1: the decision of game g sees one virtual loss on the root and on this root child (-1: on the root alone); -2: none
     uint64_t think_steps_ = 0, think_walks_ = 0, think_queries_ = 0;
+    // mz_think_reuse_tree: mz_worker_act re-roots the game's tree at the move played (think_reroot_kernel) and the next search goes on from it
+    bool think_reuse_ = false;
+    std::vector<int> think_kept_;          // root visits of the tree game g keeps for its next search (0: none, reset_search clears as ever)
+    std::vector<uint8_t> think_moved_;     // the tree of game g was re-rooted or cleared since its last decision: the chosen child is no longer a root child
+    uint64_t reuse_reroots_ = 0, reuse_kept_ = 0, reuse_kept_visits_ = 0; // moves given to the re-root, those that kept a subtree, the visits of the kept roots
+    int thinkReroot(int g, int action); // g < 0: every game; action -1 clears
+    int reuseRefusal(const char* where) const;
     int thinkRefusal() const;
     int thinkCycle();
     int thinkReadRoots(Lane& L);
@@ -303,7 +317,7 @@ private:
     int uploadRoots(Lane& L);
     int cycle();
     int createActors();
-    int resetAllSearches();
+    int resetAllSearches(const uint8_t* mask = nullptr);
     void resetGame(Game& g, Rng& rng);          // ZeroActor::reset (ref zero_actor.cpp:23-27)
     int rootPlayerFor(const Game& g) const { return g.env->numPlayers() == 2 ? 3 - g.env->turn() : g.env->turn(); }
     void buildCandidates(int g);
@@ -448,6 +462,7 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     external_ = ext != nullptr;
     if (external_) { ext_ev_ = *ext; }
     if (device >= 0 && device < 64) { counted_device_ = device; g_workers_on_device[device].fetch_add(1); }
+    if (cfg_.mz_think_reuse_tree && (external_ || match_)) { return reuseRefusal(external_ ? "external" : "match"); }
     if (external_) { int rx = extRefusal(); if (rx) { return rx; } }
     if (match_) { int rm = matchRefusal(); if (rm) { return rm; } }
     if (cfg_.nn_type_name == "muzero" && desc.type == 0) { setError("nn_type_name=muzero but the network descriptor is alphazero"); return MZ_ERR_ARG; }
@@ -461,6 +476,8 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     if (shared && shared->device_ != device) { setError("worker: the shared network lives on device %d, the worker on %d", shared->device_, device); return MZ_ERR_ARG; }
     thinkB_ = cfg_.mz_manual_step ? std::max(1, cfg_.actor_mcts_think_batch_size) : 1; // without mz_manual_step the key stays ignored, as ActorGroup never uses it
     if (thinkB_ > 1) { int rt = thinkRefusal(); if (rt) { return rt; } }
+    if (cfg_.mz_think_reuse_tree) { int rt = reuseRefusal(nullptr); if (rt) { return rt; } }
+    think_reuse_ = cfg_.mz_think_reuse_tree;
     G_ = cfg_.zero_num_parallel_games;
     A_ = desc.action_size;
     n_ = cfg_.actor_num_simulation;
@@ -538,7 +555,9 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
         Lane& L = *lanes_[0];
         if (!createThinkDevice) { setError("actor_mcts_think_batch_size=%d: this build has no device code for the batched think", thinkB_); return MZ_ERR_DEVICE; }
         think_.reset(createThinkDevice());
-        if ((rc = think_->init(device_, L.stream, L.pool, L.godev.v_, thinkB_, sc))) { return rc; }
+        if ((rc = think_->init(device_, L.stream, L.pool, L.godev.v_, thinkB_, sc, think_reuse_))) { return rc; }
+        think_kept_.assign(G_, 0);
+        think_moved_.assign(G_, 0);
         think_count_.assign(G_, 0);
         think_done_.assign(G_, 0);
         think_vl_child_.assign(G_, -2);
@@ -637,6 +656,19 @@ int Worker::extCheckDesc(const GameEnv& e) const
         return MZ_ERR_ARG;
     }
     if (desc_.action_size != e.policySize()) { setError("external evaluator: desc.action_size=%d, but the policy of %s has %d actions", desc_.action_size, e.name().c_str(), e.policySize()); return MZ_ERR_ARG; }
+    return MZ_OK;
+}
+
+// mz_think_reuse_tree=true: the option belongs to the batched think; where that does not run, or where a root that is already expanded would need a rule
+// of its own, it is refused by name when the worker is created
+int Worker::reuseRefusal(const char* where) const
+{
+    if (where && where[0] == 'e') { setError("mz_think_reuse_tree=true: an external evaluator does not run the batched think, whose trees the option keeps"); return MZ_ERR_ARG; }
+    if (where) { setError("mz_think_reuse_tree=true: a match plays on its own, one simulation at a time (the option keeps the trees of the batched think)"); return MZ_ERR_ARG; }
+    if (!cfg_.mz_manual_step) { setError("mz_think_reuse_tree=true without mz_manual_step=true: the tree is kept across mz_worker_act, which only a manually stepped worker takes"); return MZ_ERR_ARG; }
+    if (thinkB_ < 2) { setError("mz_think_reuse_tree=true with actor_mcts_think_batch_size=%d: the option keeps the trees of the batched think (a batch size of 2 to %d)", cfg_.actor_mcts_think_batch_size, kThinkMaxBatch); return MZ_ERR_ARG; }
+    if (cfg_.actor_use_dirichlet_noise) { setError("mz_think_reuse_tree=true with actor_use_dirichlet_noise=true: noise on a root that is already expanded needs a rule of its own"); return MZ_ERR_ARG; }
+    if (cfg_.actor_use_gumbel_noise) { setError("mz_think_reuse_tree=true with actor_use_gumbel_noise=true: noise on a root that is already expanded needs a rule of its own"); return MZ_ERR_ARG; }
     return MZ_OK;
 }
 
@@ -934,12 +966,12 @@ int Worker::createActors()
     return MZ_OK;
 }
 
-int Worker::resetAllSearches()
+int Worker::resetAllSearches(const uint8_t* mask) // mask: [G_], 0 = the game's tree stays (mz_think_reuse_tree)
 {
     for (auto& L : lanes_) {
         std::vector<int> rp(L->n);
         for (int j = 0; j < L->n; ++j) { rp[j] = rootPlayerFor(games_[L->g0 + j]); }
-        int rc = L->pool.resetSearch(nullptr, rp.data());
+        int rc = L->pool.resetSearch(mask ? mask + L->g0 : nullptr, rp.data());
         if (rc) { return rc; }
         if ((plan_.resident || plan_.sim_mz) && (rc = uploadRoots(*L))) { return rc; }
     }
@@ -2197,7 +2229,30 @@ int Worker::actGame(int g, int action_id, int player) // BaseActor::act (ref bas
         if (kv.first == "R") { std::ostringstream oss; oss << gm.env->reward(); kv.second = oss.str(); }
     }
     ++stats_.moves;
+    if (think_reuse_) { int rc = thinkReroot(g, action_id); if (rc) { return rc; } }
     return 1;
+}
+
+// The re-root of game g at `action` (think_reroot_kernel; the root's player is the one rootPlayerFor gives after the move: who played it).  action -1, or
+// a move whose child is missing or unexpanded, leaves the empty tree reset_search starts from.  Runs on the lane's stream, behind everything queued, and waits.
+int Worker::thinkReroot(int g, int action)
+{
+    if (!think_reuse_ || !think_) { return MZ_OK; }
+    MZ_HIP(hipSetDevice(device_));
+    int* a = think_->hostReroot();
+    for (int i = (g < 0 ? 0 : g); i < (g < 0 ? G_ : g + 1); ++i) { a[i * 2] = action; a[i * 2 + 1] = rootPlayerFor(games_[i]); }
+    int rc = think_->reroot(lanes_[0]->pool, lanes_[0]->godev.v_);
+    if (rc) { return rc; }
+    const int* st = think_->hostRerootStatus();
+    for (int i = (g < 0 ? 0 : g); i < (g < 0 ? G_ : g + 1); ++i) {
+        think_kept_[i] = st[i * 2];
+        think_moved_[i] = 1;
+        if (action >= 0) {
+            ++reuse_reroots_;
+            if (st[i * 2] > 0) { ++reuse_kept_; reuse_kept_visits_ += uint64_t(st[i * 2]); }
+        }
+    }
+    return MZ_OK;
 }
 
 int Worker::resetSearchAll() // ZeroActor::resetSearch (ref zero_actor.cpp:29-34) of every game
@@ -2214,6 +2269,17 @@ int Worker::resetSearchAll() // ZeroActor::resetSearch (ref zero_actor.cpp:29-34
         std::fill(think_done_.begin(), think_done_.end(), 0);
         int rc = think_->clearAsync();
         if (rc) { return rc; }
+        if (think_reuse_) { // a kept tree is searched on: its root's visits count towards n + 1 (isSearchDone unchanged)
+            std::vector<uint8_t> mask(G_);
+            for (int g = 0; g < G_; ++g) {
+                mask[g] = think_kept_[g] > 0 ? 0 : 1;
+                think_count_[g] = think_kept_[g];
+                think_done_[g] = think_kept_[g] >= n_ + 1 ? 1 : 0;
+                think_kept_[g] = 0;
+                think_moved_[g] = 0;
+            }
+            return resetAllSearches(mask.data());
+        }
     }
     return resetAllSearches();
 }
@@ -2264,7 +2330,7 @@ int Worker::resetGameAt(int g) // ZeroActor::reset without the search part (ref 
 {
     if (g < 0 || g >= G_) { setError("reset_game: game %d out of range", g); return MZ_ERR_ARG; }
     resetGame(games_[g], rngOf(g));
-    return MZ_OK;
+    return thinkReroot(g, -1);
 }
 
 int Worker::emitGame(int g) // ThreadSharedData::outputGame (ref actor_group.cpp:24-50)
@@ -2345,7 +2411,7 @@ int Worker::envSetTurn(int g, int player) // Env::setTurn (ref base_env.h:103)
     if (g < 0 || g >= G_ || player < 1 || player > games_[g].env->numPlayers()) { setError("env_set_turn: bad arguments"); return MZ_ERR_ARG; }
     if (!cfg_.mz_manual_step) { setError("env_set_turn: the worker plays on its own (mz_manual_step=false)"); return MZ_ERR_STATE; }
     games_[g].env->setTurn(player);
-    return MZ_OK;
+    return thinkReroot(g, -1);
 }
 
 int Worker::envResetSeed(int g, int seed) // Env::reset(seed) (ref atari.h:55; console.cpp:289): the seed comes from the caller, no draw
@@ -2354,7 +2420,7 @@ int Worker::envResetSeed(int g, int seed) // Env::reset(seed) (ref atari.h:55; c
     if (!cfg_.mz_manual_step) { setError("env_reset_seed: the worker plays on its own (mz_manual_step=false)"); return MZ_ERR_STATE; }
     games_[g].env->resetSeed(seed);
     games_[g].action_info_history.clear();
-    return MZ_OK;
+    return thinkReroot(g, -1);
 }
 
 int Worker::envRotateAction(int g, int action_id, int rotation) const // Env::getRotateAction (ref base_env.h:99)
@@ -2464,6 +2530,7 @@ int Worker::nodeInfo(int g, int which, char* buf, int cap)
     if (rc) { return rc; }
     if (which == 0) { return copyOut(nodeText(t, 0), buf, cap, "node_info"); }
     if (!search_done_) { setError("node_info: the search is not complete"); return MZ_ERR_STATE; }
+    if (think_reuse_ && think_moved_[g]) { setError("node_info: the tree of game %d was re-rooted by a move since its decision (mz_think_reuse_tree=true): the chosen node is no root child any more", g); return MZ_ERR_STATE; }
     const int sel = games_[g].selected;
     for (int e = 1; e < t.entries && t.irow(kTrParent)[e] == 0; ++e) {
         if (t.irow(kTrOrdinal)[e] == sel) { return copyOut(nodeText(t, e), buf, cap, "node_info"); }
@@ -2495,7 +2562,7 @@ int Worker::loadModel(const std::string& path, const mz_net_desc& file_desc, con
         }
     }
     cfg_.nn_file_name = path;
-    return MZ_OK;
+    return thinkReroot(-1, -1); // (mz_think_reuse_tree) a kept tree holds the old network's outputs
 }
 
 int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
@@ -2513,6 +2580,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         sims_done_ = 0;
         pending_ = false;
         for (auto& L : lanes_) { MZ_HIP(hipStreamSynchronize(L->stream)); }
+        if (think_reuse_) { std::fill(think_kept_.begin(), think_kept_.end(), 0); }
         return resetAllSearches();
     } else if (prefix == "load_model") {
         if (line.find(' ') == std::string::npos) { setError("load_model needs a path"); return MZ_ERR_ARG; }
@@ -2521,7 +2589,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         if (shared_net_ || external_) { // the caller's Network::loadModel has (or will have) reloaded the weights; the actor only follows the name (EV tag)
             pending_weights_.clear();
             cfg_.nn_file_name = path;
-            return MZ_OK;
+            return thinkReroot(-1, -1);
         }
         if (pending_weights_.empty()) { // the reference's path: every network re-reads the file (actor_group.cpp:227-232)
             mz_net_desc nd;
@@ -2545,7 +2613,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         MZ_FIXED(actor_gumbel_sigma_visit_c) MZ_FIXED(actor_gumbel_sigma_scale_c) MZ_FIXED(zero_num_threads) MZ_FIXED(zero_num_parallel_games)
         MZ_FIXED(nn_type_name) MZ_FIXED(env_board_size) MZ_FIXED(env_go_komi) MZ_FIXED(env_go_ko_rule) MZ_FIXED(env_game) MZ_FIXED(atari_init_q)
         MZ_FIXED(env_atari_name) MZ_FIXED(env_atari_episode_length) MZ_FIXED(mz_pipeline_lanes) MZ_FIXED(mz_rng_streams) MZ_FIXED(mz_cpu_base) MZ_FIXED(mz_signal_wait)
-        MZ_FIXED(mz_sim_kernel) MZ_FIXED(mz_sim_cluster) MZ_FIXED(mz_sim_split) MZ_FIXED(mz_sim_rounds) MZ_FIXED(mz_sim_round_min) MZ_FIXED(mz_sim_round_alt) MZ_FIXED(mz_sim_round_batch) MZ_FIXED(mz_sim_rounds_board) MZ_FIXED(mz_sim_round_pairs) MZ_FIXED(mz_sim_round_leaves) MZ_FIXED(mz_manual_step) MZ_FIXED(mz_nn_precision) MZ_FIXED(mz_raw_observations) MZ_FIXED(mz_device_env) MZ_FIXED(mz_zero_copy)
+        MZ_FIXED(mz_sim_kernel) MZ_FIXED(mz_sim_cluster) MZ_FIXED(mz_sim_split) MZ_FIXED(mz_sim_rounds) MZ_FIXED(mz_sim_round_min) MZ_FIXED(mz_sim_round_alt) MZ_FIXED(mz_sim_round_batch) MZ_FIXED(mz_sim_rounds_board) MZ_FIXED(mz_sim_round_pairs) MZ_FIXED(mz_sim_round_leaves) MZ_FIXED(mz_manual_step) MZ_FIXED(mz_nn_precision) MZ_FIXED(mz_raw_observations) MZ_FIXED(mz_device_env) MZ_FIXED(mz_zero_copy) MZ_FIXED(mz_think_reuse_tree)
         // a match's length, names and arithmetic are part of its records and its tally from step 0 (every other worker never reads the five keys)
         MZ_FIXED(mz_match_games) MZ_FIXED(mz_match_name_a) MZ_FIXED(mz_match_name_b) MZ_FIXED(mz_match_precision_a) MZ_FIXED(mz_match_precision_b)
         if (match_) { MZ_FIXED(zero_actor_intermediate_sequence_length) }
@@ -2779,6 +2847,11 @@ int mz_worker_env_rotate_action(const mz_worker* w, int game, int action_id, int
 {
     if (!w) { mz::setError("NULL worker"); return MZ_ERR_ARG; }
     return w->w.envRotateAction(game, action_id, rotation);
+}
+int mz_worker_think_reuse_stats(mz_worker* w, uint64_t* reroots, uint64_t* kept, uint64_t* kept_visits)
+{
+    if (!w) { mz::setError("think_reuse_stats: NULL argument"); return MZ_ERR_ARG; }
+    return w->w.thinkReuseStats(reroots, kept, kept_visits);
 }
 int mz_worker_think_stats(mz_worker* w, uint64_t* steps, uint64_t* walks, uint64_t* queries)
 {

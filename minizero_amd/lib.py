@@ -164,6 +164,11 @@ def load():
         if hasattr(L, "mz_worker_think_stats"):  # (MZ_LIBMZGPU may name a build from before the batched think: tools/think_bench.py measures one)
             u64p = C.POINTER(C.c_uint64)
             L.mz_worker_think_stats.argtypes = [vp, u64p, u64p, u64p]
+        if hasattr(L, "mz_worker_reset_game"):  # (per-actor stepping: likewise absent from a build that MZ_LIBMZGPU may name)
+            L.mz_worker_reset_game.argtypes = [vp, C.c_int]
+            L.mz_worker_env_query.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        if hasattr(L, "mz_worker_think_reuse_stats"):  # (likewise: a build from before mz_think_reuse_tree)
+            L.mz_worker_think_reuse_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
         L.mz_worker_search_done.argtypes = [vp]
         L.mz_worker_search_action.argtypes = [vp, C.c_int, ip, ip, ip]
         L.mz_worker_act.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -556,6 +561,13 @@ class Worker:
         _check(self.L, self.L.mz_worker_think_stats(self.h, C.byref(s), C.byref(w), C.byref(q)))
         return s.value, w.value, q.value
 
+    def think_reuse_stats(self):
+        """(reroots, kept, kept_visits) of mz_think_reuse_tree=true: the moves mz_worker_act handed to the re-root, those that kept a subtree for the next
+        search, and the sum of the kept roots' visits — the simulations the next searches did not have to run; zeros with the key off"""
+        r, k, v = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        _check(self.L, self.L.mz_worker_think_reuse_stats(self.h, C.byref(r), C.byref(k), C.byref(v)))
+        return r.value, k.value, v.value
+
     def search_done(self):
         return _check(self.L, self.L.mz_worker_search_done(self.h)) == 1
 
@@ -570,6 +582,20 @@ class Worker:
 
     def reset_search(self):
         _check(self.L, self.L.mz_worker_reset_search(self.h))
+
+    def reset_game(self, game):
+        """ZeroActor::reset() of one game without the search part (mz_worker_reset_game; mz_manual_step): a new game and its resign coin"""
+        _check(self.L, self.L.mz_worker_reset_game(self.h, game))
+
+    def env_query(self, game, what):
+        """mz_worker_env_query: what = 0 isTerminal, 1 getTurn, 2 getEvalScore(false), 3 getEvalScore(true), 4 number of actions played, 5 getReward"""
+        out = C.c_float()
+        _check(self.L, self.L.mz_worker_env_query(self.h, game, what, C.byref(out)))
+        return out.value
+
+    def tree_size(self, game):
+        """the number of entries mz_worker_tree gives for the game (its visited nodes)"""
+        return _check(self.L, self.L.mz_worker_tree_size(self.h, game))
 
     def finish_search(self):
         _check(self.L, self.L.mz_worker_finish_search(self.h))
