@@ -54,6 +54,9 @@ ROWS = {
     "tictactoe_mz3": f"env_game=tictactoe:actor_num_simulation=8:zero_num_parallel_games=8{_mz(3)}:learner_batch_size=64:program_seed=9|kind=oracle,cycles=360,cap=3",
     "go9_hand_mz3": f"env_game=go:env_board_size=9{_mz(3)}:learner_batch_size=64:program_seed=5|kind=hand,games=3,seed=150,cut=50,passes=0.1,short=2,cap=6",
     "go5_hand_az": "env_game=go:env_board_size=5:learner_batch_size=48:program_seed=6|kind=hand,games=3,seed=160,cut=30,passes=0.15,cap=6",
+    # beyond two 64-bit words per plane, the records played by the rules model (tests/go_rules.py) and not by the oracle: captures, passes, two passes at the end
+    "go13_hand_az": "env_game=go:env_board_size=13:learner_batch_size=32:program_seed=7|kind=hand,by=model,games=2,seed=200,cut=120,passes=0.05,cap=6",
+    "go19_hand_mz3": f"env_game=go:env_board_size=19{_mz(3)}:learner_batch_size=32:program_seed=8|kind=hand,by=model,games=2,seed=210,cut=150,passes=0.05,short=2,cap=6",
     "othello8_hand_mz3": f"env_game=othello:env_board_size=8{_mz(3)}:learner_batch_size=64:program_seed=7|kind=hand,games=2,seed=170,short=2,cap=6",
     "othello4_hand_az": "env_game=othello:env_board_size=4:learner_batch_size=32:program_seed=8|kind=hand,games=4,seed=180,cap=6",
     "tictactoe_hand_az": "env_game=tictactoe:learner_batch_size=32:program_seed=9|kind=hand,games=5,seed=190,cap=6",
@@ -150,7 +153,29 @@ def playout_records(conf, spec):
     return out
 
 
+def model_go_records(conf, spec):
+    """hand-written tags over games the Go rules model plays: uniformly random legal points, a pass with probability `passes`, two passes after `cut` moves (more than 4)"""
+    game, n, _ = rule_envs.parse(conf)
+    muzero = "nn_type_name=muzero" in conf
+    out = []
+    lengths = [int(spec["cut"])] * int(spec["games"]) + ([int(spec["short"])] if "short" in spec else [])
+    for k, cut in enumerate(lengths):
+        rng = np.random.default_rng(int(spec["seed"]) + k)
+        env = rule_envs.RuleEnv(conf)
+        moves = []
+        while not env.terminal() and not (cut <= 4 and len(moves) >= cut):  # (a short game is cut off, as if one side resigned)
+            legal = np.nonzero(env.legal())[0]
+            a = n * n if len(moves) >= cut or len(legal) == 1 or rng.random() < float(spec["passes"]) else int(rng.choice(legal[:-1]))
+            moves.append((a, p_tag(rng, legal, a)))
+            env.act(a, env.turn())
+        dlen = _partial(len(moves), rng) if k == 1 % len(lengths) and len(moves) > 4 else None
+        out.append(write_record(game, n, _result(env.score(), rng), moves, dlen, muzero, rng))
+    return out
+
+
 def hand_records(conf, spec):
+    if spec.get("by") == "model":
+        return model_go_records(conf, spec)
     import loader_cases as lc
     import oracle_lib
     kv = _kv(conf)

@@ -2,7 +2,8 @@
 (area scoring: a point counts for a colour if it is that colour or only that colour can be reached from it through empty points; no suicide; a play
 may not recreate an earlier whole-board position — positional superko) and the reference's two ending rules (two consecutive passes; more than
 2 * N * N moves, ref environment/go/go.cpp:246-257).  Checked against BOTH CPU rules engines — the oracle's (block / liberty bitsets, oracle/o_env.cpp)
-and the product's host engine (flat board + flood fill, minizero_amd/csrc/env.cpp) — and, with a GPU, against the device engine (go_dev.hip) in
+and the product's host engine (flat board + flood fill, minizero_amd/csrc/env.cpp) —, against the rules model of tests/go_rules.py that both engines are held
+to in tests/test_go_model.py, and, with a GPU, against the device engine (go_dev.hip) in
 tests/test_gpu_godev.py::test_device_known_answers.  The search oracle stays "parity unpinned" (DESIGN.md 5); this narrows what an unpinned rules
 engine could hide.  Scores are read through the winner under two komi values that bracket the hand-counted area difference."""
 import numpy as np
@@ -16,9 +17,25 @@ def p(r, c, n=N):
     return r * n + c
 
 
-@pytest.fixture(params=["oracle", "product"])
+class ModelEnv:
+    """tests/go_rules.py behind the calls these tests make"""
+
+    def __init__(self, n, komi, rule):
+        from go_rules import Go
+        self.g = Go(n, komi, rule)
+
+    def act(self, a): return self.g.act(a)
+    def turn(self): return self.g.turn
+    def legal_mask(self): return self.g.legal_mask()
+    def is_terminal(self): return self.g.is_terminal()
+    def eval_score(self, resign=False): return self.g.eval_score(resign)
+
+
+@pytest.fixture(params=["oracle", "product", "model"])
 def make_env(request, oracle, mz):
     def make(n=N, komi=0.5, rule="positional"):
+        if request.param == "model":
+            return ModelEnv(n, komi, rule)
         conf = f"env_game=go:env_board_size={n}:env_go_komi={komi}:env_go_ko_rule={rule}"
         return oracle.OracleEnv(conf) if request.param == "oracle" else mz.Env(conf)
     return make

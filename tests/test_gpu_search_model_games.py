@@ -1,4 +1,4 @@
-"""Gomoku, Hex, NoGo and Havannah self-play held to the search model: the HIP worker against tests/search_model.py playing in tests/rule_envs.py, as exact
+"""Gomoku, Hex, NoGo and Havannah self-play, and whole games of Go and Othello in the environment of their rules models, held to the search model: the HIP worker against tests/search_model.py playing in tests/rule_envs.py, as exact
 strings — action played, P dictionary, V tag, R tag, where the game ended and, for whole games, the RE tag — for every game of the pool, on the three
 execution paths of these games: the per-game simulation kernel where the board has an instance, lock-step with the device rules, lock-step with the host
 rules.  The three paths share the host search code, the candidate building and the use of the score at terminal leaves; comparing them with each other
@@ -44,7 +44,8 @@ def run_row(mz, oracle, name, wseed, path):
 @pytest.mark.parametrize("name,wseed", T.ALL_GAME_CASES)
 def test_game_row_equals_model(mz, oracle, name, wseed, path):
     """first moves on the simulation-kernel instances (Hex 11x11 with the swap, Gomoku 15x15 standard and outer-open, NoGo 9x9, Havannah edge 8 and edge 4),
-    whole games through them, whole games on boards without an instance, and the resign row: the worker resigns at the move where the model does
+    whole games through them, whole games on boards without an instance, whole Go games (4x4, 5x5 lock-step; 7x7 and 9x9 through sim_kernel_wide, 9x9 on
+    8 channels through sim_kernel<9,9,20,8,2>) and Othello games (8x8 through its sim_kernel instance; 4x4, 6x6 lock-step), and the resign row: the worker resigns at the move where the model does
     (check_against compares the moves played and whether the game ended there)"""
     run_row(mz, oracle, name, wseed, path)
 

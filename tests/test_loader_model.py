@@ -51,15 +51,13 @@ def check_batch(m, bufs, tag, planes=None):
 @pytest.mark.parametrize("name", C.ORACLE_GAMES)
 def test_model_equals_the_oracle(oracle, tmp_path, name):
     """three batches of the oracle's loader, then one update_priority with fixed values on both sides and another batch: policy, value, reward and in-game
-    action planes bit for bit, loss scales within the bound; Atari's planes too (Go, Othello and TicTacToe have no Python rules: every rotation is allowed
-    for their planes, and one of them must explain the targets)"""
+    action planes bit for bit, loss scales within the bound; the planes too: Atari's from the OBS tag, the board games' from the rules models"""
     m, ol = _model(name), _oracle_loader(oracle, name, tmp_path)
     assert ol.num_games() == m.num_games() and ol.num_data() == m.num_data() > 0
-    planes = None if m.cfg.game == "atari" else (lambda g, pos, f: m.cfg.rotations)
     for it in range(4):
         bufs = C.buffers(m.cfg)
         ol.sample_data(*bufs)
-        check_batch(m, bufs, f"{name} batch {it}", planes)
+        check_batch(m, bufs, f"{name} batch {it}")
         if it == 2:
             vals = C.fixed_values(m.cfg)
             ol.update_priority(bufs[6], vals)

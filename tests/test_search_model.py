@@ -1,7 +1,7 @@
 """The search model of tests/search_model.py (a third implementation, written from the reference's text) pinned by paper-and-pencil literals, then compared with
 the oracle's search as exact strings: action played, P tag, V tag, resignation, move by move.  The same table of configurations runs against the HIP worker in
-tests/test_gpu_search_model.py.  A second table (GAME_CASES, GAME_NOISY) holds the rows of the games no oracle plays — Gomoku, Hex, NoGo, Havannah — which the
-model plays over tests/rule_envs.py: tests/test_search_model_games.py pins what they show, tests/test_gpu_search_model_games.py runs them against the HIP
+tests/test_gpu_search_model.py.  A second table (GAME_CASES, GAME_NOISY) holds the rows of the games no oracle plays — Gomoku, Hex, NoGo, Havannah — and
+whole games of Go and Othello, which the model plays over tests/rule_envs.py: tests/test_search_model_games.py pins what they show, tests/test_gpu_search_model_games.py runs them against the HIP
 worker.  Nothing here compares with a tolerance."""
 import ctypes as C
 import re
@@ -14,6 +14,7 @@ import hand_cases as H
 from helpers import sharpen
 import rule_envs
 import search_model as S
+from tictactoe_rules import TicTacToe
 
 f32 = np.float32
 
@@ -153,43 +154,6 @@ class OracleEnvAdapter:
         buf = np.zeros(4096, np.float32)
         n = self.e.L.mzo_env_action_features(self.e.h, a, player, buf.ctypes.data_as(C.POINTER(C.c_float)))
         return buf[:n].copy()
-
-
-class TicTacToe:
-    """environment/tictactoe/tictactoe.cpp: rules, result and the four planes (own, opponent, player 1 to move, player 2 to move)"""
-    LINES = [(0, 1, 2), (3, 4, 5), (6, 7, 8), (0, 3, 6), (1, 4, 7), (2, 5, 8), (0, 4, 8), (2, 4, 6)]
-
-    def __init__(self, board=None, to_move=1):
-        self.board, self.to_move = list(board or [0] * 9), to_move
-
-    def clone(self): return TicTacToe(self.board, self.to_move)
-
-    def act(self, a, player):
-        assert self.board[a] == 0
-        self.board[a], self.to_move = player, 3 - player
-
-    def num_players(self): return 2
-    def turn(self): return self.to_move
-    def legal(self): return [int(b == 0) for b in self.board]
-
-    def winner(self):
-        for i, j, k in self.LINES:
-            if self.board[i] and self.board[i] == self.board[j] == self.board[k]:
-                return self.board[i]
-        return 0
-
-    def terminal(self): return self.winner() != 0 or 0 not in self.board
-    def eval_score(self): return f32({0: 0.0, 1: 1.0, 2: -1.0}[self.winner()])
-    def reward(self): return f32(0)
-
-    def features(self):
-        me, you = self.to_move, 3 - self.to_move
-        return np.array([b == me for b in self.board] + [b == you for b in self.board] + [me == 1] * 9 + [me == 2] * 9, np.float32)
-
-    def action_features(self, a, player):
-        f = np.zeros(9, np.float32)
-        f[a] = 1
-        return f
 
 
 class NetAdapter:
@@ -346,8 +310,17 @@ def _gomoku(n, rule="standard", five=True):
     return conf, _net(f"gomoku_{'oo_' if rule == 'outer_open' else ''}{n}x{n}", 4, n, n * n)
 
 
-# the boards with a simulation-kernel instance (32 channels): every other board of these games plays lock-step on the default plan
-SIM_BOARDS = {("hex", 11), ("gomoku", 15), ("nogo", 9), ("havannah", 8), ("havannah", 4)}
+def _go(n, komi=0.5, rule="positional", net=None):
+    conf = f"env_game=go:env_board_size={n}:env_go_komi={komi}" + ("" if rule == "positional" else f":env_go_ko_rule={rule}")
+    return conf, net or _net(f"go_{n}x{n}", 18, n, n * n + 1)
+
+
+def _othello(n, net=None): return f"env_game=othello:env_board_size={n}", net or _net(f"othello_{n}x{n}", 4, n, n * n + 1)
+
+
+# the boards with a simulation-kernel instance (32 channels; Go 9x9 and Othello 8x8 also on the 8-channel networks GO8 and OTH8): every other board of these
+# games plays lock-step on the default plan
+SIM_BOARDS = {("hex", 11), ("gomoku", 15), ("nogo", 9), ("havannah", 8), ("havannah", 4), ("go", 7), ("go", 9), ("othello", 8)}
 
 
 def has_sim_instance(conf):
@@ -355,7 +328,12 @@ def has_sim_instance(conf):
     return (game, n) in SIM_BOARDS
 
 
-PUCT16, GUMBEL16, GUMBEL50 = ":actor_num_simulation=16", _gumbel(16, 16), _gumbel(50, 16)
+# the weight seeds of the Go and Othello rows (PUCT, Gumbel), chosen like the others
+# (seed 1 raises AmbiguousOrder on Go 9x9 under Gumbel with either network, seed 3 with GO8; go9 PUCT seed 1 and go7 PUCT seed 3 end after 3 and 4 moves)
+GO4_SEEDS, GO5_SEEDS, GO7_SEEDS, GO9_SEEDS, GO9C8_SEEDS = ((3, 4), (1, 2)), ((1, 4), (1,)), ((1,), (1,)), ((2,), (2,)), ((1, 2), (2,))
+GO5_POS_SEEDS = ((11,), (1,))  # (PUCT seed 11: the row on which the two ko rules give different games)
+OTH8_SEEDS, OTH4_SEEDS, OTH6_SEEDS, GO4_N50_SEEDS, OTH4_N50_SEEDS = ((1, 2), (3,)), ((1, 4), (1,)), ((3,), (1,)), (3,), (1,)
+PUCT16, GUMBEL16, GUMBEL50, PUCT50 = ":actor_num_simulation=16", _gumbel(16, 16), _gumbel(50, 16), ":actor_num_simulation=50"
 NO_RESIGN = ":actor_resign_threshold=-2"
 WHOLE = 400  # more moves than any of these boards has cells: a whole-game row ends where the game does
 
@@ -380,6 +358,20 @@ for _b, (_c, _d), _seeds in (("hav4", _hav(4), ((2, 3), (2, 6))), ("nogo9", _nog
         GAME_CASES[f"{_b}_game_{_s}"] = (_c + _search + NO_RESIGN, _d, _sd, WHOLE, 2, None)
 # d. the default resign threshold (-0.9) with the value head times 32: with seed 3 Black plays one move and White resigns, with seed 2 Black resigns at once
 GAME_CASES["hex11_puct_n16_resign"] = (_hex(11)[0] + PUCT16, _hex(11)[1], (2, 3), 3, 4, 32)
+# f. Go and Othello, whole games in the environment of the rules models (tests/go_rules.py, tests/othello_rules.py; tests/test_go_model.py and
+# tests/test_othello_model.py hold the host engine and the oracle to them): captures, superko refusals along the tree path, two-pass leaves, leaves past
+# the move cap, Tromp-Taylor results with a komi at which both colours win; forced passes and the end of the game in Othello.  go4, go5: lock-step;
+# go7, go9: sim_kernel_wide<7,7,32,32,1> and <9,9,32,32,2>; go9c8: sim_kernel<9,9,20,8,2>; oth8: sim_kernel<8,8,4,8,kRulesOthello>; oth4, oth6: lock-step
+GO_OTHELLO_ROWS = (("go4", _go(4, 1.0), GO4_SEEDS), ("go5", _go(5), GO5_POS_SEEDS), ("go5_sit", _go(5, 0.5, "situational"), GO5_SEEDS), ("go7", _go(7), GO7_SEEDS), ("go9", _go(9), GO9_SEEDS),
+                   ("go9c8", _go(9, net=GO8), GO9C8_SEEDS), ("oth8", _othello(8, OTH8), OTH8_SEEDS), ("oth4", _othello(4), OTH4_SEEDS), ("oth6", _othello(6), OTH6_SEEDS))
+for _b, (_c, _d), _seeds in GO_OTHELLO_ROWS:
+    for _s, _search, _sd in zip(("puct", "gumbel"), (PUCT16, GUMBEL16), _seeds):
+        GAME_CASES[f"{_b}_game_{_s}"] = (_c + _search + NO_RESIGN, _d, _sd, WHOLE, 2, None)
+# 50 simulations on the smallest boards: trees deep enough for two-pass leaves
+GAME_CASES["go4_game_puct_n50"] = (_go(4, 1.0)[0] + PUCT50 + NO_RESIGN, _go(4)[1], GO4_N50_SEEDS, WHOLE, 2, None)
+GAME_CASES["oth4_game_puct_n50"] = (_othello(4)[0] + PUCT50 + NO_RESIGN, _othello(4)[1], OTH4_N50_SEEDS, WHOLE, 2, None)
+GO_ROWS = [n for n in GAME_CASES if re.match(r"go\d", n)]
+OTHELLO_ROWS = [n for n in GAME_CASES if n.startswith("oth")]
 WHOLE_GAMES = [name for name, c in GAME_CASES.items() if c[3] == WHOLE]
 # whole-game rows whose model takes more than about ten seconds on the CPU (DESIGN.md lists the seconds of every row)
 SLOW_GAMES = ("gomoku15_game_puct",)
@@ -433,15 +425,19 @@ def is_atari(conf):
     return model_cfg(conf)[2]["env_game"] == "atari"
 
 
-def make_env(oracle, conf, env_seed=None):
-    """the environment the model plays in; an Atari-shaped game is that of `env_seed`, the SD tag of the record it is compared with"""
+ORACLE_PLAYS = ("go", "othello", "tictactoe")
+
+
+def make_env(oracle, conf, env_seed=None, rules=False):
+    """the environment the model plays in; an Atari-shaped game is that of `env_seed`, the SD tag of the record it is compared with.  rules: the rules model
+    of tests/rule_envs.py also for the games the oracle plays (the rows of GAME_CASES; test_first_move_rows_on_the_rules_models)"""
     kv = model_cfg(conf)[2]
-    if kv["env_game"] == "tictactoe":
+    if kv["env_game"] == "tictactoe" and not rules:
         return TicTacToe()
     if kv["env_game"] == "atari":
         assert env_seed is not None, "an Atari-shaped game is defined by its seed"
         return AtariSynth(env_seed, int(kv["env_atari_episode_length"]))
-    if kv["env_game"] in rule_envs.GAMES:
+    if rules or kv["env_game"] not in ORACLE_PLAYS:
         return rule_envs.RuleEnv(full_conf(conf))  # no oracle for these games: the rules models of tests/, configured by the worker's own string
     return OracleEnvAdapter(oracle, ":".join(f"{k}={kv[k]}" for k in ("env_game", "env_board_size") if k in kv))
 
@@ -511,7 +507,7 @@ def model_of(oracle, name, wseed, env_seed=None):
         conf, desc_args, _, moves, _, vgain = row(name)
         trace = {}
         _MODEL_CACHE[name, wseed, env_seed] = expected_from_model(oracle, conf, desc_args, wseed, moves, weights=case_weights(oracle, desc_args, wseed, vgain),
-                                                                  env_seed=env_seed, trace=trace)
+                                                                  env_seed=env_seed, trace=trace, env=make_env(oracle, conf, rules=True) if name in GAME_CASES else None)
         _MODEL_CACHE["env", name, wseed, env_seed] = trace["env"]
     return _MODEL_CACHE[name, wseed, env_seed]
 
@@ -552,6 +548,18 @@ def test_model_equals_oracle(oracle, name, wseed):
         assert all(len(model(sd)[0]) == moves and model(sd)[2] for _, _, sd in got)
     else:
         assert len(model[0]) >= 1 or model[1]
+
+
+RULES_CASES = [(n, s) for n, s in ALL_CASES if n.startswith(("go", "othello", "ttt"))]
+
+
+@pytest.mark.parametrize("name,wseed", RULES_CASES, ids=lambda x: str(x))
+def test_first_move_rows_on_the_rules_models(oracle, name, wseed):
+    """the Go, Othello and TicTacToe rows of CASES played by the model in the rules models' environment (tests/rule_envs.py) give the same games as in the
+    oracle's: actions, P, V and R strings, and where the game ended"""
+    conf, desc_args, _, moves, _, vgain = CASES[name]
+    got = expected_from_model(oracle, conf, desc_args, wseed, moves, weights=case_weights(oracle, desc_args, wseed, vgain), env=make_env(oracle, conf, rules=True))
+    assert got == model_of(oracle, name, wseed)
 
 
 def test_resign_case_resigns_and_plays(oracle):

@@ -1,11 +1,13 @@
-"""What the Gomoku, Hex, NoGo and Havannah rows of tests/test_search_model.py (GAME_CASES, GAME_NOISY) are for, pinned on the CPU with the model alone: no
-oracle plays these games, so nothing here compares two searches.  Each test is a condition a row must meet for its GPU run
+"""What the Gomoku, Hex, NoGo and Havannah rows and the Go and Othello whole-game rows of tests/test_search_model.py (GAME_CASES, GAME_NOISY) are for,
+pinned on the CPU with the model alone: the model plays them in the rules models' environment, so nothing here compares two searches.  Each test is a condition a row must meet for its GPU run
 (tests/test_gpu_search_model_games.py) to see what it is there to see — a row that backed up no terminal leaf would pass whatever sign the worker gives
 a terminal value — and the last one ties the environment the model played in (tests/rule_envs.py over the four rules models) to the product's host
 engine, position by position."""
 import numpy as np
 import pytest
 
+from go_rules import Go
+from othello_rules import Othello
 import rule_envs
 import search_model as S
 import test_search_model as T
@@ -46,13 +48,19 @@ def test_every_game_has_its_rows():
     assert {"hex11_gumbel_n50", "gomoku15_gumbel_n50", "nogo9_gumbel_n50", "hav8_gumbel_n50"} <= names
     for b in ("hav4", "hav8", "nogo9", "hex11", "gomoku15", "hex4", "hex4_noswap", "hex5", "hex5_noswap", "nogo4", "gomoku5", "gomoku6", "gomoku6_freestyle"):
         assert {f"{b}_game_puct", f"{b}_game_gumbel"} <= names
+    for b in ("go4", "go5", "go5_sit", "go7", "go9", "go9c8", "oth8", "oth4", "oth6"):
+        assert {f"{b}_game_puct", f"{b}_game_gumbel"} <= names
+    assert {"go4_game_puct_n50", "oth4_game_puct_n50"} <= names
     for name, (conf, desc, seeds, moves, games, vgain) in T.GAME_CASES.items():
         cfg, muzero, kv = T.model_cfg(conf)
-        assert not muzero and seeds and desc[9] == rule_envs.policy_size(T.full_conf(conf)) and desc[4] == 32 and desc[8] == 1 and desc[10] == 16
+        assert not muzero and seeds and desc[9] == rule_envs.policy_size(T.full_conf(conf)) and desc[8] == 1 and desc[10] == 16
+        assert desc[4] == (8 if name.startswith(("go9c8", "oth8")) else 32) and (desc[4] == 32 or desc in (T.GO8, T.OTH8))
         assert (cfg.actor_num_simulation, cfg.actor_gumbel_sample_size) in ((16, 16), (50, 16))
         whole = name in T.WHOLE_GAMES
         assert games == (2 if whole else 4) and (cfg.actor_resign_threshold == -2.0) == whole
-        assert T.has_sim_instance(conf) == (not whole or name.startswith(("hav4", "hav8", "nogo9", "hex11", "gomoku15")))
+        assert T.has_sim_instance(conf) == (not whole or name.startswith(("hav4", "hav8", "nogo9", "hex11", "gomoku15", "go7", "go9", "oth8")))
+        if name in T.GO_ROWS:  # a komi at which both colours win; one row under the situational rule
+            assert kv["env_go_komi"] in ("0.5", "1.0") and (kv.get("env_go_ko_rule") == "situational") == name.startswith("go5_sit")
 
 
 def test_game_rows_show_what_they_are_for(oracle):
@@ -61,7 +69,7 @@ def test_game_rows_show_what_they_are_for(oracle):
     freestyle Gomoku row is won by six in a row, which the exactly-five rule does not count."""
     results, swap = {}, {}
     few_nogo = False
-    for name in T.WHOLE_GAMES:
+    for name in [n for n in T.WHOLE_GAMES if n not in T.GO_ROWS + T.OTHELLO_ROWS]:
         conf = T.GAME_CASES[name][0]
         game, _, kw = rule_envs.parse(T.full_conf(conf))
         for wseed in T.GAME_CASES[name][2]:
@@ -86,6 +94,101 @@ def test_game_rows_show_what_they_are_for(oracle):
     assert not m.exactly_five and m.winner and 6 in lines and 5 not in lines
 
 
+def _two_passes(hist, n):
+    return len(hist) >= 2 and hist[-1] == hist[-2] == n * n
+
+
+def test_go_and_othello_rows_show_what_they_are_for(oracle):
+    """Counted by the adapter over the Go rows: at least 50 terminal leaves backed up per PUCT row (leaves past the move cap, at the end of a game as long as
+    the cap, among them), a two-pass leaf, a leaf past the cap, terminal values of both signs and a drawn one (komi 1 on 4x4), a node inside a search whose
+    legal mask is smaller than the history-free rules give (a superko refusal in the tree), games won by either colour.  Over the Othello rows: a forced
+    pass inside a tree, terminal leaves of both signs, a drawn game."""
+    seen = {g: dict(two_pass=0, past_cap=0, values=set(), superko=0, forced=0, results=set()) for g in ("go", "othello")}
+    for name in T.GO_ROWS + T.OTHELLO_ROWS:
+        conf = T.GAME_CASES[name][0]
+        game, n, _ = rule_envs.parse(T.full_conf(conf))
+        for wseed in T.GAME_CASES[name][2]:
+            env, s = T.model_env_of(oracle, name, wseed), seen[game]
+            leaves = env.stats["terminal_leaves"]
+            if not T.model_cfg(conf)[0].actor_use_gumbel:
+                assert len(leaves) >= 50, (name, wseed, len(leaves))
+            s["two_pass"] += sum(_two_passes(h, n) for h, _ in leaves)
+            s["past_cap"] += sum(game == "go" and len(h) > 2 * n * n and not _two_passes(h, n) for h, _ in leaves)
+            s["values"] |= {float(v) for _, v in leaves}
+            s["superko"] += env.stats["superko_in_tree"]
+            s["forced"] += env.stats["forced_pass_in_tree"]
+            s["results"].add(float(env.score()))
+    print(seen)
+    go, oth = seen["go"], seen["othello"]
+    assert go["two_pass"] >= 1 and go["past_cap"] >= 1 and go["values"] == {1.0, -1.0, 0.0} and go["superko"] >= 1 and {1.0, -1.0} <= go["results"]
+    assert oth["forced"] >= 1 and {1.0, -1.0} <= oth["values"] and oth["results"] == {1.0, -1.0, 0.0}
+
+
+# ---- wrong readings of the rules, each of which the rows tell from the model ----------------------------------------------------------------------
+class SimpleKoGo(Go):
+    """superko reduced to the simple ko: only the position of two plies ago is refused"""
+    def refusal(self, a, player=None):
+        r = super().refusal(a, player)
+        return None if isinstance(r, tuple) and r[1] != 2 else r
+
+
+class NoKomiGo(Go):
+    """komi left out of the result"""
+    def eval_score(self, resign=False):
+        b, w = self.areas()
+        return super().eval_score(True) if resign else 1.0 if b > w else -1.0 if b < w else 0.0
+
+
+class OtherKoRuleGo(Go):
+    """the situational rule in place of the positional one"""
+    def key(self, board, to_move): return (tuple(board), to_move)
+
+
+class CapOffByOneGo(Go):
+    """the move cap with >= in place of >"""
+    def is_terminal(self): return super().is_terminal() or len(self.actions) >= 2 * self.P
+
+
+class PassAlwaysLegalOthello(Othello):
+    """the pass legal while a placing move exists"""
+    def is_legal(self, a, player=None): return a == self.P or super().is_legal(a, player)
+
+
+class DrawIsALossOthello(Othello):
+    """equal disc counts scored as White's win"""
+    def eval_score(self, resign=False):
+        v = super().eval_score(resign)
+        return -1.0 if v == 0.0 and not resign and not self.can_place(1) and not self.can_place(2) else v
+
+
+def with_model(model_class):
+    """the adapter over a mutant rules model, configured like the row"""
+    class Mutant(rule_envs.RuleEnv):
+        def __init__(self, conf, _from=None):
+            super().__init__(conf, _from=_from)
+            if _from is None:
+                self.model = model_class(self.n, **rule_envs.parse(conf)[2])
+    return Mutant
+
+
+# mutant -> the rows (first weight seed) of which at least one must play another game
+RULE_MUTANTS = {SimpleKoGo: ("go5_sit_game_puct", "go7_game_puct", "go4_game_puct_n50"), NoKomiGo: ("go4_game_puct", "go5_sit_game_puct"),
+                OtherKoRuleGo: ("go5_game_puct",), CapOffByOneGo: ("go5_sit_game_puct",),
+                PassAlwaysLegalOthello: ("oth4_game_puct",), DrawIsALossOthello: ("oth4_game_gumbel", "oth6_game_gumbel")}
+
+
+@pytest.mark.parametrize("mutant", list(RULE_MUTANTS), ids=lambda m: m.__name__)
+def test_go_and_othello_rows_would_see_a_wrong_reading_of_the_rules(oracle, mutant):
+    """with the mutant rules in the environment the search plays in, the model plays another game (other moves, or other P / V strings) on at least one
+    row: a worker with that mistake on all its paths would differ from the model there"""
+    differs = []
+    for name in RULE_MUTANTS[mutant]:
+        wseed = T.GAME_CASES[name][2][-1 if name == "go5_sit_game_puct" else 0]
+        differs.append(_mutant_game(oracle, name, wseed, with_model(mutant))[0] != T.model_of(oracle, name, wseed)[0])
+    print(mutant.__name__, dict(zip(RULE_MUTANTS[mutant], differs)))
+    assert any(differs)
+
+
 class WrongSign(rule_envs.RuleEnv):
     """the terminal value seen from the wrong player"""
     def score(self): return np.float32(-super().score())
@@ -106,7 +209,7 @@ def test_whole_game_rows_would_see_a_wrong_terminal_value(oracle):
     board without a simulation-kernel instance plays another game under PUCT (other moves, or other V strings), and so does the Havannah edge 4 row —
     all but Gomoku 5x5, whose terminal leaves are all draws; with Gomoku's draw backed up as a loss that row does.  A worker that made either mistake on all three of its paths alike
     would therefore differ from the model in these rows."""
-    rows = [n for n in T.WHOLE_GAMES if n.endswith("_puct") and (n == "hav4_game_puct" or not T.has_sim_instance(T.GAME_CASES[n][0]))]
+    rows = [n for n in T.WHOLE_GAMES if n.endswith("_puct") and n not in T.GO_ROWS + T.OTHELLO_ROWS and (n == "hav4_game_puct" or not T.has_sim_instance(T.GAME_CASES[n][0]))]
     assert len(rows) == 9
     for name in rows:
         wseed = T.GAME_CASES[name][2][0]
