@@ -337,6 +337,17 @@ int mz_worker_think_stats(mz_worker* w, uint64_t* steps, uint64_t* walks, uint64
  * external-evaluator worker and on a match worker.
  * The counters: moves handed to the re-root, those that kept a subtree, and the sum of the kept roots' visits (simulations the next searches did not run). */
 int mz_worker_think_reuse_stats(mz_worker* w, uint64_t* reroots, uint64_t* kept, uint64_t* kept_visits);
+
+/* Symmetry averaging of the batched think (mz_think_symmetries=8, default 1; fixed at creation).  With 8, every leaf that is a query is
+ * evaluated under all eight symmetries of the board in the step's one forward (8 x games x B rows), and its policy, logits and value are the f32 sums over
+ * r = 0 .. 7, in that order, of the network's outputs read back into the board's frame (getRotateAction), times 0.125f; the candidates and the backup then run as
+ * ever.  The rotation that actor_use_random_rotation_features=true draws per walk is still drawn (the generator's stream stays that of the key at 1) and not
+ * used.  The reference evaluates a leaf under one rotation, so records made with 8 are not the reference's.  Refused by name (MZ_ERR_ARG, the text names the
+ * key): a value other than 1 or 8; 8 without mz_manual_step=true or with a batch size below 2 (and so wherever the batched think is refused); 8 on a game
+ * whose rotation tables are the identity (Hex, Havannah: the text names the game too); 8 on an external-evaluator worker and on a match worker.
+ * The counters, since the worker was created: queries, the leaves evaluated through the batched think (mz_worker_think_stats's third field), and rows, the
+ * network rows computed for them: 8 per query with the key at 8, 1 per query otherwise.  Either pointer may be NULL. */
+int mz_worker_think_symmetry_stats(const mz_worker* w, long long* queries, long long* rows);
 /* the worker's network (lane 0's); NULL on an external evaluator and on a match (whose networks are fixed and take turns: there is no handle to reload) */
 mz_net* mz_worker_net(mz_worker* w);
 

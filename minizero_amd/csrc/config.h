@@ -99,6 +99,11 @@ struct WorkerConfig {
     // mz_worker_act as the tree of the next search, which then runs n + 1 - (visits kept) simulations.  The reference clears the tree
     // (zero_actor.cpp:29-34), so the records are not the reference's: opt-in, refused by name wherever the batched think does not run
     bool mz_think_reuse_tree = false;
+    // not a reference key: 1 (default) or 8.  With 8 the batched think evaluates every leaf under all eight symmetries of the board and averages policy,
+    // logits and value in the board's own frame, in f32 in the order r = 0 .. 7.  The reference evaluates a leaf under one rotation
+    // (zero_actor.cpp:56), so the records are not the reference's: opt-in, refused by name wherever the batched think does not run and on a game whose
+    // rotation tables are the identity
+    int mz_think_symmetries = 1;
     int mz_zero_copy = 3; // bit 0: kernels read their inputs from pinned host memory; bit 1: kernels write their outputs there
 
     // returns false (and sets the library error string) on an unknown key or an unparsable value,

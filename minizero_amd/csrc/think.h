@@ -9,6 +9,11 @@
 //   think_reroot_kernel          (mz_think_reuse_tree) one wave per game after a move: the subtree of the move played is compacted to the front of the
 //                                game's node range and becomes the tree of the next search (the kept nodes' position slots move down with them); any
 //                                other game is left alone or cleared
+// mz_think_symmetries=8 puts two more launches around the forward, which then runs over 8 * games * B samples:
+//   think_sym_planes_kernel      one wave per (query, r = 1 .. 7): the bit-packed planes of the leaf (written under rotation 0) gathered through
+//                                GoDevView::inv[r] into block r of the feature buffer, laid out [8][games][B] — block 0 is the buffer of the key at 1
+//   think_sym_reduce_kernel      one wave per query: policy, logit and value of the eight rows read through GoDevView::fwd and summed in f32 in the
+//                                order r = 0 .. 7, times 0.125f, into the row the candidate kernel reads (with rotation 0)
 // The node records keep their layout: the virtual loss is an array of its own beside them, allocated here.
 #pragma once
 #include "go_dev.h"
@@ -43,9 +48,10 @@ class ThinkDevice {
 public:
     virtual ~ThinkDevice() = default;
     // reuse: mz_think_reuse_tree — the scratch of the re-root (one int per node, a worklist of n + 2 entries per game) is allocated only then
-    virtual int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg, bool reuse) = 0;
+    // symmetries: mz_think_symmetries, 1 or 8 — the feature buffer and the heads' outputs hold eight blocks only with 8
+    virtual int init(int device, hipStream_t stream, const Pool& pool, const GoDevView& gv, int B, const mz_search_cfg& cfg, bool reuse, int symmetries = 1) = 0;
     virtual int clearAsync() = 0;                             // a new search: no virtual loss anywhere
-    virtual uint8_t* hostRot() = 0;                           // [games][B], uploaded by stepAsync
+    virtual uint8_t* hostRot() = 0;                           // [games][B], uploaded by stepAsync (with eight symmetries the draws are made and not used: every leaf is written under rotation 0)
     // one step of every game: select, leaves, forward, candidates, expand + backup, then the status words on their way to hostStatus()
     virtual int stepAsync(Pool& pool, const GoDevView& gv, Net& net) = 0;
     virtual const int* hostStatus() const = 0;                // valid after the stream has been waited for

@@ -189,6 +189,12 @@ public:
         if (kept_visits) { *kept_visits = reuse_kept_visits_; }
         return MZ_OK;
     }
+    int thinkSymmetryStats(long long* queries, long long* rows) const
+    {
+        if (queries) { *queries = static_cast<long long>(think_queries_); }
+        if (rows) { *rows = static_cast<long long>(think_rows_); }
+        return MZ_OK;
+    }
     int getStats(mz_worker_stats* out)
     {
         *out = stats_;
@@ -305,6 +311,11 @@ private:
     std::vector<int> think_kept_;          // root visits of the tree game g keeps for its next search (0: none, reset_search clears as ever)
     std::vector<uint8_t> think_moved_;     // the tree of game g was re-rooted or cleared since its last decision: the chosen child is no longer a root child
     uint64_t reuse_reroots_ = 0, reuse_kept_ = 0, reuse_kept_visits_ = 0; // moves given to the re-root, those that kept a subtree, the visits of the kept roots
+    // mz_think_symmetries: 8 = every query's leaf is evaluated under the eight symmetries of the board and averaged (think_sym_planes_kernel,
+    // think_sym_reduce_kernel around the step's forward); the rotations thinkCycle draws are then drawn for the generator's sake alone
+    int think_sym_ = 1;
+    uint64_t think_rows_ = 0;              // network rows computed for the queries: think_sym_ per query
+    int symRefusal(const char* where) const;
     int thinkReroot(int g, int action); // g < 0: every game; action -1 clears
     int reuseRefusal(const char* where) const;
     int thinkRefusal() const;
@@ -463,6 +474,7 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     if (external_) { ext_ev_ = *ext; }
     if (device >= 0 && device < 64) { counted_device_ = device; g_workers_on_device[device].fetch_add(1); }
     if (cfg_.mz_think_reuse_tree && (external_ || match_)) { return reuseRefusal(external_ ? "external" : "match"); }
+    if (cfg_.mz_think_symmetries != 1 && (external_ || match_)) { return symRefusal(external_ ? "external" : "match"); }
     if (external_) { int rx = extRefusal(); if (rx) { return rx; } }
     if (match_) { int rm = matchRefusal(); if (rm) { return rm; } }
     if (cfg_.nn_type_name == "muzero" && desc.type == 0) { setError("nn_type_name=muzero but the network descriptor is alphazero"); return MZ_ERR_ARG; }
@@ -478,6 +490,8 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     if (thinkB_ > 1) { int rt = thinkRefusal(); if (rt) { return rt; } }
     if (cfg_.mz_think_reuse_tree) { int rt = reuseRefusal(nullptr); if (rt) { return rt; } }
     think_reuse_ = cfg_.mz_think_reuse_tree;
+    if (cfg_.mz_think_symmetries != 1) { int rt = symRefusal(nullptr); if (rt) { return rt; } }
+    think_sym_ = cfg_.mz_think_symmetries;
     G_ = cfg_.zero_num_parallel_games;
     A_ = desc.action_size;
     n_ = cfg_.actor_num_simulation;
@@ -498,6 +512,18 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
     held_.assign(G_, Held());
     noise_policy_.resize(GA); noise_logit_.resize(GA); noise_noise_.resize(GA);
     if ((rc = createActors())) { return rc; }
+    if (think_sym_ == 8) { // the eight views of a leaf have to be eight different maps: decided from the game's own tables, not from its name
+        const RotationTables* rt = games_[0].env->rot();
+        bool distinct = rt != nullptr;
+        for (int a = 0; a < 8 && distinct; ++a) {
+            for (int b = a + 1; b < 8 && distinct; ++b) { distinct = rt->inv[a] != rt->inv[b] && rt->fwd[a] != rt->fwd[b]; }
+        }
+        if (!distinct) {
+            setError("mz_think_symmetries=8 with env_game=%s: the game has no eight symmetries (its rotation tables are not eight different maps), so the eight views of a leaf would be one",
+                     cfg_.env_game.c_str());
+            return MZ_ERR_ARG;
+        }
+    }
     plan_ = resolvePlan(match_ ? 2 : std::max(1, cfg_.mz_pipeline_lanes));
     if (match_) {
         // one plan serves both lanes and every step: the two sides' networks (the first lane holds both) must ask for the same one
@@ -555,7 +581,7 @@ int Worker::init(int device, const char* conf, const mz_net_desc& desc, const fl
         Lane& L = *lanes_[0];
         if (!createThinkDevice) { setError("actor_mcts_think_batch_size=%d: this build has no device code for the batched think", thinkB_); return MZ_ERR_DEVICE; }
         think_.reset(createThinkDevice());
-        if ((rc = think_->init(device_, L.stream, L.pool, L.godev.v_, thinkB_, sc, think_reuse_))) { return rc; }
+        if ((rc = think_->init(device_, L.stream, L.pool, L.godev.v_, thinkB_, sc, think_reuse_, think_sym_))) { return rc; }
         think_kept_.assign(G_, 0);
         think_moved_.assign(G_, 0);
         think_count_.assign(G_, 0);
@@ -669,6 +695,19 @@ int Worker::reuseRefusal(const char* where) const
     if (thinkB_ < 2) { setError("mz_think_reuse_tree=true with actor_mcts_think_batch_size=%d: the option keeps the trees of the batched think (a batch size of 2 to %d)", cfg_.actor_mcts_think_batch_size, kThinkMaxBatch); return MZ_ERR_ARG; }
     if (cfg_.actor_use_dirichlet_noise) { setError("mz_think_reuse_tree=true with actor_use_dirichlet_noise=true: noise on a root that is already expanded needs a rule of its own"); return MZ_ERR_ARG; }
     if (cfg_.actor_use_gumbel_noise) { setError("mz_think_reuse_tree=true with actor_use_gumbel_noise=true: noise on a root that is already expanded needs a rule of its own"); return MZ_ERR_ARG; }
+    return MZ_OK;
+}
+
+// mz_think_symmetries=8: the averaging is a part of the batched think's step; where that does not run it is refused by name when the worker is created (the
+// game's own refusal, which needs the rotation tables, follows createActors in init)
+int Worker::symRefusal(const char* where) const
+{
+    const int s = cfg_.mz_think_symmetries;
+    if (where && where[0] == 'e') { setError("mz_think_symmetries=%d: an external evaluator does not run the batched think, whose leaves the key evaluates under eight symmetries", s); return MZ_ERR_ARG; }
+    if (where) { setError("mz_think_symmetries=%d: a match plays on its own, one simulation at a time (the key belongs to the batched think)", s); return MZ_ERR_ARG; }
+    if (s != 8) { setError("mz_think_symmetries=%d: 1 (one view per leaf) or 8 (all eight symmetries of the board)", s); return MZ_ERR_ARG; }
+    if (!cfg_.mz_manual_step) { setError("mz_think_symmetries=8 without mz_manual_step=true: the key belongs to the batched think, which only a manually stepped worker runs"); return MZ_ERR_ARG; }
+    if (thinkB_ < 2) { setError("mz_think_symmetries=8 with actor_mcts_think_batch_size=%d: the key belongs to the batched think (a batch size of 2 to %d)", cfg_.actor_mcts_think_batch_size, kThinkMaxBatch); return MZ_ERR_ARG; }
     return MZ_OK;
 }
 
@@ -2090,6 +2129,7 @@ int Worker::thinkCycle()
         if (st[g * 4 + 1] != bs[g]) { setError("think: game %d walked %d times in a step of %d", g, st[g * 4 + 1], bs[g]); return MZ_ERR_STATE; }
         ++think_steps_; think_walks_ += bs[g]; think_queries_ += st[g * 4 + 2];
         stats_.leaf_evals += st[g * 4 + 2];
+        think_rows_ += uint64_t(think_sym_) * st[g * 4 + 2];
         first = first || think_count_[g] == 0;
         think_count_[g] = st[g * 4 + 0];
         finished = finished || think_count_[g] == n_ + 1;
@@ -2613,7 +2653,7 @@ int Worker::command(const std::string& line) // ref actor_group.cpp:200-252
         MZ_FIXED(actor_gumbel_sigma_visit_c) MZ_FIXED(actor_gumbel_sigma_scale_c) MZ_FIXED(zero_num_threads) MZ_FIXED(zero_num_parallel_games)
         MZ_FIXED(nn_type_name) MZ_FIXED(env_board_size) MZ_FIXED(env_go_komi) MZ_FIXED(env_go_ko_rule) MZ_FIXED(env_game) MZ_FIXED(atari_init_q)
         MZ_FIXED(env_atari_name) MZ_FIXED(env_atari_episode_length) MZ_FIXED(mz_pipeline_lanes) MZ_FIXED(mz_rng_streams) MZ_FIXED(mz_cpu_base) MZ_FIXED(mz_signal_wait)
-        MZ_FIXED(mz_sim_kernel) MZ_FIXED(mz_sim_cluster) MZ_FIXED(mz_sim_split) MZ_FIXED(mz_sim_rounds) MZ_FIXED(mz_sim_round_min) MZ_FIXED(mz_sim_round_alt) MZ_FIXED(mz_sim_round_batch) MZ_FIXED(mz_sim_rounds_board) MZ_FIXED(mz_sim_round_pairs) MZ_FIXED(mz_sim_round_leaves) MZ_FIXED(mz_manual_step) MZ_FIXED(mz_nn_precision) MZ_FIXED(mz_raw_observations) MZ_FIXED(mz_device_env) MZ_FIXED(mz_zero_copy) MZ_FIXED(mz_think_reuse_tree)
+        MZ_FIXED(mz_sim_kernel) MZ_FIXED(mz_sim_cluster) MZ_FIXED(mz_sim_split) MZ_FIXED(mz_sim_rounds) MZ_FIXED(mz_sim_round_min) MZ_FIXED(mz_sim_round_alt) MZ_FIXED(mz_sim_round_batch) MZ_FIXED(mz_sim_rounds_board) MZ_FIXED(mz_sim_round_pairs) MZ_FIXED(mz_sim_round_leaves) MZ_FIXED(mz_manual_step) MZ_FIXED(mz_nn_precision) MZ_FIXED(mz_raw_observations) MZ_FIXED(mz_device_env) MZ_FIXED(mz_zero_copy) MZ_FIXED(mz_think_reuse_tree) MZ_FIXED(mz_think_symmetries)
         // a match's length, names and arithmetic are part of its records and its tally from step 0 (every other worker never reads the five keys)
         MZ_FIXED(mz_match_games) MZ_FIXED(mz_match_name_a) MZ_FIXED(mz_match_name_b) MZ_FIXED(mz_match_precision_a) MZ_FIXED(mz_match_precision_b)
         if (match_) { MZ_FIXED(zero_actor_intermediate_sequence_length) }
@@ -2852,6 +2892,11 @@ int mz_worker_think_reuse_stats(mz_worker* w, uint64_t* reroots, uint64_t* kept,
 {
     if (!w) { mz::setError("think_reuse_stats: NULL argument"); return MZ_ERR_ARG; }
     return w->w.thinkReuseStats(reroots, kept, kept_visits);
+}
+int mz_worker_think_symmetry_stats(const mz_worker* w, long long* queries, long long* rows)
+{
+    if (!w) { mz::setError("think_symmetry_stats: NULL argument"); return MZ_ERR_ARG; }
+    return w->w.thinkSymmetryStats(queries, rows);
 }
 int mz_worker_think_stats(mz_worker* w, uint64_t* steps, uint64_t* walks, uint64_t* queries)
 {

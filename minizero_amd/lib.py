@@ -169,6 +169,8 @@ def load():
             L.mz_worker_env_query.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_float)]
         if hasattr(L, "mz_worker_think_reuse_stats"):  # (likewise: a build from before mz_think_reuse_tree)
             L.mz_worker_think_reuse_stats.argtypes = [vp] + [C.POINTER(C.c_uint64)] * 3
+        if hasattr(L, "mz_worker_think_symmetry_stats"):  # (likewise: a build from before mz_think_symmetries)
+            L.mz_worker_think_symmetry_stats.argtypes = [vp] + [C.POINTER(C.c_longlong)] * 2
         L.mz_worker_search_done.argtypes = [vp]
         L.mz_worker_search_action.argtypes = [vp, C.c_int, ip, ip, ip]
         L.mz_worker_act.argtypes = [vp, C.c_int, C.c_int, C.c_int]
@@ -567,6 +569,13 @@ class Worker:
         r, k, v = C.c_uint64(), C.c_uint64(), C.c_uint64()
         _check(self.L, self.L.mz_worker_think_reuse_stats(self.h, C.byref(r), C.byref(k), C.byref(v)))
         return r.value, k.value, v.value
+
+    def think_symmetry_stats(self):
+        """(queries, rows) of the batched think: the leaves evaluated and the network rows computed for them — 8 per query with mz_think_symmetries=8, 1 per
+        query otherwise; zeros where the batched think does not run"""
+        q, r = C.c_longlong(), C.c_longlong()
+        _check(self.L, self.L.mz_worker_think_symmetry_stats(self.h, C.byref(q), C.byref(r)))
+        return q.value, r.value
 
     def search_done(self):
         return _check(self.L, self.L.mz_worker_search_done(self.h)) == 1

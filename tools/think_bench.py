@@ -16,6 +16,11 @@ the kept roots over moves * (n + 1)), "reroots", "kept", "moves".  --policy-gain
 give a nearly flat prior and keep little; a sharpened prior keeps one line, as a trained network does.
 
     python tools/think_bench.py --board 9 --n 1600 --B 32 --game-moves 30 --reuse on --runs 5
+
+--symmetries 8 sets mz_think_symmetries=8 (every leaf evaluated under the eight symmetries of the board and averaged; B >= 2) in either mode and adds
+"rows", the network rows computed; with 1, the default, the key is left out of the configuration, so that a build from before it can be measured.
+
+    python tools/think_bench.py --board 19 --n 400 --B 8,16,32,64 --symmetries 8 --runs 5
 """
 import argparse
 import json
@@ -45,11 +50,15 @@ def sharpen_policy(d, w, gain):
     return w
 
 
+def sym_key(a):
+    return f":mz_think_symmetries={a.symmetries}" if a.symmetries != 1 else ""
+
+
 def play_game(a, d, w, B, reuse):
     s = a.board
     conf = (f"env_game=go:env_board_size={s}:actor_num_simulation={a.n}:zero_num_parallel_games=1:mz_manual_step=true:program_seed=1:nn_file_name=bench.pt"
             f":zero_num_threads=1:actor_use_dirichlet_noise=false:actor_resign_threshold=-2:actor_select_action_by_count=true:actor_select_action_by_softmax_count=false"
-            f":actor_mcts_think_batch_size={B}" + (":mz_think_reuse_tree=true" if reuse else ""))
+            f":actor_mcts_think_batch_size={B}" + (":mz_think_reuse_tree=true" if reuse else "") + sym_key(a))
     wk = mz.Worker(conf, d, w)
     wk.command("start")
     moves = 0
@@ -77,7 +86,7 @@ def game_mode(a, d, w):
         r = runs[-1]
         row = dict(tag=a.tag, board=a.board, n=a.n, B=B, reuse=a.reuse, policy_gain=a.policy_gain, moves=r["moves"],
                    ms_per_move=[round(x["ms"] / max(1, x["moves"]), 3) for x in runs], sims_per_move=round(r["think"][2] / max(1, r["moves"]), 1),
-                   kept_share=round(r["reuse"][2] / (max(1, r["moves"]) * (a.n + 1)), 4), reroots=r["reuse"][0], kept=r["reuse"][1])
+                   kept_share=round(r["reuse"][2] / (max(1, r["moves"]) * (a.n + 1)), 4), reroots=r["reuse"][0], kept=r["reuse"][1], symmetries=a.symmetries)
         print(json.dumps(row), flush=True)
 
 
@@ -94,6 +103,7 @@ def main():
     ap.add_argument("--b1-extra", default="", help="configuration keys added for B = 1 only, e.g. :mz_sim_kernel=false where the simulation kernel has no room for n")
     ap.add_argument("--game-moves", type=int, default=0, help="play this many moves of one game by think(with_play) instead of timing single thinks")
     ap.add_argument("--reuse", choices=("on", "off"), default="off", help="mz_think_reuse_tree of the game mode")
+    ap.add_argument("--symmetries", type=int, choices=(1, 8), default=1, help="mz_think_symmetries: 8 evaluates every leaf under the board's eight symmetries (B >= 2)")
     ap.add_argument("--policy-gain", type=float, default=1.0, help="the policy head's last layer times this (game mode)")
     a = ap.parse_args()
     s = a.board
@@ -103,7 +113,7 @@ def main():
         return game_mode(a, d, sharpen_policy(d, w, a.policy_gain) if a.policy_gain != 1.0 else w)
     for B in (int(x) for x in a.B.split(",")):
         conf = (f"env_game=go:env_board_size={s}:actor_num_simulation={a.n}:zero_num_parallel_games=1:mz_manual_step=true:program_seed=1:nn_file_name=bench.pt"
-                f":zero_num_threads=1:actor_mcts_think_batch_size={B}" + (a.b1_extra if B == 1 else ""))
+                f":zero_num_threads=1:actor_mcts_think_batch_size={B}" + (a.b1_extra if B == 1 else "") + sym_key(a))
         wk = mz.Worker(conf, d, w)
         wk.command("start")
         ms, tree_ms, tree_entries = [], [], 0
@@ -121,8 +131,10 @@ def main():
                     tree_ms.append(round((time.perf_counter() - t1) * 1e3, 3))
         steps, walks, queries = wk.think_stats() if hasattr(wk.L, "mz_worker_think_stats") else (0, 0, 0)
         sim_launches = wk.stats()["sim_launches"]
+        rows = wk.think_symmetry_stats()[1] if hasattr(wk.L, "mz_worker_think_symmetry_stats") else queries
         wk.close()
-        row = dict(tag=a.tag, board=s, n=a.n, B=B, extra=a.b1_extra if B == 1 else "", sim_launches=sim_launches, ms=ms, steps=steps, walks=walks, queries=queries)
+        row = dict(tag=a.tag, board=s, n=a.n, B=B, extra=a.b1_extra if B == 1 else "", sim_launches=sim_launches, ms=ms, steps=steps, walks=walks, queries=queries,
+                   symmetries=a.symmetries, rows=rows)
         if a.tree:
             row.update(tree_ms=tree_ms, tree_entries=tree_entries)
         print(json.dumps(row), flush=True)
